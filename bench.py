@@ -20,7 +20,7 @@ Consecutive passes run side by side on `--streams` HIP streams (default 3), one 
 as a hipGraph it captured on its own library handles (xai_engine/streams.py): the same kernels on the same shapes, so the maps are
 bit-identical to the one-stream run, while the low-occupancy layers of one pass overlap another pass's work.
 `--mode throughput` is the fastest configuration instead (the shipped MIOpen find-db's solvers, which include split-K kernels
-that are not run-to-run reproducible, and 2 images per pass); at N = 1 the default run measures it in a child process and
+that are not run-to-run reproducible, and 2 images per pass); at N = 1 a `--full` run measures it in a child process and
 reports it as `throughput_mode`.
 
 `--workload sweep` (opt-in; the driver's contract line is the default `ig` workload) measures north_star's scaling
@@ -28,10 +28,15 @@ target instead: the insertion/deletion sweep of BASELINE config 5 over ONE fixed
 (strong scaling: image i belongs to rank i % world, the list does not grow with N), every image attributed with each of
 `--sweep-methods` and pushed through the ten metrics (224 steps each); one 96-byte all-reduce per method; value = images/s.
 
+A plain run sets up, warms up, times the `--steps` steps and prints the line; `--dump-outputs DIR` then also writes what the last
+timed step returned (rank 0's attributions and |sum_c| maps, float32 .npy; for `--workload sweep` the per-method metric means,
+float64) so that two builds can be compared output for output on the same seeded inputs.
+
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline        the IG accumulation kernel (xai_ig_accum_f32): algorithmic bytes per launch ((S+2)*4N per image, SURVEY
                   8(d)) / mean launch duration measured with HIP events inside the timed steps, against the 8 TB/s HBM peak
   parity_mode     says whether the headline IS the parity configuration (it is by default), and repeats its figures
+With `--full` (off by default) the run goes on after the headline and measures the side legs below, each with runs of its own:
   single_stream   the same step with every pass on one stream (what the stream overlap buys)
   reference_api   the same 32 images as 32 calls of the reference's one-image signature IG(input, model, 50, 50, 1, 0, device, t),
                   issued serially and round-robin on the streams
@@ -42,7 +47,7 @@ Rank 0 prints ONE JSON line.  Extra objects:
                   per image, one 96-byte all-reduce; images/s = list length / max-over-ranks time
   cpu_baseline    the CPU oracle (oracle/ig.py, a port of the reference's IG) on the host cores,
                   a bounded sample (four attributions), rank 0 at N=1 only
-`--lean` skips every side leg (single_stream ... cpu_baseline).
+`--lean` leaves them out of a `--full` run again (single_stream ... cpu_baseline).
 """
 import argparse
 import json
@@ -61,6 +66,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 
 HBM_COPY_GBS = 6290.0          # the guide's measured float4 copy (read + write); a read-only stream reaches 6.75 TB/s on this part
 STEPS_IG, C, H, W = 50, 3, 224, 224
 N_ELEM = C * H * W
+DUMP_BYTES = 64 * 2 ** 20      # --dump-outputs writes at most this much
 
 
 def parse():
@@ -74,9 +80,13 @@ def parse():
                          "classifier pass -- the configuration of the parity tests; throughput: the shipped find-db's solvers, 2 images per pass")
     ap.add_argument("--streams", type=int, default=3, help="HIP streams consecutive classifier passes (sweep: consecutive images) are queued on")
     ap.add_argument("--images-per-pass", type=int, default=None, help="images x 50 interpolants per classifier pass (default: 1 parity / 2 throughput)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the side legs: single_stream, reference_api, "
+                    "unfused_classifier, throughput_mode, sweep_strong and cpu_baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to "
+                    "DIR/<name>.npy (rank 0 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--lean", action="store_true", help="headline + roofline only: skip single_stream, reference_api, unfused_classifier, "
-                    "throughput_mode, sweep_strong and cpu_baseline")
+    ap.add_argument("--lean", action="store_true", help="with --full: headline + roofline only, skip single_stream, reference_api, "
+                    "unfused_classifier, throughput_mode, sweep_strong and cpu_baseline")
     ap.add_argument("--strong-images", type=int, default=256, help="length of the fixed image list of the sweep_strong leg (IG + ten metrics "
                     "per image, image i -> rank i %% N); 0 = skip the leg")
     ap.add_argument("--workload", choices=["ig", "sweep"], default="ig", help="ig = BASELINE config 2 (the contract line); sweep = config 5, "
@@ -95,6 +105,7 @@ def parse():
                     "(image-classification-xai_amd/miopen_db, recorded by one exhaustive find of this workload on an MI355X) so that find mode "
                     "costs no search time; 0 = immediate mode")
     args = ap.parse_args()
+    args.side_legs = args.full and not args.lean
     throughput = args.mode == "throughput"
     if args.deterministic is None:
         args.deterministic = 0 if throughput else 1
@@ -151,6 +162,16 @@ def cpu_baseline():
                       f"{', '.join(f'{t:.2f}' for t in times)} s"}
 
 
+def dump_outputs(out_dir, arrays):
+    """{name: array} -> out_dir/<name>.npy, float32 kept, anything else as float64"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+    log(f"outputs written to {out_dir}: " + ", ".join(f"{k}{tuple(v.shape)}" for k, v in arrays.items()))
+
+
 class SyntheticImages:
     """Fixed global list of synthetic images (seed 1000 + i), generated on access: every rank sees
     the same list whatever the world size, and only its own images are ever materialised."""
@@ -196,6 +217,9 @@ def run_sweep_workload(args, model, dev, rank, world, prep, miopen_mode, fence, 
         means = one_pass(images)
     fence()
     dt = max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        dump_outputs(args.dump_outputs, {f"sweep_{m}_metric_means": np.array([means[m][k] for k in KEYS], dtype=np.float64) for m in methods})
     if rank == 0:
         n = len(images)
         print(json.dumps({
@@ -376,12 +400,16 @@ def main():
     log("warmup done; timing")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(events)
+        out = step(events)
     fence()
     dt = max_over_ranks(time.perf_counter() - t0)
     from xai_engine.ig import PASS_COUNTS
     how = dict(PASS_COUNTS)
     log(f"timed {args.steps} steps in {dt:.3f} s ({world * B * args.steps / dt:.1f} attributions/s); classifier passes so far: {how}")
+    if rank == 0 and args.dump_outputs:                # what ig_batch handed back in the last timed step: (B,C,H,W) maps, (B,H,W) |sum_c|
+        k = min(B, DUMP_BYTES // ((N_ELEM + H * W) * 4))  # the first k images (all 32 by default: 25.7 MB)
+        dump_outputs(args.dump_outputs, {"ig_attributions": out[0][:k], "ig_abs_channel_sum": out[1][:k]})
+    del out
 
     algo_bytes = B * (STEPS_IG + 2) * 4 * N_ELEM + B * H * W * 4      # read S grads + x, write out (+ |sum_c| map); b is a scalar
     # two HIP-event timings of the accumulation launches of the timed steps: events bracketing each launch (they include the
@@ -397,7 +425,7 @@ def main():
     achieved = algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
 
     single = api = unfused = strong = None
-    if not args.lean:
+    if args.side_legs:
         if args.streams > 1:
             step(streams=1)
             d1 = timed(lambda: step(streams=1), 2)
@@ -480,7 +508,7 @@ def main():
                                      "tests/test_gpu_configs.py::test_classifier_passes_on_several_streams_are_bit_identical_to_one_stream)") if parity_cfg else
                                     "this run is NOT the parity configuration (see config.mode / config.miopen / config.images_per_pass)"},
         }
-        if not args.lean:
+        if args.side_legs:
             line.update({"single_stream": single, "reference_api": api, "unfused_classifier": unfused, "sweep_strong": strong})
             if world == 1 and args.mode == "parity":
                 torch.cuda.empty_cache()

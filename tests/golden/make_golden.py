@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Generate the golden input/output vectors under tests/golden/ by IMPORTING the
-reference (read-only, /root/reference) in the build container and running it on
+reference (a read-only checkout of the original project, named by XAI_REFERENCE_ROOT) and running it on
 small seeded inputs.  The reference itself never travels: only the .npz data does.
 
-Run once, here (no GPU needed):
+Run once, where a checkout of the reference is at hand (no GPU needed):
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+    XAI_REFERENCE_ROOT=<reference checkout> PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 
 What is pinned (reference file:line in brackets):
   ig_small.npz / ig_224.npz   IG, Left-IG, IDG, IDGI outputs + per-step gradients/logits
@@ -49,7 +49,9 @@ import torch
 import torch.nn as nn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+REF = os.environ.get("XAI_REFERENCE_ROOT")
+if not REF or not os.path.isdir(REF):
+    sys.exit("make_golden.py: set XAI_REFERENCE_ROOT to the root of a checkout of the reference project")
 
 sys.dont_write_bytecode = True
 sys.path.insert(0, REF)

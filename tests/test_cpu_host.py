@@ -177,6 +177,7 @@ import os, sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
 import numpy as np, torch, torch.distributed as dist
 from xai_engine import dist as xd, sweep
+torch.cuda.is_available = lambda: False         # CPU ranks, also on a box with one GPU (rank r would otherwise take cuda:r)
 rank, world, device = xd.init_from_env("gloo")
 assert world == 2 and device.type == "cpu"
 # (1) image sharding + the 12-element all-reduce (10 sums, images, seconds in attribution)
@@ -250,6 +251,7 @@ import os, sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
 import numpy as np, torch, torch.distributed as dist
 from xai_engine import dist as xd, sweep, harness
+torch.cuda.is_available = lambda: False         # CPU ranks, also on a box with one GPU (rank r would otherwise take cuda:r)
 rank, world, device = xd.init_from_env("gloo")
 assert world == 8 and device.type == "cpu"
 # (1) BASELINE config 5 at 8 ranks: 1000 images round-robin, every image owned once, the 12-element all-reduce

@@ -859,7 +859,7 @@ def _bench(*flags, ranks=1):
 def test_bench_contract_line_with_one_and_four_ranks():
     """bench.py's N > 1 control flow (launcher, barrier, max-over-ranks, rank-0 print, every leg of the line) rehearsed on the one
     GPU of the test box: four ranks share cuda:0 over gloo (XAI_DIST_BACKEND / XAI_FORCE_DEVICE -- never set by the driver)."""
-    small = ("--steps", "1", "--warmup", "1", "--images", "4", "--no-cpu-baseline", "--strong-images", "4")
+    small = ("--full", "--steps", "1", "--warmup", "1", "--images", "4", "--no-cpu-baseline", "--strong-images", "4")
     one, _ = _bench(*small, ranks=1)
     two, out4 = _bench(*small, ranks=4)
     assert out4.strip().splitlines()[-1].startswith("{")                   # the JSON line is the LAST line on stdout
@@ -889,6 +889,23 @@ def test_bench_contract_line_with_one_and_four_ranks():
     assert "cpu_baseline" not in two
     # four ranks on ONE card: the aggregate can only be about what one rank gets alone (one 4-image step each: a loose band)
     assert 0.2 <= two["value"] / one["value"] <= 2.5, (one["value"], two["value"])
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without any side leg; --dump-outputs writes what the last timed step
+    returned: the (B,C,H,W) attributions and the (B,H,W) |sum_c| maps, float32, the second the channel sum of the first."""
+    import numpy as np
+    line, _ = _bench("--steps", "2", "--warmup", "1", "--images", "4", "--dump-outputs", str(tmp_path / "out"))
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "attributions/s" and line["dtype"] == "f32"
+    assert abs(line["value"] - 4 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["roofline"]["launches_timed"] == 2 and line["parity_mode"]["is_headline"] is True
+    for k in ("single_stream", "reference_api", "unfused_classifier", "sweep_strong", "throughput_mode", "cpu_baseline"):
+        assert k not in line, k
+    att = np.load(tmp_path / "out" / "ig_attributions.npy")
+    amap = np.load(tmp_path / "out" / "ig_abs_channel_sum.npy")
+    assert att.dtype == amap.dtype == np.float32 and att.shape == (4, 3, 224, 224) and amap.shape == (4, 224, 224)
+    assert np.isfinite(att).all() and np.abs(att).max() > 0
+    check("bench/dump_abs_channel_sum", amap, np.abs(att.sum(1)), 1e-5, "|sum_c| of the dumped attributions")
 
 
 def test_bench_sweep_workload_is_strong_scaling_over_one_fixed_list():

@@ -443,3 +443,113 @@ def bn_relu_maxpool_fwd(x, weight, bias, mean, var, eps, variant, kernel, stride
     _call("xai_bn_relu_maxpool_fwd_f32", x.device, _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(var), float(eps), int(variant),
           N, Cc, H, W, PH, PW, int(kernel), int(stride), int(pad), _ptr(y))
     return y
+
+
+# ------------------------------------------------------------------------------ ViT explainers (K17-K21)
+def _image0(t, name, dim):
+    """(B, *rest) or (*rest) float32 device tensor -> image 0 as a contiguous (*rest) tensor (a copy only if it is strided)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+    if t.dim() == dim + 1:
+        t = t[0]
+    if t.dim() != dim:
+        raise ValueError(f"{name} must have {dim} dimensions (or {dim + 1} with a leading image axis), got {tuple(t.shape)}")
+    return _need(t.contiguous(), F32, name)
+
+
+def _table(tensors, dev):
+    """device array of the tensors' data pointers (the pointer-table argument of K17, K18, K20); the caller keeps it referenced
+    until the launch is issued.  Staged through pinned memory and copied asynchronously on the current stream: no host sync."""
+    host = torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).pin_memory()
+    return host.to(dev, non_blocking=True)
+
+
+def _per_block(ts, name, dim):
+    ts = [_image0(t, f"{name}[{l}]", dim) for l, t in enumerate(ts)]
+    if not ts:
+        raise ValueError(f"{name}: no blocks")
+    if any(t.shape != ts[0].shape or t.device != ts[0].device for t in ts):
+        raise ValueError(f"{name}: every block must have the same shape and device")
+    return ts
+
+
+def attn_head_importance(attns, grads):
+    """K17: per-block attention maps and their gradients, L tensors (H,S,S) each (or (B,H,S,S): image 0) -> Ih (L,H), the mean of
+    |A_h^T G_h| over its S x S entries, normalised to sum 1 over the heads of each block."""
+    attns, grads = _per_block(attns, "attns", 3), _per_block(grads, "grads", 3)
+    if len(attns) != len(grads) or attns[0].shape != grads[0].shape:
+        raise ValueError("attns and grads must be the same number of equally shaped blocks")
+    dev = attns[0].device
+    L, (H, S, _) = len(attns), attns[0].shape
+    Ih = torch.empty((L, H), dtype=F32, device=dev)
+    nbytes = _lib.load().xai_attn_head_importance_workspace_bytes(L, H, S)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    atab, gtab = _table(attns, dev), _table(grads, dev)        # held until the launch: a freed table's block is reused at once
+    _call("xai_attn_head_importance_f32", dev, _ptr(atab), _ptr(gtab), L, H, S, _ptr(Ih), _ptr(ws), nbytes)
+    return Ih
+
+
+def rave_matrices(attns, Ih, b1, b2, bgrads=None, ablate=0):
+    """K18: the row-normalised InFlow matrices (L,S,S) of compute_RAVE from the blocks' attention maps (L tensors (H,S,S)), their head
+    importance Ih (L,H), the residual shares b1, b2 (L,2,S) and, for withgrad, the blocks' bottom-up attention gradients."""
+    if ablate not in (0, 1):
+        raise ValueError("ablate must be 0 or 1")
+    attns = _per_block(attns, "attns", 3)
+    dev = attns[0].device
+    L, (H, S, _) = len(attns), attns[0].shape
+    _need(Ih, F32, "Ih"); _need(b1, F32, "b1"); _need(b2, F32, "b2")
+    if tuple(Ih.shape) != (L, H) or tuple(b1.shape) != (L, 2, S) or tuple(b2.shape) != (L, 2, S):
+        raise ValueError(f"Ih must be ({L},{H}) and b1, b2 ({L},2,{S})")
+    gtab = None
+    if bgrads is not None:
+        bgrads = _per_block(bgrads, "bgrads", 3)
+        if len(bgrads) != L or bgrads[0].shape != attns[0].shape:
+            raise ValueError("bgrads must match attns")
+        gtab = _table(bgrads, dev)
+    aug = torch.empty((L, S, S), dtype=F32, device=dev)
+    atab = _table(attns, dev)
+    _call("xai_rave_matrices_f32", dev, _ptr(atab), _ptr(gtab), _ptr(Ih), _ptr(b1), _ptr(b2), L, H, S, int(ablate), _ptr(aug))
+    return aug
+
+
+def rollout_row(aug, target_token):
+    """K19: row `target_token` of aug[L-1] @ ... @ aug[0]; aug (L,S,S) -> (S,), or (n,L,S,S) -> (n,S)."""
+    _need(aug, F32, "aug")
+    one = aug.dim() == 3
+    a = aug[None] if one else aug
+    if a.dim() != 4 or a.shape[-1] != a.shape[-2]:
+        raise ValueError("aug must be (L,S,S) or (n,L,S,S)")
+    n, L, S, _ = a.shape
+    t = int(target_token)
+    if not -S <= t < S:
+        raise IndexError(f"target_token {target_token} out of range for {S} tokens")
+    out = torch.empty((n, S), dtype=F32, device=aug.device)
+    _call("xai_rollout_row_f32", aug.device, _ptr(a), n, L, S, t % S, _ptr(out))
+    return out[0] if one else out
+
+
+def residual_shares(inputs, attn_outs, resid1s, mlps):
+    """K20: per block the token 2-norm shares ((input, attention output), (input + attention, MLP output)), each L tensors (S,D)
+    (or (B,S,D): image 0) -> b1, b2 (L,2,S), p=1-normalised over the pair."""
+    groups = [_per_block(ts, name, 2) for ts, name in ((inputs, "inputs"), (attn_outs, "attn_outs"), (resid1s, "resid1s"), (mlps, "mlps"))]
+    L, (S, D) = len(groups[0]), groups[0][0].shape
+    if any(len(g) != L or g[0].shape != (S, D) for g in groups):
+        raise ValueError("inputs, attn_outs, resid1s and mlps must be the same number of equally shaped blocks")
+    dev = groups[0][0].device
+    b1 = torch.empty((L, 2, S), dtype=F32, device=dev)
+    b2 = torch.empty((L, 2, S), dtype=F32, device=dev)
+    tab = _table([g[l] for l in range(L) for g in groups], dev)
+    _call("xai_residual_shares_f32", dev, _ptr(tab), L, S, D, _ptr(b1), _ptr(b2))
+    return b1, b2
+
+
+def attn_cam(attn, grad):
+    """K21: cam_attn of one block, attn and grad (B,H,S,S) -> (B,S-1): min-max normalised clamp(mean_h(A*G), 0) of the CLS row's
+    token columns (NaN where the map is constant, as in the reference)."""
+    _need(attn, F32, "attn"); _need(grad, F32, "grad")
+    if attn.shape != grad.shape or attn.dim() != 4 or attn.shape[-1] != attn.shape[-2]:
+        raise ValueError("attn and grad must both be (B,H,S,S)")
+    B, H, S, _ = attn.shape
+    out = torch.empty((B, S - 1), dtype=F32, device=attn.device)
+    _call("xai_attn_cam_f32", attn.device, _ptr(attn), _ptr(grad), B, H, S, _ptr(out))
+    return out

@@ -124,6 +124,34 @@ def run(device="cuda:0", verbose=True):
     rows, wts = rnd(37, 200).abs(), rnd(37)
     wsum, psum = K.masked_sums(rows, wts)
     check("masked_sums", max(_rel(wsum, (rows.double() * wts.double()[:, None]).sum(0) / 37), _rel(psum, rows.double().sum(0) / 37)), 2e-6)
+    # K17-K21: the ViT explainers' post-backward arithmetic (Baselines.generate_RAVE / generate_cam_attn)
+    Lv, Hv, Sv, Dv = 3, 4, 50, 40
+    attns = [torch.softmax(rnd(Hv, Sv, Sv), -1) for _ in range(Lv)]
+    grads_, bgr = [rnd(Hv, Sv, Sv) for _ in range(Lv)], [rnd(Hv, Sv, Sv) for _ in range(Lv)]
+    Ih = K.attn_head_importance(attns, grads_)
+    m = torch.stack([(a.double().transpose(-1, -2) @ g.double()).abs().mean((-1, -2)) for a, g in zip(attns, grads_)])
+    check("attn_head_importance", _rel(Ih, m / m.sum(1, keepdim=True)), 1e-5)
+    streams4 = [[rnd(Sv, Dv) for _ in range(Lv)] for _ in range(4)]
+    b1, b2 = K.residual_shares(*streams4)
+    nrm = [torch.stack([t.double().norm(dim=1) for t in ts]) for ts in streams4]
+    check("residual_shares", max(_rel(b1, F.normalize(torch.stack((nrm[0], nrm[1]), 1), p=1, dim=1)),
+                                 _rel(b2, F.normalize(torch.stack((nrm[2], nrm[3]), 1), p=1, dim=1))), 1e-5)
+    aug = K.rave_matrices(attns, Ih, b1, b2, bgr, 0)
+    M = (torch.stack(attns).double() * Ih.double()[:, :, None, None]).amax(1)
+    M = (torch.stack(bgr).double().mean(1) * M).clamp(min=0)
+    b1d, b2d = b1.double(), b2.double()
+    r = M * b1d[:, 1, None, :] + torch.diag_embed(b1d[:, 0])
+    ratio = F.normalize(b2d[:, 1] / b2d[:, 0], p=1, dim=-1)
+    r = r * (ratio * b2d[:, 1] + b2d[:, 0])[:, None, :]
+    ref = r / r.sum(-1, keepdim=True)
+    check("rave_matrices", _rel(aug, ref), 1e-5)
+    joint = ref[0]
+    for i in range(1, Lv):
+        joint = ref[i] @ joint
+    check("rollout_row", _rel(K.rollout_row(aug, 3), joint[3]), 1e-5)
+    cam = K.attn_cam(attns[0][None], grads_[0][None])[0]
+    c = (attns[0].double() * grads_[0].double()).mean(0)[0, 1:].clamp(min=0)
+    check("attn_cam", _rel(cam, (c - c.min()) / (c.max() - c.min())), 1e-5)
     wrong = unprotected = 0.0
     for _ in range(3):          # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

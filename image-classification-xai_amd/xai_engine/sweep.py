@@ -32,7 +32,7 @@ from .streams import CAPTURE_LOCK
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
 CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "sg", "gc")
-VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS")
+VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
 
 def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
@@ -129,6 +129,9 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
         from .tis import TIS
         # :236-239 (n_masks is the class default, 1024, in the reference; the key exists for models with fewer channels)
         sal = TIS(model, n_masks=testing_dict.get("tis_n_masks", 1024), batch_size=64)(x, class_idx=target_class)[None]
+    elif attr_function == "InFlow":
+        # :240-242 passes option='b', which generate_RAVE does not take (a TypeError in the reference too): dropped here
+        sal, _ = explainer.generate_RAVE(x, target_class, device=dev)
     else:
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit

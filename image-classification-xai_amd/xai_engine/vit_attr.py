@@ -279,3 +279,67 @@ def _bidirectional(self, input, target_class, steps=20, start_layer=4, samples=2
 
 Baselines.attn_attr = _attn_attr
 Baselines.bidirectional = _bidirectional
+
+
+def _generate_cam_attn(self, input, target_class, device, layer=-1):
+    """Grad-weighted CLS attention of one block (reference Baselines.generate_cam_attn :161-178) -> (1, side, side):
+    clamp(mean_h(A * dA), 0) on the CLS row's token columns, min-max normalised -- after the backward, one launch of
+    xai_attn_cam_f32.  A constant map gives NaN, as the reference's 0/0 does.  The caller's `input.requires_grad` is left as
+    it is (the reference sets it and clears it again)."""
+    dev = hip_device(device)
+    x = input.to(dev).detach().requires_grad_(True)
+    output = self.model(x, register_hook=True)
+    _backward(output[0][target_class].sum())
+    attn = self.model.blocks[layer].attn
+    return _grid(K.attn_cam(attn.get_attention_map().detach(), attn.get_attn_gradients())[:1])
+
+
+def _block_classification_probs(model, blocks):
+    """Per-block classification logits: the model's own `get_block_classification_probs()` where it has one (the reference's timm
+    twin, ViT_new_timm.py:475-495), else the same expression, head(norm(block_out).mean(dim=1)), from each block's kept output --
+    so the build's ViT computes these heads only when generate_RAVE asks for them."""
+    if hasattr(model, "get_block_classification_probs"):
+        return model.get_block_classification_probs()
+    return [model.head(model.norm(blk.get_block_out()).mean(dim=1)) for blk in blocks]
+
+
+def _generate_RAVE(self, input, target_class, withgrad=True, device="cuda:0", ablate=0, target_token=0, stop_layer=12):
+    """InFlow attribution (reference Baselines.generate_RAVE :241-305) -> (map (1, side, side), (b1 (L,2,S), b2 (L,2,S))) for the
+    blocks [0, stop_layer].  After the classifier's passes the arithmetic is four launches: head importance Ih (K17), residual
+    shares (K20), the row-normalised InFlow matrices (K18: max over heads of A * Ih, times the head-mean bottom-up gradient and
+    clamped when `withgrad`, the residual modelling of compute_RAVE) and row `target_token` of their chained product (K19).
+
+    Deliberate divergences from the reference:
+      (a) the shapes come from this call's own forward; the reference reads blocks[-1]'s attention map before its forward, so
+          it raises on a model that has never run;
+      (b) the caller's `input.requires_grad` is not mutated (as in generate_grad);
+      (c) none in the signature: the reference's call sites pass option='b', which generate_RAVE does not take -- a TypeError
+          there and here alike."""
+    if ablate not in (0, 1):
+        raise ValueError("ablate must be 0 or 1")
+    dev = hip_device(device)
+    x = input.to(dev).detach().requires_grad_(True)
+    if x.shape[0] != 1:
+        raise ValueError("generate_RAVE attributes one image (the reference squeezes the batch axis)")
+    output = self.model(x, register_hook=True)
+    blocks = list(self.model.blocks)[0:stop_layer + 1]
+    score = output[0][target_class].sum()
+    bgrads = None
+    with backward_turn(dev):
+        score.backward(retain_graph=True)
+        grads = [blk.attn.get_attn_gradients() for blk in blocks]        # read now: the attention hooks also see the grads below
+        if withgrad:
+            prob = _block_classification_probs(self.model, blocks)
+            bgrads = [torch.autograd.grad(torch.unbind(prob[i][:, target_class]), blk.attn.get_attention_map(), retain_graph=True)[0][0]
+                      for i, blk in enumerate(blocks)]
+    attns = [blk.attn.get_attention_map().detach() for blk in blocks]
+    Ih = K.attn_head_importance(attns, grads)
+    b1, b2 = K.residual_shares([blk.get_input().detach() for blk in blocks], [blk.attn.get_output().detach() for blk in blocks],
+                               [blk.get_input_plus_attn().detach() for blk in blocks], [blk.get_mlp_val().detach() for blk in blocks])
+    aug = K.rave_matrices(attns, Ih, b1, b2, bgrads, ablate)
+    row = K.rollout_row(aug, target_token)
+    return _grid(row[1:]), (b1, b2)
+
+
+Baselines.generate_cam_attn = _generate_cam_attn
+Baselines.generate_RAVE = _generate_RAVE

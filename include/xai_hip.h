@@ -36,9 +36,11 @@ typedef void* xai_stream_t; /* hipStream_t */
  * xai_version_minor() = XAI_ABI_MINOR: bumped whenever entry points are added or an accepted argument range grows, so a
  * host can tell an older libxai_hip.so from this one without probing symbols:
  *   1 = the round-1 set;  2 = + xai_ig_accum_timed_f32, xai_maxpool_bwd_f32 accepts more than 65 535 planes;
- *   3 = + xai_version_minor, xai_masked_sums_f32 */
+ *   3 = + xai_version_minor, xai_masked_sums_f32;
+ *   4 = + xai_attn_head_importance_f32 (+ _workspace_bytes), xai_rave_matrices_f32, xai_rollout_row_f32,
+ *         xai_residual_shares_f32, xai_attn_cam_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 3
+#define XAI_ABI_MINOR 4
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -232,6 +234,53 @@ int xai_causal_apply_f32(const float* x, const float* masks, const float* noise,
  *   rows : [N][P];  weights : [N];  out_weighted, out_plain : [P] */
 int xai_masked_sums_f32(const float* rows, const float* weights, int N, int64_t P, float* out_weighted,
                         float* out_plain, xai_stream_t stream);
+
+/* ---- ViT explainers: Baselines.generate_RAVE ("InFlow") and Baselines.generate_cam_attn ----------------------------
+ * after the classifier's backward passes (util/attribution_methods/VIT_LRP/ViT_explanation_generator.py).  Per-block
+ * tensors are separate allocations, so the multi-block entries take a DEVICE array of device pointers, one per block (and
+ * operand), and cover all L blocks in one call.  No floating-point atomics: results are bit-identical from run to run. */
+
+/* K17 workspace of xai_attn_head_importance_f32: L*H*ceil(S/32)^2 floats (the per-tile partials of
+ * ViT_explanation_generator.py:268-271) */
+size_t xai_attn_head_importance_workspace_bytes(int L, int H, int S);
+
+/* K17 Ih[l][h] = m[l][h] / sum_h m[l][h],  m[l][h] = mean_ij |(A_lh^T G_lh)[i][j]|   (f32-input MFMA, f32 accumulation;
+ *     the S x S product is never written: abs and the tile sums happen in the epilogue, the tile sums are added in tile order)
+ * replaces  ViT_explanation_generator.py:268-271 (torch.matmul(attn^T, grad).abs().mean(dim=(-1,-2)), Ih / sum(Ih))
+ *   attn_tab[l], grad_tab[l] : [H][S][S] attention map / its gradient of block l (image 0);  Ih : [L][H]
+ *   ws : >= xai_attn_head_importance_workspace_bytes(L, H, S) bytes of device scratch (required) */
+int xai_attn_head_importance_f32(const float* const* attn_tab, const float* const* grad_tab, int L, int H, int S,
+                                 float* Ih, void* ws, size_t ws_bytes, xai_stream_t stream);
+
+/* K18 aug[l] = row-normalised InFlow matrix of block l:
+ *     M[i][j] = max_h A_lh[i][j] * Ih[l][h];  with bgrad: M = max(mean_h Gb_lh[i][j] * M, 0)
+ *     r[i][j] = M[i][j] * b1[l][1][j] + (i == j) * b1[l][0][j]
+ *     ablate == 0: r[i][j] *= ratio[j] * b2[l][1][j] + b2[l][0][j],  ratio = q / max(sum_j |q_j|, 1e-12),  q = b2[l][1] / b2[l][0]
+ *     aug[l][i][j] = r[i][j] / sum_j r[i][j]
+ * replaces  ViT_explanation_generator.py:272 (max over heads), :278-281 (bottom-up gradient), compute_RAVE :63-86 (the
+ *           r1 @ r2 product is a column scale: r2 is diagonal)
+ *   attn_tab[l], bgrad_tab[l] : [H][S][S] (bgrad_tab NULL = withgrad False);  Ih : [L][H];  b1, b2 : [L][2][S];
+ *   ablate : 0 or 1;  aug : [L][S][S] */
+int xai_rave_matrices_f32(const float* const* attn_tab, const float* const* bgrad_tab, const float* Ih, const float* b1,
+                          const float* b2, int L, int H, int S, int ablate, float* aug, xai_stream_t stream);
+
+/* K19 out[n] = row target_token of aug[n][L-1] . aug[n][L-2] ... aug[n][0], as L-1 vector-matrix products (all entries >= 0)
+ * replaces  compute_RAVE, ViT_explanation_generator.py:84-88, and rollout[:, target_token] of :299
+ *   aug : [n_img][L][S][S];  out : [n_img][S] */
+int xai_rollout_row_f32(const float* aug, int n_img, int L, int S, int target_token, float* out, xai_stream_t stream);
+
+/* K20 residual-stream 2-norm shares of every block, p=1-normalised with a max(., 1e-12) denominator:
+ *     b1[l] = (|x|, |attn|) / max(|x| + |attn|, 1e-12),  b2[l] = (|x + attn|, |mlp|) / max(|x + attn| + |mlp|, 1e-12) per token
+ * replaces  ViT_explanation_generator.py:286-297 (torch.linalg.norm x4, stack, normalize per block)
+ *   tab[4l + 0..3] : block l's input, attention output, input + attention, MLP output, each [S][D] (image 0);
+ *   b1, b2 : [L][2][S] */
+int xai_residual_shares_f32(const float* const* tab, int L, int S, int D, float* b1, float* b2, xai_stream_t stream);
+
+/* K21 out[n][p] = (c[p] - min c) / (max c - min c),  c[p] = max(mean_h A[n][h][0][1+p] * G[n][h][0][1+p], 0), p < S-1;
+ *     a constant c gives NaN everywhere, as the reference's 0/0
+ * replaces  ViT_explanation_generator.py:167-177 (Baselines.generate_cam_attn after its backward)
+ *   attn, grad : [n_img][H][S][S] of one block;  out : [n_img][S-1] */
+int xai_attn_cam_f32(const float* attn, const float* grad, int n_img, int H, int S, float* out, xai_stream_t stream);
 
 /* ---- opt-in classifier-side fusion (xai_engine/prepare.py: fuse_bn_relu) --------------- */
 

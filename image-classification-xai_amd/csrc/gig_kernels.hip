@@ -1,0 +1,341 @@
+// K22: Guided IG (GIGBuilder.py:194-292) for gfx950 -- one outer step of guided_ig_impl per launch, B images per launch.
+//
+// One workgroup of 1024 lanes per image runs the whole `while gamma > 1` loop of a step (:246-291) with no host round
+// trip.  An iteration is five sweeps over the image's N features (all read x, x_input, x_baseline, grad; L2-resident for
+// a 224^2 image):
+//   A   clamp to x_min (:249-253, recomputed on the fly, x is written only by the last sweep), l1_current, and the
+//       histogram of the top 11 key bits;
+//   B,C the next 11 and the last 10 key bits of the keys still in the running (a 3-pass radix select of the exact order
+//       statistic torch.quantile(..., interpolation='lower') returns, :267);
+//   D   l1_s (:272);
+//   E   the update of x (:282-289) and attr (:292).
+// Keys are `+inf` where x == x_max (:264) and |grad| elsewhere; non-negative floats order like their bit patterns.
+// The histograms count with LDS atomics (integer counts do not depend on arrival order).  l1_total, l1_current and l1_s
+// are summed by one fixed tree (lane t takes elements t, t+1024, ... in order, fp64 per lane, wave butterfly, waves in
+// order) and rounded to fp32: two runs give the same bytes, and on the last step, where every remaining feature is
+// selected, l1_current and l1_s add the same terms in the same order and gamma is exactly 1.
+// Capturable: the step index lives in the per-image state words and is advanced by the kernel, the init entry replaces
+// every memset, and no host value changes from step to step.
+#include "xai_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kBins = 2048;                  // 11-bit digits: bits [21,32), [10,21), [0,10)
+constexpr int kMaxSelections = XAI_GIG_MAX_SELECTIONS;   // per step; the reference needed 51 for 50 steps on a toy net
+constexpr uint32_t kInfKey = 0x7f800000u;
+
+enum : int32_t { kOk = 0, kNanKey = 1, kCap = 2, kGamma = 3, kSteps = 4 };
+
+template <int V>
+struct Pack {
+  float v[V];
+};
+
+template <int V>
+__device__ __forceinline__ Pack<V> ldp(const float* p) {
+  Pack<V> r;
+  if constexpr (V == 4) {
+    const float4 t = ld4(p);
+    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+  } else {
+    r.v[0] = *p;
+  }
+  return r;
+}
+
+template <int V>
+__device__ __forceinline__ void stp(float* p, const Pack<V>& a) {
+  if constexpr (V == 4) {
+    st4(p, make_float4(a.v[0], a.v[1], a.v[2], a.v[3]));
+  } else {
+    *p = a.v[0];
+  }
+}
+
+// x after the clamp of :249-253, and x_max (translate_alpha_to_x, :183).  torch rounds every operation to fp32 and
+// compares with the fp32 value of a python-float scalar; -ffp-contract=off keeps a*b+c two roundings.
+__device__ __forceinline__ float clamped_x(float x, float xi, float xb, float amin, float amax, float& xmax) {
+  const float d = xi - xb;
+  const float xmin = xb + d * amin;
+  xmax = xb + d * amax;
+  float xa = d != 0.f ? (x - xb) / d : __builtin_nanf("");   // translate_x_to_alpha, :170
+  if (xa != xa) xa = amax;                                    // :250
+  return xa < amin ? xmin : x;
+}
+
+__device__ __forceinline__ uint32_t sel_key(float xc, float xmax, float g) {
+  return xc == xmax ? kInfKey : __float_as_uint(fabsf(g));   // fabsf clears the sign bit: -0.0 keys as +0.0; NaN > kInfKey
+}
+
+// Sum over the workgroup of one fp64 value per lane, in one fixed order; every lane gets the same bits.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);                          // xor butterfly: a+b on both partners, so all lanes agree
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) s += red[w];
+  __syncthreads();
+  return s;
+}
+
+// Digit d of `hist` with count(< d) <= k < count(<= d); k becomes the rank inside that digit.  Lane t owns bins 2t, 2t+1.
+__device__ __forceinline__ uint32_t find_digit(const uint32_t* hist, uint32_t& k, uint32_t* wsum, uint32_t* pick) {
+  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  const uint32_t c0 = hist[2 * t], c1 = hist[2 * t + 1], c = c0 + c1;
+  uint32_t incl = c;
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const uint32_t up = __shfl_up(incl, off, kWave);
+    if (lane >= off) incl += up;
+  }
+  if (lane == kWave - 1) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t pre = incl - c;
+  for (int w = 0; w < wave; ++w) pre += wsum[w];
+  if (k >= pre && k < pre + c0) {
+    pick[0] = 2 * t; pick[1] = k - pre;
+  } else if (k >= pre + c0 && k < pre + c) {
+    pick[0] = 2 * t + 1; pick[1] = k - pre - c0;
+  }
+  __syncthreads();
+  const uint32_t d = pick[0];
+  k = pick[1];
+  __syncthreads();
+  return d;
+}
+
+__device__ __forceinline__ void zero_hist(uint32_t* hist) {
+  hist[2 * threadIdx.x] = 0u;
+  hist[2 * threadIdx.x + 1] = 0u;
+}
+
+// Python's math.isclose(a, b, rel_tol=1e-9, abs_tol=1e-9) on the fp32 values, in double (:258)
+__device__ __forceinline__ bool py_isclose(float a32, float b32) {
+  const double a = a32, b = b32;
+  if (a == b) return true;
+  if (isinf(a) || isinf(b)) return false;
+  const double diff = fabs(a - b);
+  return diff <= fmax(1e-9 * fmax(fabs(a), fabs(b)), 1e-9);
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void gig_init_kernel(const float* __restrict__ xin_all, const float* __restrict__ xb_all, int64_t N,
+                                                            float* __restrict__ x_all, float* __restrict__ attr_all,
+                                                            float* __restrict__ l1_total, int32_t* __restrict__ state) {
+  __shared__ double red[kWaves];
+  const int64_t off = static_cast<int64_t>(blockIdx.x) * N;
+  const float* xin = xin_all + off;
+  const float* xb = xb_all + off;
+  double s = 0.0;
+  for (int64_t i = static_cast<int64_t>(threadIdx.x) * V; i < N; i += static_cast<int64_t>(kThreads) * V) {
+    const Pack<V> a = ldp<V>(xin + i), b = ldp<V>(xb + i);
+    Pack<V> z;
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      s += static_cast<double>(fabsf(a.v[u] - b.v[u]));       // l1_distance(x_input, x_baseline), :212
+      z.v[u] = 0.f;
+    }
+    stp<V>(x_all + off + i, b);
+    stp<V>(attr_all + off + i, z);
+  }
+  const double tot = block_sum(s, red);
+  if (threadIdx.x == 0) {
+    l1_total[blockIdx.x] = static_cast<float>(tot);
+    int32_t* st = state + 4 * blockIdx.x;
+    st[0] = 0; st[1] = kOk; st[2] = 0; st[3] = 0;
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restrict__ xin_all, const float* __restrict__ xb_all,
+                                                            const float* __restrict__ g_all, int64_t N, int steps, double max_dist,
+                                                            uint32_t rank, float* __restrict__ x_all, float* __restrict__ attr_all,
+                                                            const float* __restrict__ l1_total, int32_t* __restrict__ state) {
+  __shared__ uint32_t hist[kBins];
+  __shared__ double red[kWaves];
+  __shared__ uint32_t wsum[kWaves];
+  __shared__ uint32_t pick[2];
+  __shared__ uint32_t nan_seen;
+  const int tid = threadIdx.x;
+  int32_t* st = state + 4 * blockIdx.x;
+  const int32_t step = st[0];
+  if (st[1] != kOk) return;                                    // a failed image is left as it stands
+  __syncthreads();                                             // every lane has read the state before lane 0 may write it
+  if (step >= steps) {
+    if (tid == 0) { st[1] = kSteps; st[3] = step; }
+    return;
+  }
+  const float l1t = l1_total[blockIdx.x];
+  if (l1t == 0.f) {                                            // input == baseline: attr stays zero (:222-225)
+    if (tid == 0) { st[0] = step + 1; st[2] = 0; }
+    return;
+  }
+  // :235-244 -- python floats (double), rounded to fp32 where torch meets them
+  const double alpha = (step + 1.0) / steps;
+  const float amin = static_cast<float>(fmax(alpha - max_dist, 0.0));
+  const float amax = static_cast<float>(fmin(alpha + max_dist, 1.0));
+  const float l1_target = l1t * static_cast<float>(1.0 - static_cast<double>(step + 1) / steps);
+
+  const int64_t off = static_cast<int64_t>(blockIdx.x) * N;
+  const float* xin = xin_all + off;
+  const float* xb = xb_all + off;
+  const float* g = g_all + off;
+  float* x = x_all + off;
+  float* attr = attr_all + off;
+  const int64_t i0 = static_cast<int64_t>(tid) * V, di = static_cast<int64_t>(kThreads) * V;
+
+  int selections = 0;
+  for (;;) {
+    // ---- A: clamp, l1_current, top digit
+    zero_hist(hist);
+    if (tid == 0) nan_seen = 0u;
+    __syncthreads();
+    double s = 0.0;
+    for (int64_t i = i0; i < N; i += di) {
+      const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        float xmax;
+        const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
+        s += static_cast<double>(fabsf(xc - pi.v[u]));
+        const uint32_t key = sel_key(xc, xmax, pg.v[u]);
+        if (key > kInfKey) nan_seen = 1u;
+        else atomicAdd(&hist[key >> 21], 1u);
+      }
+    }
+    const float l1_current = static_cast<float>(block_sum(s, red));   // (block_sum synchronises: hist and nan_seen are complete)
+    const bool close = py_isclose(l1_target, l1_current);
+    if (!close) {
+      int32_t err = kOk;
+      if (nan_seen) err = kNanKey;                              // torch.quantile would return NaN and the loop never ends
+      else if (selections == kMaxSelections) err = kCap;
+      if (err != kOk) {
+        if (tid == 0) { st[1] = err; st[2] = selections; st[3] = step; }
+        return;
+      }
+    }
+    float gamma = 0.f;
+    uint32_t thr = 0u;
+    if (!close) {
+      ++selections;
+      // ---- B, C: radix select of the key of rank `rank`
+      uint32_t k = rank;
+      const uint32_t d1 = find_digit(hist, k, wsum, pick);
+      zero_hist(hist);
+      __syncthreads();
+      for (int64_t i = i0; i < N; i += di) {
+        const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          float xmax;
+          const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
+          const uint32_t key = sel_key(xc, xmax, pg.v[u]);
+          if ((key >> 21) == d1) atomicAdd(&hist[(key >> 10) & 0x7FFu], 1u);
+        }
+      }
+      __syncthreads();
+      const uint32_t d2 = find_digit(hist, k, wsum, pick);
+      const uint32_t hi = (d1 << 11) | d2;
+      zero_hist(hist);
+      __syncthreads();
+      for (int64_t i = i0; i < N; i += di) {
+        const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          float xmax;
+          const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
+          const uint32_t key = sel_key(xc, xmax, pg.v[u]);
+          if ((key >> 10) == hi) atomicAdd(&hist[key & 0x3FFu], 1u);
+        }
+      }
+      __syncthreads();
+      thr = (hi << 10) | find_digit(hist, k, wsum, pick);
+      // ---- D: l1_s = sum |x - x_max| over the selection s = key <= thr && key != inf (:268, :272)
+      s = 0.0;
+      for (int64_t i = i0; i < N; i += di) {
+        const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          float xmax;
+          const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
+          const uint32_t key = sel_key(xc, xmax, pg.v[u]);
+          if (key <= thr && key != kInfKey) s += static_cast<double>(fabsf(xc - xmax));
+        }
+      }
+      const float l1_s = static_cast<float>(block_sum(s, red));
+      gamma = l1_s > 0.f ? (l1_current - l1_target) / l1_s : __builtin_inff();    // :277-280
+      if (!(gamma > 1.f) && !(gamma > 0.f)) {                                      // the reference's assert (:287)
+        if (tid == 0) { st[1] = kGamma; st[2] = selections; st[3] = step; }
+        return;
+      }
+    }
+    // ---- E: x <- clamped x, then the selection moves to x_max (gamma > 1) or by gamma toward it; attr += (x - x_old) * grad
+    for (int64_t i = i0; i < N; i += di) {
+      const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
+      Pack<V> pa = ldp<V>(attr + i), pn;
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        float xmax;
+        const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
+        float xn = xc;
+        if (!close) {
+          const uint32_t key = sel_key(xc, xmax, pg.v[u]);
+          if (key <= thr && key != kInfKey) xn = gamma > 1.f ? xmax : xc + (xmax - xc) * gamma;
+        }
+        pn.v[u] = xn;
+        pa.v[u] = pa.v[u] + (xn - px.v[u]) * pg.v[u];
+      }
+      stp<V>(x + i, pn);
+      stp<V>(attr + i, pa);
+    }
+    if (close || !(gamma > 1.f)) break;
+    __syncthreads();                                           // this sweep's writes of x before the next iteration reads them
+  }
+  if (tid == 0) { st[0] = step + 1; st[2] = selections; }
+}
+
+bool vec4_ok(int64_t N, const void* a, const void* b, const void* c, const void* d, const void* e) {
+  return N % 4 == 0 && xai_aligned16(a) && xai_aligned16(b) && xai_aligned16(c) && xai_aligned16(d) && xai_aligned16(e);
+}
+
+}  // namespace
+
+XAI_EXPORT int xai_gig_init_f32(const float* x_input, const float* x_baseline, int n_img, int64_t n_elem, float* x, float* attr,
+                                float* l1_total, int32_t* state, xai_stream_t stream) {
+  XAI_REQUIRE_PTR(x_input); XAI_REQUIRE_PTR(x_baseline); XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(attr); XAI_REQUIRE_PTR(l1_total);
+  XAI_REQUIRE_PTR(state);
+  XAI_REQUIRE(n_img > 0 && n_elem > 0, XAI_E_SHAPE);
+  XAI_REQUIRE(n_img <= 65535 && n_elem < (int64_t{1} << 31), XAI_E_UNSUPPORTED);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec4_ok(n_elem, x_input, x_baseline, x, attr, x))
+    hipLaunchKernelGGL(gig_init_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
+  else
+    hipLaunchKernelGGL(gig_init_kernel<1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
+  return xai_launch_status();
+}
+
+XAI_EXPORT int xai_gig_step_f32(const float* x_input, const float* x_baseline, const float* grad, int n_img, int64_t n_elem, int steps,
+                                float fraction, double max_dist, float* x, float* attr, const float* l1_total, int32_t* state,
+                                xai_stream_t stream) {
+  XAI_REQUIRE_PTR(x_input); XAI_REQUIRE_PTR(x_baseline); XAI_REQUIRE_PTR(grad); XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(attr);
+  XAI_REQUIRE_PTR(l1_total); XAI_REQUIRE_PTR(state);
+  XAI_REQUIRE(n_img > 0 && n_elem > 0 && steps > 0, XAI_E_SHAPE);
+  XAI_REQUIRE(fraction >= 0.f && fraction <= 1.f && max_dist == max_dist, XAI_E_SHAPE);
+  XAI_REQUIRE(n_img <= 65535 && n_elem < (int64_t{1} << 31), XAI_E_UNSUPPORTED);
+  // torch.quantile: rank = floor(q * (n - 1)) with q an fp32 tensor, so the product rounds to fp32 first
+  const float r = fraction * static_cast<float>(n_elem - 1);
+  const uint32_t rank = static_cast<uint32_t>(floorf(r));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec4_ok(n_elem, x_input, x_baseline, grad, x, attr))
+    hipLaunchKernelGGL(gig_step_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, grad, n_elem, steps, max_dist, rank, x,
+                       attr, l1_total, state);
+  else
+    hipLaunchKernelGGL(gig_step_kernel<1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, grad, n_elem, steps, max_dist, rank, x,
+                       attr, l1_total, state);
+  return xai_launch_status();
+}

@@ -553,3 +553,36 @@ def attn_cam(attn, grad):
     out = torch.empty((B, S - 1), dtype=F32, device=attn.device)
     _call("xai_attn_cam_f32", attn.device, _ptr(attn), _ptr(grad), B, H, S, _ptr(out))
     return out
+
+
+# ------------------------------------------------------------------------------ Guided IG (K22)
+GIG_STATUS = {1: "a selection key is NaN (NaN gradient): the reference would loop forever",
+              2: "the step's L1 target was not reached within the selection cap",
+              3: "gamma <= 0 or NaN (the reference's assert gamma > 0)",
+              4: "more step launches than steps"}
+
+
+def gig_init(x_input, x_baseline, x, attr, l1_total, state):
+    """x = baseline, attr = 0, l1_total = sum |x_input - baseline| per image, state = 0.  All (B, ...) device tensors."""
+    for t, n in ((x_input, "x_input"), (x_baseline, "x_baseline"), (x, "x"), (attr, "attr"), (l1_total, "l1_total")):
+        _need(t, F32, n)
+    _need(state, I32, "state")
+    B = x_input.shape[0]
+    n = x_input[0].numel()
+    if not (x_baseline.numel() == x.numel() == attr.numel() == B * n and l1_total.numel() == B and state.numel() == 4 * B):
+        raise ValueError("gig_init: inconsistent sizes")
+    _call("xai_gig_init_f32", x_input.device, _ptr(x_input), _ptr(x_baseline), B, n, _ptr(x), _ptr(attr), _ptr(l1_total), _ptr(state))
+
+
+def gig_step(x_input, x_baseline, grad, steps, fraction, max_dist, x, attr, l1_total, state):
+    """One Guided IG step (K22) of every image: reads the step index from `state`, updates x and attr in place."""
+    for t, n in ((x_input, "x_input"), (x_baseline, "x_baseline"), (grad, "grad"), (x, "x"), (attr, "attr"), (l1_total, "l1_total")):
+        _need(t, F32, n)
+    _need(state, I32, "state")
+    B = x_input.shape[0]
+    n = x_input[0].numel()
+    if not (x_baseline.numel() == grad.numel() == x.numel() == attr.numel() == B * n and l1_total.numel() == B
+            and state.numel() == 4 * B):
+        raise ValueError("gig_step: inconsistent sizes")
+    _call("xai_gig_step_f32", x_input.device, _ptr(x_input), _ptr(x_baseline), _ptr(grad), B, n, int(steps), float(fraction),
+          float(max_dist), _ptr(x), _ptr(attr), _ptr(l1_total), _ptr(state))

@@ -25,13 +25,14 @@ from . import curves
 from . import kernels as K
 from .blur import GaussianBlur
 from .gradcam import gradcam_saliency, CapturedGradCam
+from .guided_ig import guided_ig_batch
 from .ig import IG, IDG, getGradientsParallel, hip_device, _logits_of
 from .perturb import (AICMetric, MASMetric, MonotonicityMetric, PositiveNegativePerturbation, _Probe, sequence_stats)
 from .smooth import smoothGrad
 from .streams import CAPTURE_LOCK
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "sg", "gc")
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "sg", "gc")
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
 
@@ -61,6 +62,10 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         saliency_map = IG(input_tensor, model, steps, batch_size, .9, baseline, device, target_class)
     elif attr_function == "idg":
         saliency_map = IDG(input_tensor, model, steps, batch_size, baseline, device, target_class)
+    elif attr_function == "gig":
+        # :114-118: zero baseline, 50 steps, max_dist 1.0, fraction 0.5, the gradient of the softmax probability
+        t = target_class.reshape(1) if torch.is_tensor(target_class) else torch.tensor([int(target_class)])
+        saliency_map = guided_ig_batch(input_tensor.to(dev), model, t, steps=steps, fraction=0.5, max_dist=1.0, baseline=baseline)[0]
     elif attr_function == "sg":
         saliency_map = smoothGrad("IG", input_tensor, model, 50, baseline, target_class, device)
     elif attr_function == "gc":

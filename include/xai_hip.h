@@ -38,9 +38,10 @@ typedef void* xai_stream_t; /* hipStream_t */
  *   1 = the round-1 set;  2 = + xai_ig_accum_timed_f32, xai_maxpool_bwd_f32 accepts more than 65 535 planes;
  *   3 = + xai_version_minor, xai_masked_sums_f32;
  *   4 = + xai_attn_head_importance_f32 (+ _workspace_bytes), xai_rave_matrices_f32, xai_rollout_row_f32,
- *         xai_residual_shares_f32, xai_attn_cam_f32 */
+ *         xai_residual_shares_f32, xai_attn_cam_f32;
+ *   5 = + xai_gig_init_f32, xai_gig_step_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 4
+#define XAI_ABI_MINOR 5
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -281,6 +282,34 @@ int xai_residual_shares_f32(const float* const* tab, int L, int S, int D, float*
  * replaces  ViT_explanation_generator.py:167-177 (Baselines.generate_cam_attn after its backward)
  *   attn, grad : [n_img][H][S][S] of one block;  out : [n_img][S-1] */
 int xai_attn_cam_f32(const float* attn, const float* grad, int n_img, int H, int S, float* out, xai_stream_t stream);
+
+/* ---- Guided IG (util/attribution_methods/GIGBuilder.py:194-292) --------------------------------------------- */
+
+/* Per-image state words of the Guided IG entries: int32 state[n_img][4] =
+ *   { next step index, status, selections (quantile calls) of the last step, step at which the status was set }.
+ * status: 0 ok; 1 a selection key is NaN (a NaN gradient off x_max: torch.quantile returns NaN and the reference loops
+ * forever); 2 XAI_GIG_MAX_SELECTIONS selections did not reach the step's L1 target; 3 gamma <= 0 or NaN (the reference's
+ * assert, :287); 4 more step launches than `steps`.  An image with a nonzero status is not touched again. */
+#define XAI_GIG_MAX_SELECTIONS 64
+
+/* K22 init: x = x_baseline, attr = 0, l1_total[i] = sum |x_input - x_baseline| (fp32 terms, one fixed fp64 sum order,
+ * rounded to fp32), state = 0.  Replaces the set-up of guided_ig_impl, GIGBuilder.py:209-213; a kernel, not a memset,
+ * so that it can sit in front of a captured graph.
+ *   x_input, x_baseline, x, attr : [n_img][n_elem];  l1_total : [n_img];  state : [n_img][4] */
+int xai_gig_init_f32(const float* x_input, const float* x_baseline, int n_img, int64_t n_elem, float* x, float* attr,
+                     float* l1_total, int32_t* state, xai_stream_t stream);
+
+/* K22 step: one outer step of guided_ig_impl (GIGBuilder.py:228-292) for every image, the whole inner
+ * `while gamma > 1` loop (:246-291) on the device: clamp to x_min, l1_current and the math.isclose exit, the selection
+ * of the features whose |grad| is at most the torch.quantile(..., fraction, interpolation='lower') order statistic
+ * (rank floor(fp32(fraction) * fp32(n_elem - 1)), exact, keys = +inf where x == x_max), l1_s, gamma, the update of x and
+ * attr += (x - x_old) * grad.  One workgroup per image; the step index is read from and advanced in state[i][0], so the
+ * same launch serves every step (graph-capturable).  Images whose l1_total is 0 keep attr = 0 (:222-225).
+ *   grad : [n_img][n_elem], the gradient at the current x;  fraction in [0, 1];  max_dist as the reference's python float
+ *   x, attr : updated in place;  l1_total, state : as left by xai_gig_init_f32 */
+int xai_gig_step_f32(const float* x_input, const float* x_baseline, const float* grad, int n_img, int64_t n_elem, int steps,
+                     float fraction, double max_dist, float* x, float* attr, const float* l1_total, int32_t* state,
+                     xai_stream_t stream);
 
 /* ---- opt-in classifier-side fusion (xai_engine/prepare.py: fuse_bn_relu) --------------- */
 

@@ -1,0 +1,191 @@
+"""Guided IG on the MI355X: K22 step by step against the reference's own per-step x and gradients (tests/golden/gig.npz), GetMask
+end to end against the reference's masks, a ResNet-50 at full size against the fp32 torch restatement of the reference loop
+(tests/gig_restated.py), batching / graph replay / streams, the edge cases and the harness row."""
+import numpy as np
+import pytest
+import torch
+
+import gig_restated
+from conftest import check, load_golden
+from helpers import tiny_from
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _fixture(tag):
+    g = load_golden("gig.npz")
+    steps, fraction, max_dist = g[f"{tag}_params"].tolist()
+    xin = torch.from_numpy(g[f"{tag}_input"])
+    base = torch.from_numpy(g["b_baseline"]) if tag == "b" else torch.zeros_like(xin)
+    return g, xin, base, int(steps), float(fraction), float(max_dist)
+
+
+def _buffers(xin, base):
+    from xai_engine import kernels as K
+    B = xin.shape[0]
+    xin, base = xin.to(DEV).contiguous(), base.to(DEV).contiguous()
+    x, attr = torch.empty_like(xin), torch.empty_like(xin)
+    l1 = torch.empty(B, dtype=torch.float32, device=DEV)
+    state = torch.empty((B, 4), dtype=torch.int32, device=DEV)
+    K.gig_init(xin, base, x, attr, l1, state)
+    return xin, base, x, attr, l1, state
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_k22_step_by_step_matches_the_reference(tag):
+    """Every step of the reference's run, from the reference's own x and gradient: the same number of selections, the same
+    features moved, x within 1e-6 |x_input - baseline| per element, and the accumulated attribution is the reference's mask."""
+    from xai_engine import kernels as K
+    g, xin_h, base_h, steps, fraction, max_dist = _fixture(tag)
+    xin, base, x, attr, l1, state = _buffers(xin_h, base_h)
+    X, G = g[f"{tag}_x"], g[f"{tag}_g"]
+    span = np.abs(xin_h.numpy() - base_h.numpy()).astype(np.float64)
+    moving = span > 0
+    worst = 0.0
+    for s in range(steps):
+        x.copy_(torch.from_numpy(X[s]))
+        K.gig_step(xin, base, torch.from_numpy(G[s]).to(DEV), steps, fraction, max_dist, x, attr, l1, state)
+        st = state.cpu().numpy()[0]
+        assert st[1] == 0 and st[0] == s + 1, (s, st)
+        assert st[2] == g[f"{tag}_iters"][s], (s, st[2], g[f"{tag}_iters"][s])
+        got = x.cpu().numpy().astype(np.float64)
+        want = X[s + 1].astype(np.float64)
+        np.testing.assert_array_equal(got != X[s], X[s + 1] != X[s], err_msg=f"moved set of step {s}")
+        np.testing.assert_array_equal(got[~moving], want[~moving])
+        worst = max(worst, float((np.abs(got - want)[moving] / span[moving]).max()))
+    # |x - x_ref| / |x_input - baseline|: 1.75e-6 (a), 1.27e-6 (b) -- all of it from the sums inside gamma: the reference loop with
+    # its two sums taken in fp64 and rounded (tests/gig_restated.py, sums changed) gives the kernel's x to the last bit on the CPU,
+    # and (l1_current - l1_target) cancels, so the fp32 rounding of torch's sums reaches gamma amplified
+    check(f"gig/step_by_step/{tag}/x_over_span", worst, 0.0, 2e-6, absolute=True)
+    check(f"gig/step_by_step/{tag}/mask", attr.cpu().numpy(), g[f"{tag}_mask"], 1e-5)
+
+
+# No 224^2 image is held end to end against the reference (CPU) mask: Guided IG's selection is discontinuous in the
+# gradient, and at 150 528 features the CPU-vs-GPU rounding of the classifier's gradient moves features across the quantile
+# threshold in some step, after which the two paths differ (measured 0.20 relative to max |mask|, ReLU or tanh alike).  K22 itself is
+# held at that size, selection by selection, by test_resnet50_real_gradients_against_the_restated_reference.
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_getmask_matches_the_reference_mask(case):
+    from util.attribution_methods import GIGBuilder as GIG
+    g, x, base, steps, fraction, max_dist = _fixture(case)
+    target, want = int(g[f"{case}_target"]), g[f"{case}_mask"]
+    model = tiny_from(g, DEV)
+    got = GIG.GuidedIG().GetMask(x, model, DEV, GIG.call_model_function, {"class_idx_str": target}, x_baseline=base, x_steps=steps,
+                                 fraction=fraction, max_dist=max_dist)
+    assert got.shape == x.shape and got.device == x.device
+    check(f"gig/GetMask/{case}", got.numpy(), want, 1e-5)
+
+
+def test_resnet50_real_gradients_against_the_restated_reference(monkeypatch):
+    """B = 4 ResNet-50 images at 224^2 through guided_ig_batch (harness arguments); every launch of K22 is recorded (x before,
+    gradient, x after, attr after, state) and replayed through the fp32 torch restatement of :246-291."""
+    from xai_engine import guided_ig as gig
+    from xai_engine import kernels as K
+    from xai_engine.zoo import resnet50
+    model = resnet50(seed=0).to(DEV).eval()
+    x = torch.randn(4, 3, 224, 224, generator=torch.Generator().manual_seed(5)).to(DEV)
+    with torch.no_grad():
+        t = model(x).argmax(1)
+    log = []
+    real = K.gig_step
+
+    def recording(xin, xb, grad, steps, fraction, max_dist, xs, attr, l1, state):
+        before, a0 = xs.cpu(), attr.cpu()
+        real(xin, xb, grad, steps, fraction, max_dist, xs, attr, l1, state)
+        a1 = attr.cpu()
+        log.append((before, grad.cpu(), xs.cpu(), a1 - a0, state.cpu(), a1.abs().double()))
+    monkeypatch.setattr(K, "gig_step", recording)
+    steps = 50
+    attr = gig.guided_ig_batch(x, model, t, steps=steps, fraction=0.5, max_dist=1.0, baseline=0, graphs=False).cpu()
+    assert len(log) == steps
+    xin = x.cpu()
+    worst_x, worst_a = 0.0, 0.0
+    for i in range(4):
+        l1 = xin[i].abs().sum()
+        for s, (before, grad, after, dattr, state, attr_abs) in enumerate(log):
+            xr, ar, sel, moved = gig_restated.step(before[i], xin[i], torch.zeros_like(xin[i]), grad[i], s, steps, 0.5, 1.0, l1)
+            assert int(state[i, 2]) == sel, (i, s, int(state[i, 2]), sel)
+            assert torch.equal(after[i] != before[i], moved), (i, s)
+            span = xin[i].abs().double()
+            worst_x = max(worst_x, float(((after[i].double() - xr.double()).abs() - 1e-6 * span).max()))
+            moved_by = (after[i].double() - before[i].double()).abs() * grad[i].abs().double()
+            worst_a = max(worst_a, float(((dattr[i].double() - ar.double()).abs() - 1e-6 * span * grad[i].abs().double()
+                                          - 2.0 ** -22 * (ar.abs().double() + moved_by + attr_abs[i])).max()))
+    assert worst_x <= 0.0 and worst_a <= 0.0, (worst_x, worst_a)
+    assert torch.isfinite(attr).all() and attr.abs().max() > 0
+
+
+def _tiny_batch(B=6, hw=32, seed=3):
+    g = load_golden("gig.npz")
+    model = tiny_from(g, DEV)
+    x = torch.randn(B, 3, hw, hw, generator=torch.Generator().manual_seed(seed)).to(DEV)
+    with torch.no_grad():
+        t = model(x).argmax(1)
+    return model, x, t
+
+
+def test_batching_replay_repeats_and_streams():
+    from xai_engine import guided_ig as gig
+    model, x, t = _tiny_batch()
+    kw = dict(steps=50, fraction=0.25, max_dist=0.02, baseline=0)
+    one = gig.guided_ig_batch(x, model, t, images_per_pass=1, **kw)
+    full = gig.guided_ig_batch(x, model, t, **kw)
+    check("gig/batching/one_image_per_pass_vs_six", one.cpu().numpy(), full.cpu().numpy(), 1e-6, against="B images per pass")
+    eager = gig.guided_ig_batch(x, model, t, graphs=False, **kw)
+    before = dict(gig.GIG_COUNTS)
+    replayed = gig.guided_ig_batch(x, model, t, **kw)
+    assert gig.GIG_COUNTS["replayed"] == before["replayed"] + 1, gig.GIG_COUNTS
+    assert torch.equal(replayed, eager) and torch.equal(full, eager)
+    again = gig.guided_ig_batch(x, model, t, **kw)
+    assert torch.equal(again.view(torch.int32), replayed.view(torch.int32))
+    s1 = gig.guided_ig_batch(x, model, t, images_per_pass=2, streams=1, **kw)
+    s3 = gig.guided_ig_batch(x, model, t, images_per_pass=2, streams=3, **kw)
+    assert torch.equal(s1, s3)
+
+
+def test_input_equal_to_its_baseline_gives_zeros():
+    from xai_engine.guided_ig import guided_ig_batch
+    model, x, t = _tiny_batch(B=2)
+    base = torch.zeros_like(x)
+    base[0] = x[0]
+    attr = guided_ig_batch(x, model, t, steps=10, fraction=0.5, max_dist=1.0, baseline=base)
+    assert torch.equal(attr[0], torch.zeros_like(attr[0])) and attr[1].abs().max() > 0
+
+
+class _NaNNet(torch.nn.Module):
+    def __init__(self, inner):
+        super().__init__()
+        self.inner = inner
+
+    def forward(self, x):
+        return self.inner(x) * float("nan")
+
+
+def test_a_nan_classifier_raises_with_the_status_instead_of_looping():
+    from xai_engine import XaiHipError
+    from xai_engine.guided_ig import guided_ig_batch
+    model, x, t = _tiny_batch(B=2)
+    with pytest.raises(XaiHipError, match=r"image 0: status 1 .*NaN"):
+        guided_ig_batch(x, _NaNNet(model), t, steps=5, fraction=0.5, max_dist=1.0)
+
+
+def test_harness_gig_row_device_maps_and_sweep():
+    from xai_engine.sweep import get_CNN_attr, sweep_images, KEYS
+    g = load_golden("gig.npz")
+    model = tiny_from(g, DEV)
+    x = torch.randn(1, 3, 32, 32, generator=torch.Generator().manual_seed(9))
+    with torch.no_grad():
+        t = model(x.to(DEV)).argmax(1)[0]
+    td = {"models": [model], "img_hw": 32, "batch_size": 25, "device": DEV, "attr_func": "gig"}
+    host = get_CNN_attr(x.clone(), None, t, td)
+    devm = get_CNN_attr(x.clone(), None, t, dict(td, device_maps=True))
+    assert host.shape == (32, 32) and host.dtype == np.float32 and np.isfinite(host).all() and host.max() > 0
+    assert torch.is_tensor(devm) and devm.is_cuda
+    np.testing.assert_array_equal(devm.cpu().numpy(), host)
+    imgs = [torch.randn(1, 3, 32, 32, generator=torch.Generator().manual_seed(90 + i)) for i in range(3)]
+    tds = dict(td, device_maps=True)
+    for streams in (1, 3):
+        tot, used, _ = sweep_images(imgs, model, DEV, lambda xx, tt: get_CNN_attr(xx, None, tt, tds), img_hw=32, batch_size=25,
+                                    streams=streams, kind="gig")
+        assert used == 3 and set(tot) == set(KEYS) and all(np.isfinite(float(v)) for v in tot.values())

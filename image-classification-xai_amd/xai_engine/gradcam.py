@@ -12,7 +12,7 @@ import torch
 
 from . import kernels as K
 from ._lib import XaiHipError
-from .streams import CAPTURE_LOCK, backward_turn
+from .streams import backward_turn, capture
 
 
 def _grad_of_activation(score, act):
@@ -149,19 +149,9 @@ class CapturedGradCam:
         self.target = torch.zeros(self.x.shape[0], dtype=torch.int64, device=self.dev)
         self._cam = LayerGradCam(model, layer)
         self._channels = float(channels)
-        with CAPTURE_LOCK:
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                for _ in range(warmup):                       # MIOpen picks its algorithms here, never inside the capture
-                    self._run()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            torch.cuda.synchronize(self.dev)
-            self.graph = torch.cuda.CUDAGraph()
-            # thread_local: other stream workers keep launching and allocating while this thread captures; the default ("global") lets
-            # any other thread's hipMalloc invalidate the capture
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.sal = self._run()
+        for _ in range(warmup):                               # MIOpen picks its algorithms here, never inside the capture
+            self._run()
+        self.graph, self.sal = capture(self._run)
         if verify:
             self._verify(model, layer, channels)
 

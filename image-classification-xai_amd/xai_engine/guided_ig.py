@@ -10,19 +10,16 @@ The state words are read once per call, after a synchronize of the calling strea
 all of them); `GuidedIG.GetMask` keeps the reference's signature (the mirror module util/attribution_methods/GIGBuilder.py
 serves it).
 """
-import threading
-
 import torch
 
 from . import kernels as K
 from ._lib import XaiHipError
 from .ig import _logits_of, hip_device
-from .streams import CAPTURE_LOCK, backward_turn, on_worker, run_on_streams
+from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_on_streams
 
 INPUT_OUTPUT_GRADIENTS = "INPUT_OUTPUT_GRADIENTS"      # the key of GIGBuilder.py:15
 GIG_COUNTS = {"captures": 0, "captures_refused": 0, "replayed": 0, "eager": 0}     # how the passes ran (diagnostics)
-
-_thread_passes = threading.local()       # per host thread: {key: _GigPass}; a graph is replayed only by the thread that captured it
+_PASSES = ThreadGraphs(limit=4)
 
 
 def softmax_grad(model, x, targets):
@@ -34,18 +31,14 @@ def softmax_grad(model, x, targets):
     return g.contiguous()
 
 
-def _bits_equal(a, b):
-    return bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+class _GigPass(CapturedCall):
+    """Static buffers of k images; one call is K22's init and `steps` runs of one step (forward, softmax, backward, K22), replayed
+    from a hipGraph of that step once it has proven itself on the caller's first real batch (streams.CapturedCall)."""
 
+    warmup = 1                                            # the eager call runs the step `steps` times before the capture
 
-class _GigPass:
-    """Static buffers of k images and, once it has proven itself, the hipGraph of one step (forward, softmax, backward, K22).
-
-    The first call runs eagerly on the caller's real batch, then captures one step and replays the whole call from the same inputs;
-    the capture is kept only if the replay reproduces the eager result -- bit for bit with deterministic solvers, to the solvers'
-    own run-to-run noise otherwise -- and the call returns the eager result either way.  Later calls replay (or stay eager)."""
-
-    def __init__(self, model, k, img_shape, dev, steps, fraction, max_dist, capture):
+    def __init__(self, model, k, img_shape, dev, steps, fraction, max_dist):
+        super().__init__(GIG_COUNTS, (GRAD_RTOL, 0))
         self.model, self.steps, self.fraction, self.max_dist = model, steps, fraction, max_dist
         self.xin = torch.zeros((k,) + img_shape, dtype=torch.float32, device=dev)
         self.base = torch.zeros_like(self.xin)
@@ -54,81 +47,23 @@ class _GigPass:
         self.l1 = torch.zeros(k, dtype=torch.float32, device=dev)
         self.state = torch.zeros((k, 4), dtype=torch.int32, device=dev)
         self.t = torch.zeros(k, dtype=torch.int64, device=dev)
-        self.graph = None
-        self.ok = None if capture else False
 
-    def _step(self):
+    def step(self):
         g = softmax_grad(self.model, self.x, self.t)
         K.gig_step(self.xin, self.base, g, self.steps, self.fraction, self.max_dist, self.x, self.attr, self.l1, self.state)
 
-    def _init(self):
+    def compose(self, run):
         K.gig_init(self.xin, self.base, self.x, self.attr, self.l1, self.state)
-
-    def _eager(self):
-        self._init()
         for _ in range(self.steps):
-            self._step()
+            run()
+        return self.attr, self.state
 
-    def _replay(self):
-        self._init()
-        for _ in range(self.steps):
-            self.graph.replay()
-
-    def _prove(self):
-        cur = torch.cuda.current_stream(self.x.device)
-        self._eager()
-        eager_attr, eager_state = self.attr.clone(), self.state.clone()
-        cur.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with CAPTURE_LOCK, torch.autograd.set_multithreading_enabled(False):
-                # the backward runs inline on this thread (streams.py); thread_local: other threads may go on launching
-                with torch.cuda.graph(graph, stream=cur if on_worker() else None, capture_error_mode="thread_local"):
-                    self._step()
-            self.graph = graph
-            self._replay()
-            cur.synchronize()
-            if torch.backends.cudnn.deterministic:
-                ok = _bits_equal(self.attr, eager_attr) and torch.equal(self.state, eager_state)
-            else:
-                ok = torch.equal(self.state, eager_state) and bool(
-                    (self.attr - eager_attr).abs().max() <= 2e-2 * eager_attr.abs().max())
-        except Exception:                                 # a classifier that cannot be captured: eager
-            ok = False
-        self.ok = bool(ok)
-        GIG_COUNTS["captures" if self.ok else "captures_refused"] += 1
-        if not self.ok:
-            self.graph = None                             # give the graph's memory pool back
-        self.attr.copy_(eager_attr)
-        self.state.copy_(eager_state)
-
-    def __call__(self, xin, base, targets):
+    def __call__(self, xin, base, targets, graphs=True):
         self.xin.copy_(xin)
         self.base.copy_(base)
         self.t.copy_(targets)
-        if self.ok is None:
-            self._prove()
-        elif self.ok:
-            GIG_COUNTS["replayed"] += 1
-            self._replay()
-        else:
-            GIG_COUNTS["eager"] += 1
-            self._eager()
-        return self.attr.clone(), self.state.clone()
-
-
-def _pass_for(model, k, img_shape, dev, steps, fraction, max_dist):
-    """This thread's `_GigPass` for k images of `img_shape` (created, and proven on its first real batch, on first use)."""
-    cache = getattr(_thread_passes, "passes", None)
-    if cache is None:
-        cache = _thread_passes.passes = {}
-    key = (id(model), k, img_shape, str(dev), int(steps), float(fraction), float(max_dist),
-           bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark))
-    if key not in cache:
-        if len(cache) >= 4:
-            cache.pop(next(iter(cache)))
-        cache[key] = _GigPass(model, k, img_shape, dev, steps, fraction, max_dist, capture=True)
-    return cache[key]
+        attr, state = self.run() if graphs else self.eager()
+        return attr.clone(), state.clone()
 
 
 def _raise_on_status(state, first=0):
@@ -170,11 +105,11 @@ def guided_ig_batch(x, model, targets, steps=50, fraction=0.25, max_dist=0.02, b
 
     def one_pass(lo, hi):
         if graphs:
-            p = _pass_for(model, hi - lo, img_shape, dev, steps, fraction, max_dist)
+            key = (hi - lo, img_shape, int(steps), float(fraction), float(max_dist))
+            p = _PASSES.get(model, dev, key, lambda: _GigPass(model, hi - lo, img_shape, dev, steps, fraction, max_dist))
         else:
-            GIG_COUNTS["eager"] += 1
-            p = _GigPass(model, hi - lo, img_shape, dev, steps, fraction, max_dist, capture=False)
-        return p(x[lo:hi], base[lo:hi], targets[lo:hi])
+            p = _GigPass(model, hi - lo, img_shape, dev, steps, fraction, max_dist)
+        return p(x[lo:hi], base[lo:hi], targets[lo:hi], graphs)
 
     n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))
     if n_streams == 1:

@@ -7,13 +7,12 @@ shapes, the print-and-return-zeros error convention); `ig_batch` is the multi-im
 path the reference does not have.
 """
 import contextlib
-import threading
 
 import torch
 
 from . import kernels as K
 from ._lib import XaiHipError
-from .streams import CAPTURE_LOCK, backward_turn, on_worker, run_on_streams
+from .streams import GRAD_RTOL, LOGIT_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_on_streams
 
 
 def hip_device(device):
@@ -114,7 +113,8 @@ def _path(x, base, alphas, model, batch_size, target_class, want_grads=True):
 
 def _worker_pass(x, base, alphas, model, batch_size, target_class):
     """On a stream worker, when ONE classifier pass covers the whole path (batch_size == steps): this thread's hipGraph of that pass
-    (`_CapturedPass`, shared with ig_batch) -> (gradients (steps, C,H,W), logits (steps,)), else None.  Same kernels, same bits."""
+    (`_CapturedPass`, shared with ig_batch; its first call proves the capture, streams.CapturedCall) -> (gradients (steps, C,H,W),
+    logits (steps,)), else None.  Same kernels, same bits."""
     steps = alphas.shape[0]
     if not on_worker() or batch_size != steps or x.shape[0] != 1:
         return None
@@ -125,10 +125,7 @@ def _worker_pass(x, base, alphas, model, batch_size, target_class):
     else:
         t = torch.full((1,), int(target_class), dtype=torch.int64, device=x.device)
     cp = _thread_pass(model, 1, steps, tuple(x.shape[1:]), x.device, alphas, base)
-    if cp is None:
-        return None
-    PASS_COUNTS["replayed"] += 1
-    return cp(x, t, base if torch.is_tensor(base) else None)
+    return None if cp is None else cp(x, t, base if torch.is_tensor(base) else None)
 
 
 def _path_sum(x, base, alphas, model, batch_size, target_class):
@@ -241,53 +238,24 @@ def IDGI(input, model, steps, batch_size, baseline, device, target_class):
     return K.idgi_accum(g, logits[0].contiguous(), K.sumsq(g))
 
 
-_thread_graphs = threading.local()        # per host thread: {key: _CapturedPass} -- a graph is replayed only by the thread that captured it
 PASS_COUNTS = {"replayed": 0, "eager": 0, "captures": 0, "captures_refused": 0}     # how ig_batch's passes ran (diagnostics; bench.py prints them)
+_PASSES = ThreadGraphs(limit=4)          # a handful of (model, shape) combinations per stream worker
 
 
-class _CapturedPass:
-    """K1 + classifier forward + backward of `k` images x `steps` interpolants as ONE hipGraph on static buffers.
+class _CapturedPass(CapturedCall):
+    """K1 + classifier forward + backward of `k` images x `steps` interpolants on static buffers, replayed as ONE hipGraph by the
+    stream worker that captured it (streams.CapturedCall: why, and how a capture proves itself).  Measured on ResNet-50: 77-84
+    attributions/s eager against 84-85 replayed."""
 
-    Why: with one host thread per stream (streams.py) the passes of a step are enqueued by three Python threads that share one
-    interpreter lock -- ~1000 launches and ~100 autograd nodes per pass; the host, not the GPU, becomes the limit (77-84 attributions/s
-    eager against 84-85 replayed, ResNet-50).  A replay is one launch.
-    Why it is safe: a graph bakes in the pointers of the library workspaces its kernels were captured with, and those belong to the
-    capturing THREAD's MIOpen / rocBLAS handles (streams.py).  Each stream worker captures its own graph, on its own handles, with
-    autograd inline, and is the only thread that ever replays it -- graphs of different workers share nothing.  (Graphs captured by ONE
-    thread and replayed on several streams corrupt each other: profiles/r03_exp_ig_graph_streams*.jsonl.)
-    The capture proves itself: its first replay must reproduce the eager pass on the same buffers -- bit for bit with deterministic
-    solvers, to the solvers' own run-to-run noise otherwise -- else the pass stays eager."""
-
-    def __init__(self, model, k, steps, img_shape, dev, alphas, base_tensor, base_scalar):
+    def __init__(self, model, k, steps, img_shape, dev, alphas, base):
+        super().__init__(PASS_COUNTS, (GRAD_RTOL, LOGIT_RTOL))
         self.x = torch.zeros((k,) + img_shape, dtype=torch.float32, device=dev)
         self.t = torch.zeros(k, dtype=torch.int64, device=dev)
-        self.base = torch.zeros_like(self.x) if base_tensor else None
-        self.base_scalar, self.alphas, self.model, self.steps, self.img_shape = base_scalar, alphas, model, steps, img_shape
-        cur = torch.cuda.current_stream(dev)
-        for _ in range(2):                                    # MIOpen picks its solvers and loads their kernels here, never inside the capture
-            eager_g, eager_s = self._run()
-        cur.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        try:
-            with CAPTURE_LOCK:
-                # thread_local: the other stream workers may keep launching and allocating while this thread captures
-                with torch.cuda.graph(self.graph, stream=cur, capture_error_mode="thread_local"):
-                    self.g, self.scores = self._run()
-            self.graph.replay()
-            cur.synchronize()
-        except Exception:                                     # a classifier that cannot be captured (host syncs in its forward, ...): eager
-            self.g = None
-        if self.g is None:
-            self.ok = False
-        elif torch.backends.cudnn.deterministic:
-            self.ok = bool(torch.equal(self.g, eager_g) and torch.equal(self.scores, eager_s))
-        else:       # MIOpen's non-deterministic solvers differ run to run by themselves (~1e-3 after ReLU-gate flips); a broken replay is off by tens of per cent
-            self.ok = bool((self.g - eager_g).abs().max() <= 2e-2 * eager_g.abs().max() and (self.scores - eager_s).abs().max() <= 1e-3 * eager_s.abs().max())
-        PASS_COUNTS["captures" if self.ok else "captures_refused"] += 1
-        if not self.ok:
-            self.graph = self.g = self.scores = None          # give the graph's memory pool back; the pass stays eager
+        self.base = torch.zeros_like(self.x) if torch.is_tensor(base) else None
+        self.base_scalar = None if torch.is_tensor(base) else float(base)
+        self.alphas, self.model, self.steps, self.img_shape = alphas, model, steps, img_shape
 
-    def _run(self):
+    def step(self):
         imgs = K.ig_interp(self.x, self.base if self.base is not None else self.base_scalar, self.alphas)
         flat = imgs.view((-1,) + self.img_shape).requires_grad_(True)
         out = _logits_of(self.model(flat))
@@ -300,22 +268,14 @@ class _CapturedPass:
         self.t.copy_(targets, non_blocking=True)
         if self.base is not None:
             self.base.copy_(base, non_blocking=True)
-        self.graph.replay()
-        return self.g, self.scores
+        return self.run()
 
 
 def _thread_pass(model, k, steps, img_shape, dev, alphas, base):
-    """This stream worker's graph of a k-image pass (captured on first use), or None when the pass has to stay eager."""
-    cache = getattr(_thread_graphs, "passes", None)
-    if cache is None:
-        cache = _thread_graphs.passes = {}
-    key = (id(model), k, steps, img_shape, str(dev), torch.is_tensor(base), None if torch.is_tensor(base) else float(base),
-           bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark))
-    if key not in cache:
-        if len(cache) >= 4:                                                       # a handful of (model, shape) combinations per thread
-            cache.pop(next(iter(cache)))
-        cache[key] = _CapturedPass(model, k, steps, img_shape, dev, alphas, torch.is_tensor(base), None if torch.is_tensor(base) else float(base))
-    return cache[key] if cache[key].ok else None
+    """This stream worker's `_CapturedPass` of a k-image pass, or None once its capture has been refused (the pass stays eager)."""
+    key = (k, steps, img_shape, torch.is_tensor(base), None if torch.is_tensor(base) else float(base))
+    cp = _PASSES.get(model, dev, key, lambda: _CapturedPass(model, k, steps, img_shape, dev, alphas, base))
+    return None if cp.refused else cp
 
 
 def ig_batch(x, model, targets, steps=50, alpha_star=1, baseline=0, images_per_pass=4, want_abs=False,
@@ -338,8 +298,8 @@ def ig_batch(x, model, targets, steps=50, alpha_star=1, baseline=0, images_per_p
     rows, so the result is bit-identical to `streams=1`
     (tests/test_gpu_configs.py::test_classifier_passes_on_several_streams_are_bit_identical_to_one_stream).
     `graphs` (with `streams` > 1; default on): every stream worker replays its full-size passes as ONE hipGraph it captured itself
-    (`_CapturedPass`: the host stops being the limit once three threads enqueue); a ragged last pass, or a capture whose first replay
-    does not reproduce the eager pass bit for bit, runs eagerly.
+    (`_CapturedPass`: the host stops being the limit once three threads enqueue); a ragged last pass runs eagerly, and so does every
+    pass of a capture that `streams.CapturedCall` refused on its first call (its replay did not reproduce the eager pass).
     `event_sink`: optional list that receives (start, end, kernel_start, kernel_stop) torch.cuda.Events of the
     accumulation launch: a pair bracketing it and a pair stamped by the dispatch itself (used by bench.py for the roofline figure)."""
     if not x.is_cuda:
@@ -369,10 +329,10 @@ def ig_batch(x, model, targets, steps=50, alpha_star=1, baseline=0, images_per_p
     def one_pass(lo, hi, on_worker=False):
         b = base[lo:hi] if torch.is_tensor(base) else base
         cp = _thread_pass(model, hi - lo, steps, img_shape, dev, alphas, base) if (on_worker and use_graphs and hi - lo == images_per_pass) else None
-        PASS_COUNTS["replayed" if cp is not None else "eager"] += 1
         if cp is not None:
             g, scores = cp(x[lo:hi], targets[lo:hi], b if torch.is_tensor(base) else None)
         else:
+            PASS_COUNTS["eager"] += 1
             imgs = K.ig_interp(x[lo:hi], b, alphas)                              # (k, steps, C,H,W)
             flat = imgs.view((-1,) + img_shape).requires_grad_(True)
             out = _logits_of(model(flat))

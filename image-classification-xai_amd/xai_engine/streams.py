@@ -25,7 +25,8 @@ over thousands of passes); that is luck, not safety.  Hence the rule:
     one device thread that all callers share.
 
 The rule is structural: it does not depend on which solver MIOpen picks for which shape.  The drivers (`ig.ig_batch`, `rise.rise`,
-`sweep.sweep_images`) apply it whenever `streams > 1`.  Code that runs backward passes from threads that are NOT workers (a caller's
+`sweep.sweep_images`) apply it whenever `streams > 1`; a worker replays its passes from hipGraphs it captured itself (`CapturedCall`,
+`ThreadGraphs`).  Code that runs backward passes from threads that are NOT workers (a caller's
 own threads, the main thread) goes through autograd's shared device thread; for those, `backward_turn` makes backward passes of a
 device take turns (a host lock around the enqueue plus a device-side event chain) -- measured unnecessary (0 of 1440 wrong without
 it) but not provably so, and it costs nothing when there is one caller.
@@ -201,3 +202,127 @@ def backward_turn(dev):
                 ev = torch.cuda.Event()
                 ev.record(cur)
                 turn.last = ev
+
+
+# ------------------------------------------------------------------------------ hipGraphs of classifier passes
+# With one host thread per stream the ~1000 launches of a pass are enqueued by several Python threads that share one interpreter
+# lock, and the host, not the GPU, becomes the limit; a replay is one launch.  A graph bakes in the library workspaces of the
+# handles it was captured with, which belong to the capturing THREAD (module docstring): each thread captures its own graphs, with
+# autograd inline, and is the only thread that replays them.  (Graphs captured by one thread and replayed on several streams corrupt
+# each other: profiles/r03_exp_ig_graph_streams*.jsonl.)
+GRAD_RTOL = 2e-2      # MIOpen's non-deterministic solvers differ run to run by ~1e-3 after ReLU-gate flips; a broken replay is off by tens of per cent
+LOGIT_RTOL = 1e-3
+
+
+def capture(step):
+    """`step()` captured as ONE hipGraph -> (graph, what `step` returned during the capture).  One capture at a time in the process
+    (`CAPTURE_LOCK`), backward nodes inline on this thread, hipStreamCaptureModeThreadLocal so that other threads go on launching
+    and allocating; on a stream worker the capture runs on its own stream, elsewhere on torch's side capture stream."""
+    graph = torch.cuda.CUDAGraph()
+    with CAPTURE_LOCK, torch.autograd.set_multithreading_enabled(False):
+        with torch.cuda.graph(graph, stream=torch.cuda.current_stream() if on_worker() else None, capture_error_mode="thread_local"):
+            out = step()
+    return graph, out
+
+
+def replay_matches(got, want, rtol):
+    """Per output: bit for bit with deterministic solvers (and always for integer outputs), else max |got - want| <= rtol * max |want|."""
+    for g, w, tol in zip(got, want, rtol, strict=True):
+        if torch.backends.cudnn.deterministic or not g.is_floating_point():
+            same = torch.equal(_bits(g), _bits(w))
+        else:
+            same = bool((g - w).abs().max() <= tol * w.abs().max())
+        if not same:
+            return False
+    return True
+
+
+def _bits(t):
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]) if t.is_floating_point() else t
+
+
+class CapturedCall:
+    """One call of a driver on its static buffers, replayed from a hipGraph once the graph has proven itself.
+
+    A subclass owns the static buffers and defines `step()` (what is captured: reads and writes static buffers only, returns None or
+    the tensors it produced) and, if a call is more than one step, `compose(run)` (one call, built from `run()` -- an eager step or a
+    replay -- returning the call's outputs).  The caller fills the buffers and calls `run()`.
+    Proof, on the first call, i.e. on the caller's first real inputs: the call runs eagerly `warmup` times (MIOpen settles its solvers
+    here, never inside the capture), `step` is captured and the call is replayed; the graph is kept only if `replay_matches` the last
+    eager outputs, per output with the relative tolerance `rtol[i]`.  Kept: the replayed outputs are returned and every later call
+    replays.  Refused (an exception in the capture or the replay, or "replay differs", kept in `refused`): the graph and its memory pool
+    are given back, the eager outputs are returned and later calls run eagerly.  `counts` (the driver's dict) counts every call once
+    as "replayed" or "eager" and the proof once as "captures" or "captures_refused"."""
+
+    warmup = 2
+
+    def __init__(self, counts, rtol):
+        self.counts, self.rtol = counts, rtol
+        self.graph = self._outputs = self.refused = None
+
+    def step(self):
+        raise NotImplementedError
+
+    def compose(self, run):
+        return run()
+
+    def run(self):
+        if self.graph is not None:
+            self.counts["replayed"] += 1
+            return self.compose(self._replay)
+        if self.refused is not None:
+            return self.eager()
+        return self._prove()
+
+    def eager(self):
+        self.counts["eager"] += 1
+        return self.compose(self.step)
+
+    def _replay(self):
+        self.graph.replay()
+        return self._outputs
+
+    def _prove(self):
+        for _ in range(self.warmup):
+            want = self.compose(self.step)
+        want = tuple(t.clone() for t in want)             # the replay overwrites outputs that are static buffers
+        try:
+            self.graph, self._outputs = capture(self.step)
+            got = self.compose(self._replay)
+            torch.cuda.current_stream().synchronize()
+        except Exception as e:                            # a classifier that cannot be captured (a host sync in its forward, ...)
+            self.refused = f"{type(e).__name__}: {e}"
+        else:
+            if not replay_matches(got, want, self.rtol):
+                self.refused = "replay differs"
+        self.counts["captures" if self.refused is None else "captures_refused"] += 1
+        self.counts["replayed" if self.refused is None else "eager"] += 1
+        if self.refused is None:
+            return got
+        self.graph = self._outputs = None                 # give the graph's memory pool back
+        return want
+
+
+class ThreadGraphs:
+    """One driver's `CapturedCall`s, per host thread (a graph is replayed only by the thread that captured it), keyed by the model,
+    the driver's key, the device and the solver switches, at most `limit` of them, first in first out (every graph keeps a private
+    memory pool for its pass's intermediate tensors).  An entry holds its model: a graph reads the weights' pointers, so the model must
+    not be freed (and its id reused by another) while the graph can be replayed."""
+
+    def __init__(self, limit):
+        self.limit = limit
+        self._local = threading.local()
+
+    def entries(self):
+        """this thread's {key: (model, entry)}"""
+        return self._local.__dict__.setdefault("entries", {})
+
+    def get(self, model, dev, key, make):
+        """this thread's entry for (model, dev, key), created by `make()` on first use"""
+        entries = self.entries()
+        key = (id(model), str(dev), bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark)) + tuple(key)
+        if key not in entries:
+            if len(entries) >= self.limit:
+                entries.pop(next(iter(entries)))
+            entries[key] = (model, make())
+        return entries[key][1]

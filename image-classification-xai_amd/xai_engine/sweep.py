@@ -13,7 +13,6 @@ MonotonicityTest.py:93-120): 3 + 3*n_steps classifier passes instead of ~8*(n_st
 import collections
 import csv
 import os
-import threading
 import time
 from collections import Counter
 
@@ -29,7 +28,7 @@ from .guided_ig import guided_ig_batch
 from .ig import IG, IDG, getGradientsParallel, hip_device, _logits_of
 from .perturb import (AICMetric, MASMetric, MonotonicityMetric, PositiveNegativePerturbation, _Probe, sequence_stats)
 from .smooth import smoothGrad
-from .streams import CAPTURE_LOCK
+from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
 CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "sg", "gc")
@@ -169,43 +168,23 @@ def run_perturbation(input_tensor, attribution, testing_dict, CLIP_test_info=Non
                     "MONO_pos": MONO_pos, "MONO_neg": MONO_neg})
 
 
-_thread_forwards = threading.local()     # per host thread: {key: _CapturedForward}
 FORWARD_COUNTS = {"replayed": 0, "eager": 0, "captures": 0, "captures_refused": 0}
+_FORWARDS = ThreadGraphs(limit=6)
 
 
-class _CapturedForward:
-    """The classifier's forward pass for a batch of b step images as ONE hipGraph on a static input buffer, captured and replayed by
-    one stream worker only (same reasoning as ig._CapturedPass: with one host thread per stream the ~250 launches of every forward
-    batch are enqueued under one interpreter lock; a replay is one launch, and a graph captured on the worker's own library
-    handles shares nothing with the other workers' graphs).  Its first replay must reproduce the eager forward (bit for bit with
-    deterministic solvers)."""
+class _CapturedForward(CapturedCall):
+    """The classifier's forward pass for a batch of b step images on a static input buffer `x` (K6 writes the step images into it),
+    replayed as ONE hipGraph by the stream worker that captured it (streams.CapturedCall; with one host thread per stream the ~250
+    launches of every forward batch are otherwise enqueued under one interpreter lock)."""
 
     def __init__(self, model, b, img_shape, dev):
+        super().__init__(FORWARD_COUNTS, (LOGIT_RTOL,))
+        self.model = model
         self.x = torch.zeros((b,) + tuple(img_shape), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
+
+    def step(self):
         with torch.no_grad():
-            for _ in range(2):
-                eager = _logits_of(model(self.x)).detach().clone()
-            cur.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            self.logits = None
-            try:
-                with CAPTURE_LOCK:
-                    with torch.cuda.graph(self.graph, stream=cur, capture_error_mode="thread_local"):
-                        self.logits = _logits_of(model(self.x))
-                self.graph.replay()
-                cur.synchronize()
-            except Exception:                                  # a classifier whose forward cannot be captured: eager
-                self.logits = None
-        if self.logits is None:
-            self.ok = False
-        elif torch.backends.cudnn.deterministic:
-            self.ok = bool(torch.equal(self.logits, eager))
-        else:                                                  # non-deterministic solvers: to their own run-to-run noise
-            self.ok = bool((self.logits - eager).abs().max() <= 1e-3 * eager.abs().max())
-        FORWARD_COUNTS["captures" if self.ok else "captures_refused"] += 1
-        if not self.ok:
-            self.graph = self.logits = None
+            return (_logits_of(self.model(self.x)),)
 
 
 class PerturbationSweep:
@@ -225,24 +204,16 @@ class PerturbationSweep:
             return _Probe(_logits_of(self.model(images)).detach(), target, out, offset)
 
     def _captured(self, b, img_shape):
-        """this thread's graph of a b-image forward, or None; only on stream workers (`graphs` is set by sweep_images)"""
-        if not getattr(_thread_forwards, "enabled", False):
-            return None
-        cache = getattr(_thread_forwards, "graphs", None)
-        if cache is None:
-            cache = _thread_forwards.graphs = {}
-        key = (id(self.model), b, tuple(img_shape), str(self.dev), bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark))
-        if key not in cache:
-            if len(cache) >= 6:
-                cache.pop(next(iter(cache)))
-            cache[key] = _CapturedForward(self.model, b, img_shape, self.dev)
-        return cache[key] if cache[key].ok else None
+        """this thread's graph of a b-image forward, or None once its capture has been refused"""
+        cf = _FORWARDS.get(self.model, self.dev, (b, tuple(img_shape)), lambda: _CapturedForward(self.model, b, img_shape, self.dev))
+        return None if cf.refused else cf
 
-    def launch(self, input_tensor, attribution):
+    def launch(self, input_tensor, attribution, graphs=False):
         """Queue the whole device part of one image (probes, ranking, three sequences) and an asynchronous
         copy of the curves into pinned host memory; returns a handle for `finish`.  Nothing here waits for the
         GPU, so the next image can be queued (or the previous one finished) while this one runs.
-        `attribution`: (H,W) float32 NumPy array or device tensor (a device tensor avoids the upload)."""
+        `attribution`: (H,W) float32 NumPy array or device tensor (a device tensor avoids the upload).
+        `graphs` (stream workers only, sweep_images): replay the forward passes of the step batches from this thread's hipGraphs."""
         dev = self.dev
         n_steps, step, batches = curves.step_plan(self.HW, self.step_size, self.batch_size)
         if input_tensor.is_cuda:
@@ -267,17 +238,15 @@ class PerturbationSweep:
         img_shape = tuple(img.shape[1:])
 
         def slot_for(b):
-            cf = self._captured(b, img_shape)
+            cf = self._captured(b, img_shape) if graphs else None
             return None if cf is None else cf.x
 
         def stats(images, tgt, out=None, offset=0):
-            cf = self._captured(images.shape[0], img_shape)
+            cf = self._captured(images.shape[0], img_shape) if graphs else None
             if cf is None or images.data_ptr() != cf.x.data_ptr():
                 FORWARD_COUNTS["eager"] += 1
                 return self._stats(images, tgt, out, offset)
-            FORWARD_COUNTS["replayed"] += 1
-            cf.graph.replay()                                  # the step images are in cf.x already (K6 wrote them there)
-            return _Probe(cf.logits, tgt, out, offset)
+            return _Probe(cf.run()[0], tgt, out, offset)      # the step images are in cf.x already (K6 wrote them there)
 
         ins = sequence_stats(stats, blurred[0], img[0], f_desc, n_steps, batches, target, pb, slot_for)
         dele = sequence_stats(stats, img[0], zeros[0], f_desc, n_steps, batches, target, orig, slot_for)
@@ -477,7 +446,8 @@ def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fuse
     the hooked ViT saves attention maps / gradients / block outputs on its modules and TIS / ViT-CX hang hooks on it, so concurrent
     passes through one such model would read each other's tensors -- use `streams=1` there (the harness does).
     `graphs` (with `streams` > 1): every stream worker replays the forward passes of its step batches as hipGraphs it captured itself
-    (`_CapturedForward`; three threads enqueueing ~250 launches per batch under one interpreter lock are otherwise the limit).
+    (`_CapturedForward`, a streams.CapturedCall; three threads enqueueing ~250 launches per batch under one interpreter lock are
+    otherwise the limit).
     Every image still runs the same kernels on the same shapes and the per-image Counters are folded in image order, so the sums are
     bit-identical to `streams=1` (tests/test_gpu_configs.py::test_classifier_passes_on_several_streams_are_bit_identical_to_one_stream).
     The third return value, seconds in attribution, is measured with HIP events on the image's stream when the map stays on the
@@ -523,7 +493,6 @@ def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fuse
         x = images[mine[pos]]
         if ws is not None:
             torch.cuda.current_stream(dev).wait_event(ready)
-            _thread_forwards.enabled = graphs
         if fused and not x.is_cuda:
             # one upload through pinned memory, queued behind the previous image's work: a pageable .to(dev) blocks the
             # host until the stream has drained, which would undo the pipelining
@@ -540,7 +509,7 @@ def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fuse
             host_seconds = time.time() - t0              # a host map: attr_fn has waited for the device itself
             timer = None
         if fused:
-            return sweep.launch(x, sal), timer, host_seconds
+            return sweep.launch(x, sal, graphs=graphs and ws is not None), timer, host_seconds
         if timer is not None:
             timer[1].synchronize()
             host_seconds, timer = timer[0].elapsed_time(timer[1]) * 1e-3, None

@@ -611,3 +611,15 @@ def test_stream_workers_fail_loudly_without_a_device():
     with pytest.raises(Exception):
         streams.workers(torch.device("cuda", 0), 1)
     assert not streams.on_worker()
+
+
+def test_only_streams_py_captures_hip_graphs():
+    """How a hipGraph is captured and when it is trusted is decided in one module (xai_engine/streams.py: capture, CapturedCall)."""
+    capturing = []
+    for d, _, files in os.walk(PKG):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(d, f)).read()
+                if "torch.cuda.graph(" in src or "CUDAGraph(" in src:
+                    capturing.append(os.path.relpath(os.path.join(d, f), PKG))
+    assert capturing == [os.path.join("xai_engine", "streams.py")]

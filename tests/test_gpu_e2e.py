@@ -126,6 +126,32 @@ def test_IG_streams_when_alpha_star_is_1_and_equals_the_buffered_flow_bit_for_bi
         ig_batch(xs5, model, ts, steps=50, alpha_star=.9, buffered=False)
 
 
+class Syncing(torch.nn.Module):
+    """A forward that waits for the device: illegal inside a stream capture."""
+
+    def __init__(self, inner):
+        super().__init__()
+        self.inner = inner
+
+    def forward(self, x):
+        assert float(x.detach().sum()) == float(x.detach().sum())
+        return self.inner(x)
+
+
+class SquaresWhenCaptured(torch.nn.Module):
+    """Captures, but the graph computes inner(x + x * x) where the eager pass computes inner(x): the two agree on an all-zero input
+    (value and input gradient) and nowhere else, so only a proof on real inputs can refuse the graph."""
+
+    def __init__(self, inner):
+        super().__init__()
+        self.inner = inner
+
+    def forward(self, x):
+        if torch.cuda.is_current_stream_capturing():
+            x = x + x * x
+        return self.inner(x)
+
+
 def test_ig_batch_on_stream_workers_with_and_without_graphs_and_with_an_uncapturable_classifier():
     """ig_batch(streams=3): every worker replays its passes as its own hipGraph when the classifier can be captured, and runs them eagerly
     when it cannot (a forward with a host sync) or when graphs are switched off -- the same bits as one stream in all three cases."""
@@ -144,15 +170,6 @@ def test_ig_batch_on_stream_workers_with_and_without_graphs_and_with_an_uncaptur
     np.testing.assert_array_equal(with_graphs.cpu().numpy(), one.cpu().numpy())
     no_graphs = ig_batch(xs, model, ts, steps=50, images_per_pass=2, streams=3, graphs=False)
     np.testing.assert_array_equal(no_graphs.cpu().numpy(), one.cpu().numpy())
-
-    class Syncing(torch.nn.Module):                      # a forward that waits for the device: illegal inside a stream capture
-        def __init__(self, inner):
-            super().__init__()
-            self.inner = inner
-
-        def forward(self, x):
-            assert float(x.detach().sum()) == float(x.detach().sum())
-            return self.inner(x)
     sync_model = Syncing(model)
     before = dict(igmod.PASS_COUNTS)
     got = ig_batch(xs, sync_model, ts, steps=50, images_per_pass=2, streams=3)
@@ -171,6 +188,69 @@ def test_ig_batch_on_stream_workers_with_and_without_graphs_and_with_an_uncaptur
     for a, b in zip(maps, serial):
         np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
     np.testing.assert_array_equal(torch.stack(maps).cpu().numpy(), ig_batch(xs, model, ts, steps=50, images_per_pass=1).cpu().numpy())
+
+
+def _refusals(cache, model):
+    """the refusal reasons of `model`'s entries in a driver's graph cache, on each of three stream workers"""
+    from xai_engine.streams import run_on_streams
+    per_worker = run_on_streams(DEV, 3, [lambda: [e.refused for m, e in cache.entries().values() if m is model]] * 3)
+    return [r for reasons in per_worker for r in reasons]
+
+
+@pytest.mark.parametrize("wrapper", [Syncing, SquaresWhenCaptured])
+def test_refused_captures_run_eagerly_in_ig_the_sweep_and_guided_ig(wrapper):
+    """A classifier whose forward cannot be captured (a host sync), or whose graph differs from the eager pass only away from zero: every
+    driver refuses the graph on its first real inputs and keeps the reason, replays nothing, and returns the one-stream eager result."""
+    from xai_engine import ig as igmod, sweep as swmod, guided_ig as gig
+    model = tiny_from(load_golden("ig_small.npz"), DEV)
+    wrapped = wrapper(model)
+    xs = torch.randn(6, 3, 32, 32, generator=torch.Generator().manual_seed(11)).to(DEV)
+    with torch.no_grad():
+        ts = model(xs).argmax(1)
+
+    def assert_refused(counts, before, reasons):
+        assert counts["replayed"] == before["replayed"] and counts["captures"] == before["captures"], (counts, before)
+        assert counts["captures_refused"] > before["captures_refused"], (counts, before)
+        assert reasons and all(r and (r == "replay differs") == (wrapper is SquaresWhenCaptured) for r in reasons), reasons
+
+    before = dict(igmod.PASS_COUNTS)
+    got = igmod.ig_batch(xs, wrapped, ts, steps=50, images_per_pass=2, streams=3)
+    assert_refused(igmod.PASS_COUNTS, before, _refusals(igmod._PASSES, wrapped))
+    np.testing.assert_array_equal(got.cpu().numpy(), igmod.ig_batch(xs, model, ts, steps=50, images_per_pass=2).cpu().numpy())
+
+    sal = torch.rand(32, 32, generator=torch.Generator().manual_seed(12)).to(DEV)
+    imgs = [xs[i:i + 1] for i in range(3)]
+    before = dict(swmod.FORWARD_COUNTS)
+    s3, used, _ = swmod.sweep_images(imgs, wrapped, DEV, lambda x, t: sal, img_hw=32, batch_size=25, streams=3)
+    assert_refused(swmod.FORWARD_COUNTS, before, _refusals(swmod._FORWARDS, wrapped))
+    s1, _, _ = swmod.sweep_images(imgs, model, DEV, lambda x, t: sal, img_hw=32, batch_size=25)
+    assert used == 3
+    np.testing.assert_array_equal([s3[k] for k in swmod.KEYS], [s1[k] for k in swmod.KEYS])
+
+    before = dict(gig.GIG_COUNTS)
+    got = gig.guided_ig_batch(xs, wrapped, ts)
+    assert_refused(gig.GIG_COUNTS, before, [e.refused for m, e in gig._PASSES.entries().values() if m is wrapped])
+    assert torch.equal(got, gig.guided_ig_batch(xs, model, ts, graphs=False))
+
+
+def test_the_sweeps_graph_cache_keeps_its_model_alive():
+    """A cached forward graph reads its model's weights: the graph cache holds the model, so a model its caller has dropped is neither
+    freed nor its id reused by another model while its graphs can be replayed."""
+    import gc
+    import weakref
+    from xai_engine.streams import run_on_streams
+    from xai_engine.sweep import FORWARD_COUNTS, sweep_images
+    imgs = [torch.randn(1, 3, 32, 32, generator=torch.Generator().manual_seed(20 + i)) for i in range(3)]
+    sal = torch.rand(32, 32, generator=torch.Generator().manual_seed(23)).to(DEV)
+    before = FORWARD_COUNTS["replayed"]
+    model = tiny_from(load_golden("ig_small.npz"), DEV)
+    sweep_images(imgs, model, DEV, lambda x, t: sal, img_hw=32, batch_size=25, streams=3)
+    assert FORWARD_COUNTS["replayed"] > before
+    run_on_streams(DEV, 3, [lambda: None] * 3)            # the workers drop their last sweep job (and with it the sweep's closures)
+    alive = weakref.ref(model)
+    del model
+    gc.collect()
+    assert alive() is not None
 
 
 def test_IDG_IDGI_and_helpers(attr):

@@ -80,7 +80,28 @@ class SelectedImages:
     def __getitem__(self, i):
         if isinstance(i, slice):
             return [self[j] for j in range(*i.indices(len(self.names)))]
-        return normalize(load_image(os.path.join(self.root, self.names[i]), self.img_hw), self.mean, self.std).unsqueeze(0)
+        return self.load(i)[0]
+
+    def load(self, i):
+        """(normalised (1,3,H,W) tensor, load_image's (3,H,W) [0,1] tensor itself) of image i"""
+        trans = load_image(os.path.join(self.root, self.names[i]), self.img_hw)
+        return normalize(trans, self.mean, self.std).unsqueeze(0), trans
+
+    def with_trans(self):
+        """The same images as pairs (normalised tensor, (load_image's tensor, file name)): sweep_images(..., extra=True)."""
+        return _WithTrans(self)
+
+
+class _WithTrans:
+    def __init__(self, images):
+        self.images = images
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, i):
+        x, trans = self.images.load(i)
+        return x, (trans, self.images.names[i])
 
 
 def _verdict(model, blur, dev, path, img_hw, mean, std):
@@ -204,6 +225,18 @@ def evaluate_perturbation(testing_dict, rank=0, world=1, fused=True, out_dir="pe
     def attr_fn(x, target):
         return (_sweep.get_VIT_attr if is_vit else _sweep.get_CNN_attr)(x, None, target, td_attr)
 
+    # rows that need the un-normalised image the harness loaded (the reference passes trans_img, :584) get load_image's tensor
+    extra = not is_vit and testing_dict["attr_func"] in _sweep.TRANS_ATTR_FUNCS
+    if extra:
+        images = images.with_trans()
+
+        def attr_fn(x, target, trans_and_name):             # noqa: F811
+            trans, name = trans_and_name
+            try:
+                return _sweep.get_CNN_attr(x, trans, target, td_attr)
+            except ValueError as e:
+                raise ValueError(f"{name}: {e}") from e
+
     identity = _sweep.sweep_identity(attr_func=testing_dict["attr_func"], model_name=testing_dict["model_name"],
                                      image_count=testing_dict["image_count"], files="|".join(names),
                                      weights=testing_dict.get("weights_path", ""), fold="reference" if reference_counter else "sums")
@@ -211,7 +244,7 @@ def evaluate_perturbation(testing_dict, rank=0, world=1, fused=True, out_dir="pe
                                                  batch_size=testing_dict["batch_size"], fused=fused, rank=rank, world=world,
                                                  testing_dict=testing_dict, checkpoint=checkpoint, identity=identity,
                                                  streams=1 if is_vit else streams,      # the hooked ViT keeps per-pass state on its modules
-                                                 reference_counter=reference_counter, kind=testing_dict["attr_func"])
+                                                 reference_counter=reference_counter, kind=testing_dict["attr_func"], extra=extra)
     if rank == 0 and used:
         name = f'{testing_dict["attr_func"]}_{testing_dict["image_count"]}_images.csv'
         _sweep.write_csv(os.path.join(out_dir, testing_dict["model_name"], name), total, used, attr_time, time.time() - t_start,

@@ -586,3 +586,67 @@ def gig_step(x_input, x_baseline, grad, steps, fraction, max_dist, x, attr, l1_t
         raise ValueError("gig_step: inconsistent sizes")
     _call("xai_gig_step_f32", x_input.device, _ptr(x_input), _ptr(x_baseline), _ptr(grad), B, n, int(steps), float(fraction),
           float(max_dist), _ptr(x), _ptr(attr), _ptr(l1_total), _ptr(state))
+
+
+# ------------------------------------------------------------------------------ AGI (K23-K25)
+AGI_REASON = {0: "running", 1: "reached the class", 2: "skipped: the class is init_pred", 3: "max_iter updates"}
+I64 = torch.int64
+
+
+def _agi_pairs(data, classes, x_cur, c_delta, state, name):
+    _need(data, F32, "data"); _need(classes, I32, "classes"); _need(x_cur, F32, "x_cur"); _need(c_delta, F32, "c_delta")
+    _need(state, I32, "state")
+    B, K = data.shape[0], classes.numel()
+    n = data[0].numel() if B else 0
+    if B < 1 or K < 1 or n < 1:
+        raise ValueError(f"{name}: empty data or classes")
+    if not (x_cur.numel() == c_delta.numel() == B * K * n and state.numel() == 4 * B * K):
+        raise ValueError(f"{name}: x_cur, c_delta must hold {B * K} x {n} and state {B * K} x 4 elements")
+    return B, K, n
+
+
+def agi_init(logits, data, classes, init_pred, x_cur, c_delta, state):
+    """K23: init_pred (int64 (B,)) = argmax of logits (B, n_out); x_cur = data per pair, c_delta = 0, state per pair.
+    Pair p = image * K + k attacks classes[k] (int32 (K,), each in [0, n_out))."""
+    B, K, n = _agi_pairs(data, classes, x_cur, c_delta, state, "agi_init")
+    _need(logits, F32, "logits"); _need(init_pred, I64, "init_pred")
+    if logits.dim() != 2 or logits.shape[0] != B or init_pred.numel() != B:
+        raise ValueError("agi_init: logits must be (B, n_out) and init_pred (B,)")
+    _call("xai_agi_init_f32", data.device, _ptr(logits), _ptr(data), _ptr(classes), B, K, logits.shape[1], n, _ptr(init_pred),
+          _ptr(x_cur), _ptr(c_delta), _ptr(state))
+
+
+def agi_step(logits, g_adv, g_lab, data, classes, epsilon, max_iter, x_cur, c_delta, state):
+    """K24: one pgd_step iteration of every pair; logits (B*K, n_out) of the forward of x_cur, g_adv / g_lab the gradients of
+    the class's and init_pred's softmax probabilities with respect to x_cur.  Updates x_cur, c_delta and state in place."""
+    B, K, n = _agi_pairs(data, classes, x_cur, c_delta, state, "agi_step")
+    _need(logits, F32, "logits"); _need(g_adv, F32, "g_adv"); _need(g_lab, F32, "g_lab")
+    if logits.dim() != 2 or logits.shape[0] != B * K:
+        raise ValueError(f"agi_step: logits must be ({B * K}, n_out)")
+    if not g_adv.numel() == g_lab.numel() == B * K * n:
+        raise ValueError("agi_step: g_adv and g_lab must have the shape of x_cur")
+    if int(max_iter) < 1:
+        raise ValueError("agi_step: max_iter must be >= 1")
+    _call("xai_agi_step_f32", data.device, _ptr(logits), _ptr(g_adv), _ptr(g_lab), _ptr(data), _ptr(classes), B, K, logits.shape[1],
+          n, float(epsilon), int(max_iter), _ptr(x_cur), _ptr(c_delta), _ptr(state))
+
+
+def agi_heatmap(c_delta, n_img, q_lo=80, q_hi=99, out=None, step_grad=None, qu=None):
+    """K25: c_delta (n_img * K, C, H, W) -> the normalised heat map (n_img, H, W) of evaluatePerturbation.py:132-138; optionally
+    writes step_grad (n_img, C, H, W) and qu (n_img, 2) = the two percentiles."""
+    _need(c_delta, F32, "c_delta")
+    if c_delta.dim() != 4 or n_img < 1 or c_delta.shape[0] % n_img:
+        raise ValueError("agi_heatmap: c_delta must be (n_img * K, C, H, W)")
+    if not (0.0 <= float(q_lo) <= 100.0 and 0.0 <= float(q_hi) <= 100.0):
+        raise ValueError("agi_heatmap: percentiles must be in [0, 100]")
+    K, C, H, W = c_delta.shape[0] // n_img, c_delta.shape[1], c_delta.shape[2], c_delta.shape[3]
+    if out is None:
+        out = torch.empty((n_img, H, W), dtype=F32, device=c_delta.device)
+    for t, nm, cnt in ((out, "out", n_img * H * W), (step_grad, "step_grad", n_img * C * H * W), (qu, "qu", 2 * n_img)):
+        if t is not None:
+            _need(t, F32, nm)
+            if t.numel() != cnt:
+                raise ValueError(f"agi_heatmap: {nm} must hold {cnt} elements")
+    _call("xai_agi_heatmap_f32", c_delta.device, _ptr(c_delta), n_img, K, C, H * W, float(q_lo), float(q_hi), _ptr(out), _ptr(step_grad),
+          _ptr(qu))
+    return out

@@ -152,6 +152,29 @@ def run(device="cuda:0", verbose=True):
     cam = K.attn_cam(attns[0][None], grads_[0][None])[0]
     c = (attns[0].double() * grads_[0].double()).mean(0)[0, 1:].clamp(min=0)
     check("attn_cam", _rel(cam, (c - c.min()) / (c.max() - c.min())), 1e-5)
+    # K23-K25: AGI (init, one fgsm iteration, the percentile-clipped map)
+    import numpy as np
+    Bq, Kq, n_out = 2, 3, 10
+    data = torch.rand(Bq, 3, 32, 32, device=dev, generator=gen)
+    lg = rnd(Bq, n_out)
+    cls = torch.tensor([0, 4, 9], dtype=torch.int32).to(dev)
+    xa, cda = torch.empty((Bq * Kq, 3, 32, 32), device=dev), torch.empty((Bq * Kq, 3, 32, 32), device=dev)
+    sta, ipa = torch.empty((Bq * Kq, 4), dtype=torch.int32, device=dev), torch.empty(Bq, dtype=torch.int64, device=dev)
+    K.agi_init(lg, data, cls, ipa, xa, cda, sta)
+    check("agi_init (argmax, state)", float((ipa != lg.argmax(1)).sum() + (sta[:, 0].view(Bq, Kq).long() != (cls.long()[None] != ipa[:, None]).long()).sum()), 0.0)
+    ga, gl, lp = rnd(Bq * Kq, 3, 32, 32), rnd(Bq * Kq, 3, 32, 32), rnd(Bq * Kq, n_out)
+    K.agi_step(lp, ga, gl, data, cls, 0.05, 20, xa, cda, sta)
+    upd = (sta[:, 3] == 1).view(-1, 1, 1, 1)
+    d0 = data.repeat_interleave(Kq, 0)
+    xw = torch.clamp(d0 + 0.05 * torch.sign(ga), 0, 1)
+    check("agi_step (bitwise vs torch)", float(((xa != torch.where(upd, xw, d0)).sum() + (cda != torch.where(upd, -gl * (xw - d0), 0.0)).sum())), 0.0)
+    hm = K.agi_heatmap(cda, Bq, 80, 99)
+    want = []
+    for b in range(Bq):
+        s = cda[b * Kq:(b + 1) * Kq].sum(0).mean(0).cpu().numpy()
+        q, u = np.percentile(s, 80), np.percentile(s, 99)
+        want.append((np.clip(s, q, u) - q) / (u - q))
+    check("agi_heatmap", _rel(hm, torch.from_numpy(np.stack(want)).to(dev)), 1e-5)
     wrong = unprotected = 0.0
     for _ in range(3):          # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

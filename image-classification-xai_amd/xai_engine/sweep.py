@@ -31,7 +31,8 @@ from .smooth import smoothGrad
 from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "sg", "gc")
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "gc")
+TRANS_ATTR_FUNCS = ("agi",)          # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
 
@@ -65,6 +66,25 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         # :114-118: zero baseline, 50 steps, max_dist 1.0, fraction 0.5, the gradient of the softmax probability
         t = target_class.reshape(1) if torch.is_tensor(target_class) else torch.tensor([int(target_class)])
         saliency_map = guided_ig_batch(input_tensor.to(dev), model, t, steps=steps, fraction=0.5, max_dist=1.0, baseline=baseline)[0]
+    elif attr_function == "agi":
+        # :119-139: epsilon 0.05, topk 1, max_iter 20, selected_ids range(0, 999, 1000) == [0], the reference's Normalize in
+        # front of the classifier, the [0, 1] image divided by 255 once more (AGI.py:31), the 80/99 percentile clip
+        if trans_img is None:
+            raise ValueError("agi: the row needs the harness's un-normalised [0, 1] image (trans_img)")
+        from .agi import agi_batch, pre_processing
+        from .harness import CNN_MEAN, CNN_STD
+        norm = testing_dict.get("normalize", (CNN_MEAN, CNN_STD))
+        mean, std = (norm.mean, norm.std) if hasattr(norm, "mean") else norm
+        topk = 1
+        data = pre_processing(torch.as_tensor(trans_img).permute(1, 2, 0).numpy().astype(np.float32), dev)
+        _, init_pred, iters, hm = agi_batch(data, model, list(range(0, 999, int(1000 / topk))), epsilon=0.05, max_iter=20,
+                                            normalize=(mean, std), want_map=True)
+        if int(iters.max()) == 0:
+            # the reference's AGI.test returns (0, 0, 0) and the harness dies in np.mean(0, axis=0) (:133)
+            raise ValueError(f"agi: the image predicted as class {int(init_pred[0])} has no attribution: every selected class "
+                             "equals its prediction or no attack made an update (the reference crashes here)")
+        sal = hm[0]
+        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     elif attr_function == "sg":
         saliency_map = smoothGrad("IG", input_tensor, model, 50, baseline, target_class, device)
     elif attr_function == "gc":
@@ -423,7 +443,8 @@ class SweepState:
 
 
 def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fused=True, rank=0, world=1, testing_dict=None,
-                 checkpoint=None, checkpoint_every=25, identity=None, streams=1, reference_counter=False, kind=None, graphs=True):
+                 checkpoint=None, checkpoint_every=25, identity=None, streams=1, reference_counter=False, kind=None, graphs=True,
+                 extra=False):
     """Attribution + ten perturbation numbers for every image this rank owns; returns the
     globally reduced (Counter of sums, images used, seconds in attribution).
     images: sequence of (1,C,H,W) CPU/device tensors (already selected -- the order-dependent
@@ -452,7 +473,9 @@ def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fuse
     bit-identical to `streams=1` (tests/test_gpu_configs.py::test_classifier_passes_on_several_streams_are_bit_identical_to_one_stream).
     The third return value, seconds in attribution, is measured with HIP events on the image's stream when the map stays on the
     device (the reference times a finished attribution, evaluatePerturbation.py:581-590; the host clock around an asynchronous
-    launch would only see the enqueue)."""
+    launch would only see the enqueue).
+    `extra`: images[i] is a pair (x, extra_i) and the attribution is attr_fn(x, target, extra_i) (the harness passes the
+    un-normalised image and its file name to the rows that need them, TRANS_ATTR_FUNCS)."""
     dev = hip_device(device)
     sweep = PerturbationSweep(model, img_hw, dev, batch_size=batch_size) if fused else None
     td = testing_dict or {"models": [model], "img_hw": img_hw, "batch_size": batch_size, "device": str(dev)}
@@ -490,7 +513,7 @@ def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fuse
     def device_part(pos):
         """Everything of one image that runs on the device, queued on the current stream of the calling thread:
         -> (handle for `finish` or the finished Counter, attribution timer or None)."""
-        x = images[mine[pos]]
+        x, ext = images[mine[pos]] if extra else (images[mine[pos]], None)
         if ws is not None:
             torch.cuda.current_stream(dev).wait_event(ready)
         if fused and not x.is_cuda:
@@ -502,7 +525,7 @@ def sweep_images(images, model, device, attr_fn, img_hw=224, batch_size=50, fuse
         timer = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         t0 = time.time()
         timer[0].record(torch.cuda.current_stream(dev))
-        sal = attr_fn(x, target)
+        sal = attr_fn(x, target, ext) if extra else attr_fn(x, target)
         timer[1].record(torch.cuda.current_stream(dev))
         host_seconds = None
         if not (torch.is_tensor(sal) and sal.is_cuda):

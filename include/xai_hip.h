@@ -39,9 +39,10 @@ typedef void* xai_stream_t; /* hipStream_t */
  *   3 = + xai_version_minor, xai_masked_sums_f32;
  *   4 = + xai_attn_head_importance_f32 (+ _workspace_bytes), xai_rave_matrices_f32, xai_rollout_row_f32,
  *         xai_residual_shares_f32, xai_attn_cam_f32;
- *   5 = + xai_gig_init_f32, xai_gig_step_f32 */
+ *   5 = + xai_gig_init_f32, xai_gig_step_f32;
+ *   6 = + xai_agi_init_f32, xai_agi_step_f32, xai_agi_heatmap_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 5
+#define XAI_ABI_MINOR 6
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -310,6 +311,40 @@ int xai_gig_init_f32(const float* x_input, const float* x_baseline, int n_img, i
 int xai_gig_step_f32(const float* x_input, const float* x_baseline, const float* grad, int n_img, int64_t n_elem, int steps,
                      float fraction, double max_dist, float* x, float* attr, const float* l1_total, int32_t* state,
                      xai_stream_t stream);
+
+/* ---- Adversarial Gradient Integration (util/attribution_methods/AGI.py:39-115, evaluatePerturbation.py:119-139) -- */
+
+/* A pair is one (image, false class) attack: pair p = image * n_cls + k attacks classes[k]; x_cur, c_delta, g_adv, g_lab are
+ * [n_img * n_cls][n_elem], data is [n_img][n_elem].  Per-pair state words int32 state[n_img * n_cls][4] =
+ *   { active, iterations done (fgsm updates applied), stop reason, updated by the last step launch }.
+ * stop reason: 0 running; 1 the argmax reached the class (the reference's break, AGI.py:64-65); 2 skipped, the class is
+ * init_pred (:97-98); 3 max_iter updates done.  An inactive pair is not touched again. */
+
+/* K23 init: init_pred[i] = the first maximal logit of logits[i] (NaN counted as maximal, as torch.max on the CPU; AGI.py:87),
+ * the state words of every pair (active when classes[k] != init_pred), x_cur = data, c_delta = 0 (the int 0 of pgd_step, :55).
+ * A kernel, not a memset, so that it can sit in front of a captured graph.
+ *   logits : [n_img][n_out] of the forward of data;  classes : [n_cls] in [0, n_out);  init_pred : int64 [n_img] */
+int xai_agi_init_f32(const float* logits, const float* data, const int32_t* classes, int n_img, int n_cls, int n_out, int64_t n_elem,
+                     int64_t* init_pred, float* x_cur, float* c_delta, int32_t* state, xai_stream_t stream);
+
+/* K24 step: one iteration of pgd_step (AGI.py:57-79) for every pair.  An active pair whose argmax of `logits` (the forward of
+ * x_cur just run) is its class stops without an update; every other active pair gets fgsm_step (:39-49), from the ORIGINAL
+ * image: x_cur = clamp(data + epsilon * sign(g_adv), 0, 1), c_delta += -g_lab * (x_cur - data), fp32 in the reference's order
+ * (sign(NaN) = sign(-0) = +0), and stops after its max_iter-th update.  Two launches (decide, update): every block of a pair
+ * acts on the same decision.  Graph-capturable: the iteration count lives in the state words.
+ *   logits : [n_img * n_cls][n_out];  g_adv, g_lab : d softmax[class] / d x_cur and d softmax[init_pred] / d x_cur */
+int xai_agi_step_f32(const float* logits, const float* g_adv, const float* g_lab, const float* data, const int32_t* classes,
+                     int n_img, int n_cls, int n_out, int64_t n_elem, float epsilon, int max_iter, float* x_cur, float* c_delta,
+                     int32_t* state, xai_stream_t stream);
+
+/* K25 heatmap (evaluatePerturbation.py:132-139 after AGI.py:93-101): per image, step_grad = the sum of its pairs' c_delta in
+ * class order from +0; hm = the channel mean (((c0 + c1) + c2) / C in fp32); q, u = NumPy 2's 'linear' percentiles q_lo,
+ * q_hi of hm (float32 arithmetic, exact order statistics); hm < q -> q, hm > u -> u, out = (hm - q) / (u - q).  A NaN in hm
+ * makes every output NaN (NumPy's NaN percentiles).  One workgroup per image.
+ *   c_delta : [n_img * n_cls][C][HW];  out : [n_img][HW];  step_grad : [n_img][C][HW] or NULL;  qu : [n_img][2] (q, u) or NULL
+ *   q_lo, q_hi in [0, 100];  HW < 2^24 */
+int xai_agi_heatmap_f32(const float* c_delta, int n_img, int n_cls, int C, int64_t HW, double q_lo, double q_hi, float* out,
+                        float* step_grad, float* qu, xai_stream_t stream);
 
 /* ---- opt-in classifier-side fusion (xai_engine/prepare.py: fuse_bn_relu) --------------- */
 

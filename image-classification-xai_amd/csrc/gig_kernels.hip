@@ -9,7 +9,9 @@
 //       statistic torch.quantile(..., interpolation='lower') returns, :267);
 //   D   l1_s (:272);
 //   E   the update of x (:282-289) and attr (:292).
-// Keys are `+inf` where x == x_max (:264) and |grad| elsewhere; non-negative floats order like their bit patterns.
+// A key is the gradient's bit pattern rotated left by one: |grad| in the upper 31 bits (non-negative floats order like their
+// bit patterns), the sign below it.  The key of +inf (kOutKey) also marks x == x_max (:264): never selected, as the reference
+// never selects grad == +inf (:268); -inf is the one key above it and is selected exactly when the threshold is infinite.
 // The histograms count with LDS atomics (integer counts do not depend on arrival order).  l1_total, l1_current and l1_s
 // are summed by one fixed tree (lane t takes elements t, t+1024, ... in order, fp64 per lane, wave butterfly, waves in
 // order) and rounded to fp32: two runs give the same bytes, and on the last step, where every remaining feature is
@@ -26,7 +28,9 @@ constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kBins = 2048;                  // 11-bit digits: bits [21,32), [10,21), [0,10)
 constexpr int kMaxSelections = XAI_GIG_MAX_SELECTIONS;   // per step; the reference needed 51 for 50 steps on a toy net
-constexpr uint32_t kInfKey = 0x7f800000u;
+constexpr uint32_t kOutKey = 0xff000000u;     // +inf rotated: x == x_max or grad == +inf
+constexpr uint32_t kNegInfKey = 0xff000001u;  // -inf rotated; every NaN is above it
+constexpr int64_t kMaxElems = int64_t{1} << 24;   // torch.quantile's own limit; up to it fp32(n_elem - 1) is exact
 
 enum : int32_t { kOk = 0, kNanKey = 1, kCap = 2, kGamma = 3, kSteps = 4 };
 
@@ -68,7 +72,8 @@ __device__ __forceinline__ float clamped_x(float x, float xi, float xb, float am
 }
 
 __device__ __forceinline__ uint32_t sel_key(float xc, float xmax, float g) {
-  return xc == xmax ? kInfKey : __float_as_uint(fabsf(g));   // fabsf clears the sign bit: -0.0 keys as +0.0; NaN > kInfKey
+  const uint32_t b = __float_as_uint(g);
+  return xc == xmax ? kOutKey : (b << 1) | (b >> 31);          // +x and -x are neighbours: 2k and 2k + 1
 }
 
 // Sum over the workgroup of one fp64 value per lane, in one fixed order; every lane gets the same bits.
@@ -204,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
         const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
         s += static_cast<double>(fabsf(xc - pi.v[u]));
         const uint32_t key = sel_key(xc, xmax, pg.v[u]);
-        if (key > kInfKey) nan_seen = 1u;
+        if (key > kNegInfKey) nan_seen = 1u;
         else atomicAdd(&hist[key >> 21], 1u);
       }
     }
@@ -254,8 +259,8 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
         }
       }
       __syncthreads();
-      thr = (hi << 10) | find_digit(hist, k, wsum, pick);
-      // ---- D: l1_s = sum |x - x_max| over the selection s = key <= thr && key != inf (:268, :272)
+      thr = (hi << 10) | find_digit(hist, k, wsum, pick) | 1u;   // | 1: |grad| <= threshold takes -x with +x
+      // ---- D: l1_s = sum |x - x_max| over the selection s = |grad| <= threshold && grad != inf (:268, :272)
       s = 0.0;
       for (int64_t i = i0; i < N; i += di) {
         const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
@@ -264,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
           float xmax;
           const float xc = clamped_x(px.v[u], pi.v[u], pb.v[u], amin, amax, xmax);
           const uint32_t key = sel_key(xc, xmax, pg.v[u]);
-          if (key <= thr && key != kInfKey) s += static_cast<double>(fabsf(xc - xmax));
+          if (key <= thr && key != kOutKey) s += static_cast<double>(fabsf(xc - xmax));
         }
       }
       const float l1_s = static_cast<float>(block_sum(s, red));
@@ -285,7 +290,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
         float xn = xc;
         if (!close) {
           const uint32_t key = sel_key(xc, xmax, pg.v[u]);
-          if (key <= thr && key != kInfKey) xn = gamma > 1.f ? xmax : xc + (xmax - xc) * gamma;
+          if (key <= thr && key != kOutKey) xn = gamma > 1.f ? xmax : xc + (xmax - xc) * gamma;
         }
         pn.v[u] = xn;
         pa.v[u] = pa.v[u] + (xn - px.v[u]) * pg.v[u];
@@ -310,7 +315,7 @@ XAI_EXPORT int xai_gig_init_f32(const float* x_input, const float* x_baseline, i
   XAI_REQUIRE_PTR(x_input); XAI_REQUIRE_PTR(x_baseline); XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(attr); XAI_REQUIRE_PTR(l1_total);
   XAI_REQUIRE_PTR(state);
   XAI_REQUIRE(n_img > 0 && n_elem > 0, XAI_E_SHAPE);
-  XAI_REQUIRE(n_img <= 65535 && n_elem < (int64_t{1} << 31), XAI_E_UNSUPPORTED);
+  XAI_REQUIRE(n_img <= 65535 && n_elem <= kMaxElems, XAI_E_UNSUPPORTED);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (vec4_ok(n_elem, x_input, x_baseline, x, attr, x))
     hipLaunchKernelGGL(gig_init_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
@@ -326,8 +331,9 @@ XAI_EXPORT int xai_gig_step_f32(const float* x_input, const float* x_baseline, c
   XAI_REQUIRE_PTR(l1_total); XAI_REQUIRE_PTR(state);
   XAI_REQUIRE(n_img > 0 && n_elem > 0 && steps > 0, XAI_E_SHAPE);
   XAI_REQUIRE(fraction >= 0.f && fraction <= 1.f && max_dist == max_dist, XAI_E_SHAPE);
-  XAI_REQUIRE(n_img <= 65535 && n_elem < (int64_t{1} << 31), XAI_E_UNSUPPORTED);
-  // torch.quantile: rank = floor(q * (n - 1)) with q an fp32 tensor, so the product rounds to fp32 first
+  XAI_REQUIRE(n_img <= 65535 && n_elem <= kMaxElems, XAI_E_UNSUPPORTED);
+  // torch.quantile: rank = floor(q * (n - 1)) with q an fp32 tensor, so the product rounds to fp32 first (n_elem - 1 < 2^24 is
+  // exact in fp32, so the rank is at most n_elem - 1)
   const float r = fraction * static_cast<float>(n_elem - 1);
   const uint32_t rank = static_cast<uint32_t>(floorf(r));
   const hipStream_t st = static_cast<hipStream_t>(stream);

@@ -296,7 +296,8 @@ int xai_attn_cam_f32(const float* attn, const float* grad, int n_img, int H, int
 /* K22 init: x = x_baseline, attr = 0, l1_total[i] = sum |x_input - x_baseline| (fp32 terms, one fixed fp64 sum order,
  * rounded to fp32), state = 0.  Replaces the set-up of guided_ig_impl, GIGBuilder.py:209-213; a kernel, not a memset,
  * so that it can sit in front of a captured graph.
- *   x_input, x_baseline, x, attr : [n_img][n_elem];  l1_total : [n_img];  state : [n_img][4] */
+ *   x_input, x_baseline, x, attr : [n_img][n_elem];  l1_total : [n_img];  state : [n_img][4]
+ * n_elem above 16 777 216 (2^24) returns XAI_E_UNSUPPORTED, as xai_gig_step_f32 does. */
 int xai_gig_init_f32(const float* x_input, const float* x_baseline, int n_img, int64_t n_elem, float* x, float* attr,
                      float* l1_total, int32_t* state, xai_stream_t stream);
 
@@ -304,10 +305,13 @@ int xai_gig_init_f32(const float* x_input, const float* x_baseline, int n_img, i
  * `while gamma > 1` loop (:246-291) on the device: clamp to x_min, l1_current and the math.isclose exit, the selection
  * of the features whose |grad| is at most the torch.quantile(..., fraction, interpolation='lower') order statistic
  * (rank floor(fp32(fraction) * fp32(n_elem - 1)), exact, keys = +inf where x == x_max), l1_s, gamma, the update of x and
- * attr += (x - x_old) * grad.  One workgroup per image; the step index is read from and advanced in state[i][0], so the
+ * attr += (x - x_old) * grad.  Infinite gradients are treated as the reference treats them: +inf is never selected
+ * (:264, :268), -inf ranks with the infinities and is selected when the threshold itself is infinite.  One workgroup per image; the step index is read from and advanced in state[i][0], so the
  * same launch serves every step (graph-capturable).  Images whose l1_total is 0 keep attr = 0 (:222-225).
  *   grad : [n_img][n_elem], the gradient at the current x;  fraction in [0, 1];  max_dist as the reference's python float
- *   x, attr : updated in place;  l1_total, state : as left by xai_gig_init_f32 */
+ *   x, attr : updated in place;  l1_total, state : as left by xai_gig_init_f32
+ * n_elem above 16 777 216 (2^24) returns XAI_E_UNSUPPORTED: torch.quantile refuses such inputs, so the reference has no
+ * result there, and only up to 2^24 is fp32(n_elem - 1) exact and the rank below n_elem. */
 int xai_gig_step_f32(const float* x_input, const float* x_baseline, const float* grad, int n_img, int64_t n_elem, int steps,
                      float fraction, double max_dist, float* x, float* attr, const float* l1_total, int32_t* state,
                      xai_stream_t stream);

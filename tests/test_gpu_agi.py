@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import agi_restated as R
+import gig_edges
 from conftest import check, load_golden
 from helpers import tiny_from
 
@@ -84,7 +85,7 @@ def test_k24_step_by_step_matches_the_reference(tag):
 def _maps():
     rng = np.random.default_rng(21)
     out = []
-    for n in (50176, 1, 2, 7, 50177):
+    for n in (50176, 1, 2, 7, 50177, 1023, 1025, 2049):
         out.append((f"random_{n}", rng.standard_normal(n).astype(np.float32)))
     out.append(("ties", np.round(rng.standard_normal(50176) * 2).astype(np.float32)))
     out.append(("constant", np.full(50176, 0.25, np.float32)))
@@ -98,6 +99,12 @@ def _maps():
     w2 = rng.standard_normal(7).astype(np.float32)
     w2[3] = np.inf
     out.append(("inf_7", w2))
+    # where the three-pass radix select has to work (the find_digit K22 shares): keys that share their top 22 bits, their top 11
+    # bits, and keys on both sides of digit boundaries (powers of two +- 1 ulp); the gradient kinds of tests/gig_edges.py
+    gen = np.random.default_rng(22)
+    for kind in ("band", "mid_band", "pow2"):
+        for n in (50176, 2049):
+            out.append((f"{kind}_{n}", gig_edges.gradient(kind, n, gen).numpy()))
     v = rng.standard_normal(50176).astype(np.float32)
     v[1234] = np.nan
     out.append(("nan", v))

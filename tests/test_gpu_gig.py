@@ -55,8 +55,9 @@ def test_k22_step_by_step_matches_the_reference(tag):
         np.testing.assert_array_equal(got[~moving], want[~moving])
         worst = max(worst, float((np.abs(got - want)[moving] / span[moving]).max()))
     # |x - x_ref| / |x_input - baseline|: 1.75e-6 (a), 1.27e-6 (b) -- all of it from the sums inside gamma: the reference loop with
-    # its two sums taken in fp64 and rounded (tests/gig_restated.py, sums changed) gives the kernel's x to the last bit on the CPU,
-    # and (l1_current - l1_target) cancels, so the fp32 rounding of torch's sums reaches gamma amplified
+    # its two sums taken in fp64 and rounded (gig_restated.step(..., sum_dtype=torch.float64)) gives the kernel's x to the last bit
+    # (checked step by step over the edge matrix, tests/test_gpu_gig_edges.py::test_k22_over_the_edge_matrix), and
+    # (l1_current - l1_target) cancels, so the fp32 rounding of torch's sums reaches gamma amplified
     check(f"gig/step_by_step/{tag}/x_over_span", worst, 0.0, 2e-6, absolute=True)
     check(f"gig/step_by_step/{tag}/mask", attr.cpu().numpy(), g[f"{tag}_mask"], 1e-5)
 

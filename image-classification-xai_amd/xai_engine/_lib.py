@@ -59,6 +59,10 @@ SIGNATURES = {
     "xai_agi_init_f32": [_p, _p, _p, _i, _i, _i, _l, _p, _p, _p, _p, _p],
     "xai_agi_step_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _i, _p, _p, _p, _p],
     "xai_agi_heatmap_f32": [_p, _i, _i, _i, _l, _d, _d, _p, _p, _p, _p],
+    "xai_ablate_features_f32": [_p, _p, _i, _i, _i, _p, _f, _i, _i, _i, _i, _l, _i, _p, _p],
+    "xai_ablate_windows_f32": [_p, _i, _i, _i, _i, _p, _f, _i, _i, _i, _i, _l, _i, _p, _p],
+    "xai_ablation_finish_features_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
+    "xai_ablation_finish_windows_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "xai_bn_act_fwd_f32": [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _p, _p],
     "xai_bn_relu_bwd_f32": [_p, _p, _p, _p, _p, _f, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p],
     "xai_maxpool_bwd_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
@@ -67,7 +71,7 @@ SIGNATURES = {
 _RESTYPE = {"xai_strerror": C.c_char_p, "xai_rank_workspace_bytes": C.c_size_t, "xai_gradcam_workspace_bytes": C.c_size_t,
             "xai_attn_head_importance_workspace_bytes": C.c_size_t}
 
-ABI_VERSION, ABI_MINOR = 1, 6       # XAI_ABI_VERSION / XAI_ABI_MINOR of include/xai_hip.h this binding was written against
+ABI_VERSION, ABI_MINOR = 1, 7       # XAI_ABI_VERSION / XAI_ABI_MINOR of include/xai_hip.h this binding was written against
 
 _lib = None
 

@@ -650,3 +650,110 @@ def agi_heatmap(c_delta, n_img, q_lo=80, q_hi=99, out=None, step_grad=None, qu=N
     _call("xai_agi_heatmap_f32", c_delta.device, _ptr(c_delta), n_img, K, C, H * W, float(q_lo), float(q_hi), _ptr(out), _ptr(step_grad),
           _ptr(qu))
     return out
+
+
+# ------------------------------------------------------------------------------ Feature Ablation / Occlusion (K26, K27)
+def window_counts(H, W, window, strides):
+    """(count_h, count_w) of captum's Occlusion over (H, W): ceil((dim - window) / stride) + 1 shifts per axis."""
+    (wh, ww), (sh, sw) = window, strides
+    if not (1 <= wh <= H and 1 <= ww <= W):
+        raise ValueError(f"occlusion: window {tuple(window)} must fit the image ({H}, {W})")
+    if not (sh >= 1 and sw >= 1 and (sh <= wh or wh == H) and (sw <= ww or ww == W)):
+        raise ValueError(f"occlusion: strides {tuple(strides)} must be >= 1 and, where the window can move, at most the window {tuple(window)}")
+    return -((wh - H) // sh) + 1, -((ww - W) // sw) + 1
+
+
+def _ablation_ids(ids, Cc, H, W):
+    """ids int32 (H, W) or (C, H, W) -> ids_C"""
+    _need(ids, I32, "ids")
+    if tuple(ids.shape) == (H, W):
+        return 1
+    if tuple(ids.shape) == (Cc, H, W):
+        return Cc
+    raise ValueError(f"ids must be ({H}, {W}) or ({Cc}, {H}, {W}), got {tuple(ids.shape)}")
+
+
+def _ablation_base(baseline, x):
+    if isinstance(baseline, torch.Tensor):
+        _need(baseline, F32, "baseline")
+        if tuple(baseline.shape) != tuple(x.shape[1:]):
+            raise ValueError(f"baseline must be a scalar or {tuple(x.shape[1:])}, got {tuple(baseline.shape)}")
+        return baseline, 0.0
+    return None, float(baseline)
+
+
+def _ablation_rows(x, n_total, first, n, out):
+    B, Cc, H, W = x.shape
+    if not (n >= 1 and 0 <= first and first + n <= B * n_total):
+        raise ValueError(f"rows [{first}, {first + n}) are not inside the {B} x {n_total} altered images")
+    if out is None:
+        return torch.empty((n, Cc, H, W), dtype=F32, device=x.device)
+    _need(out, F32, "out")
+    if out.numel() != n * Cc * H * W:
+        raise ValueError("out has the wrong size")
+    return out
+
+
+def ablate_features(x, ids, id_min, n_total, baseline, first, n, out=None):
+    """K26: rows [first, first + n) of the flat list of altered images (image * n_total + id - id_min) of x (B, C, H, W):
+    x * (1 - m) + baseline * m with m = (ids == id) -> (n, C, H, W).  ids: int32 (H, W) or (C, H, W); baseline: scalar or (C, H, W)."""
+    _need(x, F32, "x")
+    if x.dim() != 4:
+        raise ValueError("x must be (B, C, H, W)")
+    B, Cc, H, W = x.shape
+    ids_C = _ablation_ids(ids, Cc, H, W)
+    b, bs = _ablation_base(baseline, x)
+    out = _ablation_rows(x, int(n_total), int(first), int(n), out)
+    _call("xai_ablate_features_f32", x.device, _ptr(x), _ptr(ids), ids_C, int(id_min), int(n_total), _ptr(b), bs, B, Cc, H, W, int(first),
+          int(n), _ptr(out))
+    return out
+
+
+def ablate_windows(x, window, strides, baseline, first, n, out=None):
+    """K26, occlusion mode: rows [first, first + n) of the flat list (image * n_windows + k), window k of captum's enumeration
+    (row shift fastest), all channels; window, strides: (h, w) pairs."""
+    _need(x, F32, "x")
+    if x.dim() != 4:
+        raise ValueError("x must be (B, C, H, W)")
+    B, Cc, H, W = x.shape
+    ch, cw = window_counts(H, W, window, strides)
+    b, bs = _ablation_base(baseline, x)
+    out = _ablation_rows(x, ch * cw, int(first), int(n), out)
+    _call("xai_ablate_windows_f32", x.device, _ptr(x), int(window[0]), int(window[1]), int(strides[0]), int(strides[1]), _ptr(b), bs, B, Cc,
+          H, W, int(first), int(n), _ptr(out))
+    return out
+
+
+def _finish_outputs(s0, scores, B, n_total, shape, g, want_attr):
+    _need(s0, F32, "s0"); _need(scores, F32, "scores")
+    if s0.numel() != B or scores.numel() != B * n_total:
+        raise ValueError(f"s0 must hold {B} and scores {B} x {n_total} values")
+    if not want_attr and g is None:
+        raise ValueError("nothing to compute: neither the attribution nor samples")
+    if g is not None and int(g) < 1:
+        raise ValueError("g must be >= 1")
+    attr = torch.empty(shape, dtype=F32, device=s0.device) if want_attr else None
+    samples = torch.empty((shape[0], shape[1], int(g), int(g)), dtype=F32, device=s0.device) if g is not None else None
+    return attr, samples
+
+
+def ablation_finish_features(s0, scores, ids, id_min, shape, g=None, want_attr=True):
+    """K27: s0 (B,), scores (B, n_total), ids int32 (H, W) or (C, H, W) -> (attr (B, C, H, W) or None, samples (B, C, g, g) or None):
+    captum's FeatureAblation attribution and its nearest-exact g x g samples."""
+    B, Cc, H, W = (int(v) for v in shape)
+    n_total = scores.shape[-1]
+    attr, samples = _finish_outputs(s0, scores, B, n_total, (B, Cc, H, W), g, want_attr)
+    ids_C = _ablation_ids(ids, Cc, H, W)
+    _call("xai_ablation_finish_features_f32", s0.device, _ptr(s0), _ptr(scores), _ptr(ids), ids_C, int(id_min), int(n_total), B, Cc, H, W,
+          int(g or 0), _ptr(attr), _ptr(samples))
+    return attr, samples
+
+
+def ablation_finish_windows(s0, scores, window, strides, shape, g=None, want_attr=True):
+    """K27, occlusion mode: the sum of s0 - scores[k] over the windows covering an element, ascending k, over their count."""
+    B, Cc, H, W = (int(v) for v in shape)
+    ch, cw = window_counts(H, W, window, strides)
+    attr, samples = _finish_outputs(s0, scores, B, ch * cw, (B, Cc, H, W), g, want_attr)
+    _call("xai_ablation_finish_windows_f32", s0.device, _ptr(s0), _ptr(scores), int(window[0]), int(window[1]), int(strides[0]),
+          int(strides[1]), B, Cc, H, W, int(g or 0), _ptr(attr), _ptr(samples))
+    return attr, samples

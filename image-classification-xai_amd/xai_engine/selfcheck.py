@@ -175,8 +175,28 @@ def run(device="cuda:0", verbose=True):
         q, u = np.percentile(s, 80), np.percentile(s, 99)
         want.append((np.clip(s, q, u) - q) / (u - q))
     check("agi_heatmap", _rel(hm, torch.from_numpy(np.stack(want)).to(dev)), 1e-5)
+    # K26 / K27: Feature Ablation and Occlusion (altered images, attribution, nearest-exact samples)
+    xa_ = rnd(2, 3, 28, 28)
+    ids = torch.randint(0, 6, (28, 28), device=dev, generator=gen, dtype=torch.int32)
+    m = (ids[None] == torch.arange(6, device=dev).view(-1, 1, 1)).float()[:, None]                    # (6, 1, H, W)
+    want = (xa_[:, None] * (1 - m) + 0.5 * m).flatten(0, 1)
+    check("ablate_features (bitwise vs torch)", float((K.ablate_features(xa_, ids, 0, 6, 0.5, 0, 12) != want).sum()), 0.0)
+    s0_, sc_ = rnd(2), rnd(2, 6)
+    attr, smp = K.ablation_finish_features(s0_, sc_, ids, 0, xa_.shape, g=7)
+    want = ((s0_[:, None] - sc_)[:, :, None, None, None] * m[None]).sum(1).expand(2, 3, 28, 28)
+    check("ablation_finish_features", _rel(attr, want), 0.0)
+    check("ablation samples (nearest-exact)", _rel(smp, F.interpolate(attr, size=(7, 7), mode="nearest-exact")), 0.0)
+    wm = torch.zeros(9, 1, 28, 28, device=dev)
+    for k in range(9):
+        wm[k, :, (k % 3) * 8:(k % 3) * 8 + 12, (k // 3) * 8:(k // 3) * 8 + 12] = 1.0                  # row shift fastest
+    want = (xa_[:, None] * (1 - wm) + 0.0 * wm).flatten(0, 1)
+    check("ablate_windows (bitwise vs torch)", float((K.ablate_windows(xa_, (12, 12), (8, 8), 0.0, 0, 18) != want).sum()), 0.0)
+    sc_ = rnd(2, 9)
+    attr, _ = K.ablation_finish_windows(s0_, sc_, (12, 12), (8, 8), xa_.shape)
+    want = ((s0_[:, None] - sc_).double()[:, :, None, None, None] * wm[None].double()).sum(1) / wm.double().sum(0)
+    check("ablation_finish_windows", _rel(attr, want.expand(2, 3, 28, 28)), 2e-6)
     wrong = unprotected = 0.0
-    for _ in range(3):          # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
+    for _ in range(3):         # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)
         wrong, unprotected = max(wrong, w), max(unprotected, u)
     check("stream workers (wrong results)", float(wrong), 0.0)

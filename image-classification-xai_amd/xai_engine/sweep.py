@@ -31,7 +31,7 @@ from .smooth import smoothGrad
 from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "gc")
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "gc", "fa", "occ")
 TRANS_ATTR_FUNCS = ("agi",)          # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
@@ -100,6 +100,22 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
             sal = cache[key](x, target_class)[0]
         else:
             sal = gradcam_saliency(model, model.layer4, x, target_class, (img_hw, img_hw))[0]
+        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
+    elif attr_function in ("fa", "occ"):
+        # :171-176: captum's FeatureAblation over the 14 x 14 patch mask (:94-97) / Occlusion with window (3, 64, 64), stride 32;
+        # resize(downsize(.)) and |sum over channels| (:92-95, :181) come from K27's 14 x 14 samples and the up-sample kernel
+        from . import ablation
+        x = input_tensor.to(dev)
+        if attr_function == "fa":
+            # the id plane is uploaded once per stream: its upload and its readers must be ordered on one stream
+            key = (img_hw, tuple(x.shape), str(dev), torch.cuda.current_stream(dev).cuda_stream)
+            cache = testing_dict.setdefault("_fa_masks", {})
+            if key not in cache:
+                cache[key] = ablation.prepare_mask(ablation.harness_patch_mask(img_hw), x.shape, dev)
+            sal = ablation.feature_ablation_batch(x, model, target_class, cache[key], want_map=ablation.NUM_PATCHES, attribution=False)[0]
+        else:
+            sal = ablation.occlusion_batch(x, model, target_class, ablation.OCC_WINDOW, ablation.OCC_STRIDE,
+                                           want_map=ablation.NUM_PATCHES, attribution=False)[0]
         return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     else:
         print("Model-attribution mismatch, please use --help.")

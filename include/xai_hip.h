@@ -40,9 +40,10 @@ typedef void* xai_stream_t; /* hipStream_t */
  *   4 = + xai_attn_head_importance_f32 (+ _workspace_bytes), xai_rave_matrices_f32, xai_rollout_row_f32,
  *         xai_residual_shares_f32, xai_attn_cam_f32;
  *   5 = + xai_gig_init_f32, xai_gig_step_f32;
- *   6 = + xai_agi_init_f32, xai_agi_step_f32, xai_agi_heatmap_f32 */
+ *   6 = + xai_agi_init_f32, xai_agi_step_f32, xai_agi_heatmap_f32;
+ *   7 = + xai_ablate_features_f32, xai_ablate_windows_f32, xai_ablation_finish_features_f32, xai_ablation_finish_windows_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 6
+#define XAI_ABI_MINOR 7
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -349,6 +350,48 @@ int xai_agi_step_f32(const float* logits, const float* g_adv, const float* g_lab
  *   q_lo, q_hi in [0, 100];  HW < 2^24 */
 int xai_agi_heatmap_f32(const float* c_delta, int n_img, int n_cls, int C, int64_t HW, double q_lo, double q_hi, float* out,
                         float* step_grad, float* qu, xai_stream_t stream);
+
+/* ---- Feature Ablation / Occlusion (captum 0.7.0 as called at evaluatePerturbation.py:171-176) ------------------------ */
+
+/* The altered images of a call form one flat list: row r = image * n_total + j, j = feature id - id_min (feature mode) or the
+ * window index (occlusion mode).  A classifier pass is a run [first, first + n) of that list; it may cross from one image into
+ * the next.  Scores are the target logits of those rows, [n_img][n_total].  Occlusion windows span all channels; over (H, W)
+ * there are count = ceil((dim - window) / stride) + 1 shifts per axis (n_total = count_h * count_w, computed by the entries),
+ * window j starts at row (j % count_h) * stride_h, column (j / count_h) * stride_w -- captum's order, the row shift fastest --
+ * and is clipped to the image.  Per axis 1 <= window <= dim and 1 <= stride, stride <= window unless window == dim, as captum requires. */
+
+/* K26 out[r - first][c][p] = x[b][c][p] * (1 - m) + baseline[c][p] * m,  m = (ids[c][p] == id_min + j) as 0.f / 1.f
+ *     (captum's float expression, no select: -0 + 0 = +0, inf * 0 = NaN as there)
+ * replaces  FeatureAblation._construct_ablated_input behind evaluatePerturbation.py:171-173, all n rows in one launch instead of
+ *           one altered image per classifier call
+ *   x : [B][C][H][W];  ids : int32 [H][W] (ids_C = 1) or [C][H][W] (ids_C = C);  baseline : [C][H][W] or NULL -> baseline_scalar;
+ *   out : [n][C][H][W];  0 <= first, first + n <= B * n_total;  an id outside [id_min, id_min + n_total) is never ablated */
+int xai_ablate_features_f32(const float* x, const int32_t* ids, int ids_C, int id_min, int n_total, const float* baseline,
+                            float baseline_scalar, int B, int C, int H, int W, int64_t first, int n, float* out,
+                            xai_stream_t stream);
+
+/* K26, occlusion mode: the same expression with m = (pixel inside window j)
+ * replaces  Occlusion._construct_ablated_input / _occlusion_mask behind evaluatePerturbation.py:174-176 */
+int xai_ablate_windows_f32(const float* x, int win_h, int win_w, int stride_h, int stride_w, const float* baseline,
+                           float baseline_scalar, int B, int C, int H, int W, int64_t first, int n, float* out,
+                           xai_stream_t stream);
+
+/* K27 attr[b][c][p] = +0 + (s0[b] - scores[b][ids[c][p] - id_min])   (captum's attr += (s0 - s_j) * m over ascending j, from +0)
+ *     samples[b][c][i][j] = attr[b][c][floor((i + 0.5) * H / g)][floor((j + 0.5) * W / g)]   (nearest-exact, fp32 index
+ *     arithmetic as F.interpolate; computed from the scores, attr need not be written)
+ * replaces  the accumulation of FeatureAblation.attribute behind evaluatePerturbation.py:171-173 and `downsize`, :95
+ *   s0 : [B];  scores : [B][n_total];  attr : [B][C][H][W] or NULL;  samples : [B][C][g][g] or NULL (one of the two required)
+ * Finite scores only: captum's d * m turns one NaN or infinite score into NaN at EVERY element of the image (NaN * 0); the
+ * gather confines it to the elements of that feature. */
+int xai_ablation_finish_features_f32(const float* s0, const float* scores, const int32_t* ids, int ids_C, int id_min, int n_total,
+                                     int B, int C, int H, int W, int g, float* attr, float* samples, xai_stream_t stream);
+
+/* K27, occlusion mode: attr[b][c][p] = (sum over the windows k covering p, ascending k, from +0, of s0[b] - scores[b][k]) / their
+ *     count as fp32 (captum's attr / weights; at most ceil(window / stride)^2 windows cover an element); samples as above
+ * replaces  the accumulation and the division of Occlusion.attribute behind evaluatePerturbation.py:174-176 and `downsize`, :95
+ * Finite scores only, as above. */
+int xai_ablation_finish_windows_f32(const float* s0, const float* scores, int win_h, int win_w, int stride_h, int stride_w, int B,
+                                    int C, int H, int W, int g, float* attr, float* samples, xai_stream_t stream);
 
 /* ---- opt-in classifier-side fusion (xai_engine/prepare.py: fuse_bn_relu) --------------- */
 

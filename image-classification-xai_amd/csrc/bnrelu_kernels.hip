@@ -185,6 +185,184 @@ XAI_EXPORT int xai_bn_relu_bwd_f32(const float* gy, const float* gy2, const floa
   return xai_launch_status();
 }
 
+// ---- the same pair with a 1-bit ReLU gate in place of y in the backward ----------------------------------------------
+// The backward above loads y only to evaluate `y > 0`.  The forward form below also writes that bit per element (NaN -> 0)
+// into a caller-provided mask, and the backward form reads the mask instead of y: 1/32 of the bytes.
+//
+// Mask layout, by flat element index e of the [N][C][HW] tensor (private to this pair; xai_bn_gate_mask_bytes(n)):
+// 64-bit words, four per group of 256 consecutive elements;  the gate of e is
+//     bit (e % 256) / 4  of word  (e / 256) * 4 + e % 4.
+// A lane owns elements 4t .. 4t+3, so a wavefront owns exactly one group and word c of the group is the wave ballot of
+// component c; lanes 0..3 store the four words with ordinary vector stores.  Every word of the mask is written, the tail
+// group's bits of elements >= n as 0: nothing relies on a zero-fill.  When HW % 4 != 0 (layer4: HW = 49) the four
+// elements of a lane can straddle two channels and any n is allowed; they are then loaded one by one with the channel
+// taken per element -- same arithmetic per element, same layout.
+namespace {
+
+constexpr int kGateGroup = 256;                 // elements per mask group = 4 per lane * 64 lanes
+
+__device__ __forceinline__ void store_gate_words(uint64_t* __restrict__ mask, int64_t group, int lane, bool p0, bool p1, bool p2, bool p3) {
+  const uint64_t b0 = __ballot(p0), b1 = __ballot(p1), b2 = __ballot(p2), b3 = __ballot(p3);
+  if (lane < 4) mask[group * 4 + lane] = lane == 0 ? b0 : lane == 1 ? b1 : lane == 2 ? b2 : b3;
+}
+
+template <bool VEC, bool ADD>
+__global__ __launch_bounds__(kBlock) void bn_relu_fwd_mask_kernel(const float* __restrict__ x, const float* __restrict__ idt,
+                                                                  const float* __restrict__ w, const float* __restrict__ b,
+                                                                  const float* __restrict__ mean, const float* __restrict__ var,
+                                                                  float eps, BnParams bn2, int variant, int C, int HW, int64_t n,
+                                                                  float* __restrict__ y, uint64_t* __restrict__ mask) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t group = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  if (group * kGateGroup >= n) return;                  // wave-uniform: this wavefront owns no element and no mask word
+  const int64_t i = group * kGateGroup + lane * 4;
+  const bool second = ADD && bn2.w != nullptr;
+  float o[4] = {0.f, 0.f, 0.f, 0.f};                    // elements >= n keep +0: gate bit 0
+  if (VEC) {                                            // HW % 4 == 0, so n % 4 == 0: a lane is inside or outside as a whole
+    if (i < n) {
+      const int c = static_cast<int>((i / HW) % C);
+      const float m = mean[c], is = inv_std(var[c], eps, variant), wc = w[c], bc = b[c];
+      const float4 v = ld4_nt(x + i);
+      o[0] = bn_value(v.x, m, is, wc, bc, variant); o[1] = bn_value(v.y, m, is, wc, bc, variant);
+      o[2] = bn_value(v.z, m, is, wc, bc, variant); o[3] = bn_value(v.w, m, is, wc, bc, variant);
+      if (ADD) {
+        float4 a = ld4_nt(idt + i);
+        if (second) {
+          const float m2 = bn2.mean[c], is2 = inv_std(bn2.var[c], bn2.eps, variant), w2 = bn2.w[c], b2 = bn2.b[c];
+          a = make_float4(bn_value(a.x, m2, is2, w2, b2, variant), bn_value(a.y, m2, is2, w2, b2, variant),
+                          bn_value(a.z, m2, is2, w2, b2, variant), bn_value(a.w, m2, is2, w2, b2, variant));
+        }
+        o[0] += a.x; o[1] += a.y; o[2] += a.z; o[3] += a.w;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
+      st4(y + i, make_float4(o[0], o[1], o[2], o[3]));
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t e = i + k;
+      if (e < n) {
+        const int c = static_cast<int>((e / HW) % C);
+        float v = bn_value(x[e], mean[c], inv_std(var[c], eps, variant), w[c], b[c], variant);
+        if (ADD) v += second ? bn_value(idt[e], bn2.mean[c], inv_std(bn2.var[c], bn2.eps, variant), bn2.w[c], bn2.b[c], variant) : idt[e];
+        v = fmaxf(v, 0.f);
+        y[e] = v;
+        o[k] = v;
+      }
+    }
+  }
+  store_gate_words(mask, group, lane, o[0] > 0.f, o[1] > 0.f, o[2] > 0.f, o[3] > 0.f);
+}
+
+template <bool VEC, bool ADD>
+__global__ __launch_bounds__(kBlock) void bn_relu_bwd_mask_kernel(const float* __restrict__ gy, const float* __restrict__ gy2,
+                                                                  const uint64_t* __restrict__ mask, const float* __restrict__ w,
+                                                                  const float* __restrict__ var, float eps, BnParams bn2, int variant,
+                                                                  int C, int HW, int64_t n, float* __restrict__ gx,
+                                                                  float* __restrict__ gid) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t group = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  if (group * kGateGroup >= n) return;
+  const int64_t i = group * kGateGroup + lane * 4;
+  if (i >= n) return;
+  const uint64_t* mw = mask + group * 4;                // wave-uniform address: four words shared by the whole wavefront
+  const bool open[4] = {((mw[0] >> lane) & 1) != 0, ((mw[1] >> lane) & 1) != 0, ((mw[2] >> lane) & 1) != 0, ((mw[3] >> lane) & 1) != 0};
+  const bool second = ADD && bn2.w != nullptr;          // g_identity then goes through the identity operand's own BatchNorm
+  if (VEC) {
+    const int c = static_cast<int>((i / HW) % C);
+    const float is = inv_std(var[c], eps, variant), wc = w[c];
+    float is2 = 1.f, w2 = 1.f;
+    if (second) { is2 = inv_std(bn2.var[c], bn2.eps, variant); w2 = bn2.w[c]; }
+    float4 g = ld4_nt(gy + i);
+    if (gy2 != nullptr) {
+      const float4 h = ld4_nt(gy2 + i);
+      g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
+    }
+    const float4 g1 = make_float4(open[0] ? g.x : 0.f, open[1] ? g.y : 0.f, open[2] ? g.z : 0.f, open[3] ? g.w : 0.f);
+    st4(gx + i, make_float4(bn_grad(g1.x, is, wc, variant), bn_grad(g1.y, is, wc, variant), bn_grad(g1.z, is, wc, variant),
+                            bn_grad(g1.w, is, wc, variant)));
+    if (ADD)
+      st4(gid + i, second ? make_float4(bn_grad(g1.x, is2, w2, variant), bn_grad(g1.y, is2, w2, variant), bn_grad(g1.z, is2, w2, variant),
+                                        bn_grad(g1.w, is2, w2, variant))
+                          : g1);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t e = i + k;
+      if (e < n) {
+        const int c = static_cast<int>((e / HW) % C);
+        float g = gy[e];
+        if (gy2 != nullptr) g += gy2[e];
+        const float g1 = open[k] ? g : 0.f;
+        gx[e] = bn_grad(g1, inv_std(var[c], eps, variant), w[c], variant);
+        if (ADD) gid[e] = second ? bn_grad(g1, inv_std(bn2.var[c], bn2.eps, variant), bn2.w[c], variant) : g1;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+XAI_EXPORT size_t xai_bn_gate_mask_bytes(int64_t n) {
+  return n <= 0 ? 0 : static_cast<size_t>(xai_ceil_div(n, kGateGroup)) * 4 * sizeof(uint64_t);
+}
+
+XAI_EXPORT int xai_bn_relu_fwd_mask_f32(const float* x, const float* identity, const float* weight, const float* bias, const float* mean,
+                                        const float* var, float eps, const float* weight2, const float* bias2, const float* mean2,
+                                        const float* var2, float eps2, int variant, int N, int C, int HW, float* y, void* mask,
+                                        xai_stream_t stream) {
+  XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(weight); XAI_REQUIRE_PTR(bias); XAI_REQUIRE_PTR(mean); XAI_REQUIRE_PTR(var); XAI_REQUIRE_PTR(y);
+  XAI_REQUIRE_PTR(mask);
+  XAI_REQUIRE(N > 0 && C > 0 && HW > 0 && variant >= 0 && variant < 16, XAI_E_SHAPE);
+  XAI_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 7u) == 0, XAI_E_SHAPE);
+  if (weight2 != nullptr) {
+    XAI_REQUIRE_PTR(identity); XAI_REQUIRE_PTR(bias2); XAI_REQUIRE_PTR(mean2); XAI_REQUIRE_PTR(var2);
+  }
+  const BnParams bn2{weight2, bias2, mean2, var2, eps2};
+  const int64_t n = static_cast<int64_t>(N) * C * HW;
+  const bool vec = HW % 4 == 0 && xai_aligned16(x) && xai_aligned16(y) && (identity == nullptr || xai_aligned16(identity));
+  const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * 4));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uint64_t* mk = static_cast<uint64_t*>(mask);
+#define XAI_BN_FWDM(V, A) \
+  hipLaunchKernelGGL((bn_relu_fwd_mask_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, x, identity, weight, bias, mean, var, eps, bn2, variant, C, HW, n, y, mk)
+  if (identity != nullptr) {
+    if (vec) XAI_BN_FWDM(true, true); else XAI_BN_FWDM(false, true);
+  } else {
+    if (vec) XAI_BN_FWDM(true, false); else XAI_BN_FWDM(false, false);
+  }
+#undef XAI_BN_FWDM
+  return xai_launch_status();
+}
+
+XAI_EXPORT int xai_bn_relu_bwd_mask_f32(const float* gy, const float* gy2, const void* mask, const float* weight, const float* var,
+                                        float eps, const float* weight2, const float* var2, float eps2, int variant, int N, int C, int HW,
+                                        float* gx, float* g_identity, xai_stream_t stream) {
+  XAI_REQUIRE_PTR(gy); XAI_REQUIRE_PTR(mask); XAI_REQUIRE_PTR(weight); XAI_REQUIRE_PTR(var); XAI_REQUIRE_PTR(gx);
+  XAI_REQUIRE(N > 0 && C > 0 && HW > 0 && variant >= 0 && variant < 16, XAI_E_SHAPE);
+  XAI_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 7u) == 0, XAI_E_SHAPE);
+  const int64_t n = static_cast<int64_t>(N) * C * HW;
+  if (weight2 != nullptr) {
+    XAI_REQUIRE_PTR(g_identity); XAI_REQUIRE_PTR(var2);
+  }
+  const BnParams bn2{weight2, nullptr, nullptr, var2, eps2};
+  const bool vec = HW % 4 == 0 && xai_aligned16(gy) && xai_aligned16(gx) && (g_identity == nullptr || xai_aligned16(g_identity)) &&
+                   (gy2 == nullptr || xai_aligned16(gy2));
+  const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * 4));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint64_t* mk = static_cast<const uint64_t*>(mask);
+#define XAI_BN_BWDM(V, A) \
+  hipLaunchKernelGGL((bn_relu_bwd_mask_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, mk, weight, var, eps, bn2, variant, C, HW, n, gx, g_identity)
+  if (g_identity != nullptr) {
+    if (vec) XAI_BN_BWDM(true, true); else XAI_BN_BWDM(false, true);
+  } else {
+    if (vec) XAI_BN_BWDM(true, false); else XAI_BN_BWDM(false, false);
+  }
+#undef XAI_BN_BWDM
+  return xai_launch_status();
+}
+
 // ---- MaxPool2d backward (stem) ------------------------------------------------------------------------------------
 // gx[plane][h][w] = sum of gy[plane][ph][pw] over the pooling windows (ph, pw ascending) whose arg-max index (from
 // PyTorch's own forward, int64 = h * W + w) is this position -- the loop and the accumulation order of PyTorch's
@@ -435,5 +613,179 @@ XAI_EXPORT int xai_bn_relu_maxpool_fwd_f32(const float* x, const float* weight, 
     hipLaunchKernelGGL(bn_relu_maxpool_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, weight, bias, mean, var, eps, variant,
                        C, H, W, PH, PW, kernel, stride, pad, y);
   }
+  return xai_launch_status();
+}
+
+// ---- the stem with autograd: max_pool( relu( bn(x) ) ) forward and its whole backward, one kernel each -----------------
+// Forward: the tiled kernel above, which also writes one uint8 code per pooled output -- the position a * k + b of the
+// arg-max inside its k x k window (a, b counted from the window's padded origin) under PyTorch's rule (scan h then w
+// ascending, update on val > max || isnan(val)), or kStemClosed when the pooled value is <= 0, i.e. when PyTorch's
+// threshold_backward passes no gradient at the selected position.  A NaN goes through the ReLU as in PyTorch's clamp_min,
+// wins every window it is in and keeps its gate open.  The un-pooled activation is never stored.
+// Backward: per input position the gradients gy[q] (+ gy2[q]) of the windows q that selected it are added in (ph, pw)
+// ascending order from +0 -- the order of maxpool_bwd_tiled_kernel and of PyTorch's max_pool_backward_nchw -- and the sum
+// goes through (g * w) * invstd.  Gating per window is PyTorch's gate per position: every window that selects position p
+// has the pooled value y[p], so either all of p's contributions pass or none does, and a position that nothing selected
+// gets +0 both ways.
+namespace {
+
+constexpr int kStemClosed = 255;
+
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
+__global__ __launch_bounds__(256) void bn_relu_maxpool_code_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                   const float* __restrict__ b, const float* __restrict__ mean,
+                                                                   const float* __restrict__ var, float eps, int variant, int C, int H,
+                                                                   int W, int PH, int PW, int k, int stride, int pad,
+                                                                   float* __restrict__ y, uint8_t* __restrict__ code) {
+  extern __shared__ float tile[];                       // [rows][W + 2 * pad]
+  const int plane = blockIdx.y;
+  const int c = plane % C;
+  const float m = mean[c], is = inv_std(var[c], eps, variant), wc = w[c], bc = b[c];
+  const int ph0 = blockIdx.x * kPoolRows;
+  const int n_out = min(kPoolRows, PH - ph0);
+  const int rows = (n_out - 1) * stride + k;
+  const int h_first = ph0 * stride - pad;               // input row of tile row 0 (may be negative)
+  const int TWp = W + 2 * pad;
+  const float* src = x + static_cast<int64_t>(plane) * H * W;
+  for (int base = threadIdx.x; base < rows * TWp; base += 256 * 8) {
+    float v[8];
+    bool in[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = base + u * 256;
+      const int r = i / TWp, cx = i - r * TWp;
+      const int h = h_first + r, ww = cx - pad;
+      in[u] = i < rows * TWp && h >= 0 && h < H && ww >= 0 && ww < W;
+      v[u] = in[u] ? src[h * W + ww] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = base + u * 256;
+      if (i < rows * TWp) tile[i] = in[u] ? relu_keep_nan(bn_value(v[u], m, is, wc, bc, variant)) : -INFINITY;
+    }
+  }
+  __syncthreads();
+  for (int q = threadIdx.x; q < n_out * PW; q += 256) {
+    const int pr = q / PW, pw = q - pr * PW;
+    const float* t = tile + (pr * stride) * TWp + pw * stride;
+    float best = -INFINITY;
+    int arg = 0;
+    for (int a = 0; a < k; ++a)
+      for (int bb = 0; bb < k; ++bb) {
+        const float v = t[a * TWp + bb];
+        if (v > best || v != v) { best = v; arg = a * k + bb; }
+      }
+    const int64_t o = (static_cast<int64_t>(plane) * PH + ph0 + pr) * PW + pw;
+    y[o] = best;
+    code[o] = static_cast<uint8_t>(best <= 0.f ? kStemClosed : arg);
+  }
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ gy2,
+                                                                  const uint8_t* __restrict__ code, const float* __restrict__ w,
+                                                                  const float* __restrict__ var, float eps, int variant, int C, int H,
+                                                                  int W, int PH, int PW, int k, int stride, int pad,
+                                                                  float* __restrict__ gx) {
+  extern __shared__ int lds_i[];                         // [rows][PW] codes, then [rows][PW] gradients
+  const int c = blockIdx.y % C;
+  const float is = inv_std(var[c], eps, variant), wc = w[c];
+  const int h0 = blockIdx.x * kBwdRows;
+  const int h_last = min(h0 + kBwdRows, H) - 1;
+  const int pr0 = (h0 + pad < k) ? 0 : (h0 + pad - k) / stride + 1;           // first pooled row that can cover row h0
+  const int pr1 = min((h_last + pad) / stride + 1, PH);                         // one past the last that can cover h_last
+  const int rows = max(pr1 - pr0, 0);
+  float* lds_g = reinterpret_cast<float*>(lds_i + rows * PW);
+  const int64_t off = static_cast<int64_t>(blockIdx.y) * PH * PW + static_cast<int64_t>(pr0) * PW;
+  const int total = rows * PW;
+  for (int base = threadIdx.x; base < total; base += 256 * 8) {
+    int iv[8];
+    float gv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = base + u * 256;
+      iv[u] = i < total ? static_cast<int>(code[off + i]) : kStemClosed;
+      gv[u] = i < total ? gy[off + i] : 0.f;
+      if (gy2 != nullptr && i < total) gv[u] += gy2[off + i];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = base + u * 256;
+      if (i < total) { lds_i[i] = iv[u]; lds_g[i] = gv[u]; }
+    }
+  }
+  __syncthreads();
+  const int n_rows = h_last - h0 + 1;
+  for (int q = threadIdx.x; q < n_rows * W; q += 256) {
+    const int r = q / W, ww = q - r * W;
+    const int h = h0 + r;
+    const int ph0 = (h + pad < k) ? 0 : (h + pad - k) / stride + 1;
+    const int ph1 = min((h + pad) / stride + 1, PH);
+    const int pw0 = (ww + pad < k) ? 0 : (ww + pad - k) / stride + 1;
+    const int pw1 = min((ww + pad) / stride + 1, PW);
+    float g = 0.f;
+#pragma unroll
+    for (int a = 0; a < NW; ++a)
+#pragma unroll
+      for (int bb = 0; bb < NW; ++bb) {
+        const int ph = ph0 + a, pw = pw0 + bb;
+        if (ph < ph1 && pw < pw1) {
+          const int t = (ph - pr0) * PW + pw;
+          const int mine = (h + pad - ph * stride) * k + (ww + pad - pw * stride);   // this position inside window (ph, pw)
+          if (lds_i[t] == mine) g += lds_g[t];
+        }
+      }
+    gx[static_cast<int64_t>(blockIdx.y) * H * W + h * W + ww] = bn_grad(g, is, wc, variant);
+  }
+}
+
+// what both stem entry points accept: a plain square pool whose windows all hold an input element, codes that fit a byte
+// next to kStemClosed, consistent pooled extents (the kernels index by them), planes on grid.y
+static int stem_geometry_status(int N, int C, int H, int W, int PH, int PW, int kernel, int stride, int pad, int variant) {
+  XAI_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && PH > 0 && PW > 0 && kernel > 0 && stride > 0 && pad >= 0 && variant >= 0 && variant < 16,
+              XAI_E_SHAPE);
+  XAI_REQUIRE(2 * pad <= kernel && H + 2 * pad >= kernel && W + 2 * pad >= kernel, XAI_E_SHAPE);
+  XAI_REQUIRE(PH == (H + 2 * pad - kernel) / stride + 1 && PW == (W + 2 * pad - kernel) / stride + 1, XAI_E_SHAPE);
+  XAI_REQUIRE(static_cast<int64_t>(N) * C <= 65535 && static_cast<int64_t>(H) * W <= INT32_MAX && kernel * kernel <= kStemClosed &&
+                  (kernel + stride - 1) / stride <= 2,
+              XAI_E_UNSUPPORTED);
+  return XAI_OK;
+}
+
+}  // namespace
+
+XAI_EXPORT int xai_bn_relu_maxpool_fwd_code_f32(const float* x, const float* weight, const float* bias, const float* mean,
+                                                const float* var, float eps, int variant, int N, int C, int H, int W, int PH, int PW,
+                                                int kernel, int stride, int pad, float* y, uint8_t* code, xai_stream_t stream) {
+  XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(weight); XAI_REQUIRE_PTR(bias); XAI_REQUIRE_PTR(mean); XAI_REQUIRE_PTR(var); XAI_REQUIRE_PTR(y);
+  XAI_REQUIRE_PTR(code);
+  const int rc = stem_geometry_status(N, C, H, W, PH, PW, kernel, stride, pad, variant);
+  if (rc != XAI_OK) return rc;
+  const size_t lds = static_cast<size_t>((kPoolRows - 1) * stride + kernel) * (W + 2 * pad) * sizeof(float);
+  XAI_REQUIRE(lds <= 48 * 1024, XAI_E_UNSUPPORTED);
+  dim3 grid(static_cast<unsigned>(xai_ceil_div(PH, kPoolRows)), N * C);
+  hipLaunchKernelGGL(bn_relu_maxpool_code_kernel, grid, dim3(256), lds, static_cast<hipStream_t>(stream), x, weight, bias, mean, var, eps,
+                     variant, C, H, W, PH, PW, kernel, stride, pad, y, code);
+  return xai_launch_status();
+}
+
+XAI_EXPORT int xai_bn_relu_maxpool_bwd_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight, const float* var,
+                                           float eps, int variant, int N, int C, int H, int W, int PH, int PW, int kernel, int stride,
+                                           int pad, float* gx, xai_stream_t stream) {
+  XAI_REQUIRE_PTR(gy); XAI_REQUIRE_PTR(code); XAI_REQUIRE_PTR(weight); XAI_REQUIRE_PTR(var); XAI_REQUIRE_PTR(gx);
+  const int rc = stem_geometry_status(N, C, H, W, PH, PW, kernel, stride, pad, variant);
+  if (rc != XAI_OK) return rc;
+  const int pooled_rows = (kBwdRows + kernel - 2) / stride + 2;                   // upper bound of the pooled rows one tile needs
+  const size_t lds = static_cast<size_t>(pooled_rows) * PW * 8;
+  XAI_REQUIRE(lds <= 48 * 1024, XAI_E_UNSUPPORTED);
+  dim3 grid(static_cast<unsigned>(xai_ceil_div(H, kBwdRows)), N * C);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if ((kernel + stride - 1) / stride == 1)
+    hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<1>, grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
+                       kernel, stride, pad, gx);
+  else
+    hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<2>, grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
+                       kernel, stride, pad, gx);
   return xai_launch_status();
 }

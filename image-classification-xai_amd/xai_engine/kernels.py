@@ -445,6 +445,101 @@ def bn_relu_maxpool_fwd(x, weight, bias, mean, var, eps, variant, kernel, stride
     return y
 
 
+def bn_gate_mask_bytes(n):
+    """Bytes of the 1-bit ReLU gate mask of an n-element activation (xai_bn_gate_mask_bytes)."""
+    return int(_lib.load().xai_bn_gate_mask_bytes(int(n)))
+
+
+def bn_relu_fwd_mask(x, identity, weight, bias, mean, var, eps, variant, bn2=None, mask=None):
+    """-> (y, mask): y = relu(bn(x) [+ identity]) exactly as bn_act_fwd, plus the gate `y > 0` of every element as one bit in
+    `mask` (uint8 storage of bn_gate_mask_bytes(x.numel()) bytes, allocated here unless given; every word is written) for
+    bn_relu_bwd_mask.  The bit layout is private to the two kernels."""
+    _need(x, F32, "x")
+    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
+        _need(t, F32, name)
+    if identity is not None:
+        _need(identity, F32, "identity")
+        if identity.shape != x.shape:
+            raise ValueError("identity must have the shape of x")
+    w2 = b2 = m2 = v2 = None
+    eps2 = 0.0
+    if bn2 is not None:
+        w2, b2, m2, v2, eps2 = bn2
+        for name, t in (("weight2", w2), ("bias2", b2), ("mean2", m2), ("var2", v2)):
+            _need(t, F32, name)
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x[0, 0].numel()
+    need = bn_gate_mask_bytes(x.numel())
+    if mask is None:
+        mask = torch.empty(need, dtype=torch.uint8, device=x.device)
+    else:
+        _need(mask, torch.uint8, "mask")
+        if mask.numel() < need:
+            raise ValueError(f"mask has {mask.numel()} bytes, needs {need}")
+    y = torch.empty_like(x)
+    _call("xai_bn_relu_fwd_mask_f32", x.device, _ptr(x), _ptr(identity), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(var), float(eps),
+          _ptr(w2), _ptr(b2), _ptr(m2), _ptr(v2), float(eps2), int(variant), N, Cc, HW, _ptr(y), _ptr(mask))
+    return y, mask
+
+
+def bn_relu_bwd_mask(gy, mask, weight, var, eps, variant, want_identity=False, gy2=None, bn2=None):
+    """bn_relu_bwd with the gate mask of bn_relu_fwd_mask in place of y; gy (N,C,H,W) gives the shape."""
+    _need(gy, F32, "gy"); _need(mask, torch.uint8, "mask"); _need(weight, F32, "weight"); _need(var, F32, "var")
+    if gy.dim() < 3:
+        raise ValueError("gy must be (N, C, ...)")
+    if mask.numel() < bn_gate_mask_bytes(gy.numel()):
+        raise ValueError(f"mask has {mask.numel()} bytes, needs {bn_gate_mask_bytes(gy.numel())}")
+    if gy2 is not None:
+        _need(gy2, F32, "gy2")
+        if gy2.shape != gy.shape:
+            raise ValueError("gy2 must have the shape of gy")
+    w2 = v2 = None
+    eps2 = 0.0
+    if bn2 is not None:
+        w2, v2, eps2 = bn2
+        _need(w2, F32, "weight2"); _need(v2, F32, "var2")
+        want_identity = True
+    N, Cc = gy.shape[0], gy.shape[1]
+    HW = gy[0, 0].numel()
+    gx = torch.empty_like(gy)
+    gid = torch.empty_like(gy) if want_identity else None
+    _call("xai_bn_relu_bwd_mask_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(mask), _ptr(weight), _ptr(var), float(eps), _ptr(w2), _ptr(v2),
+          float(eps2), int(variant), N, Cc, HW, _ptr(gx), _ptr(gid))
+    return gx, gid
+
+
+def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, stride, pad):
+    """-> (y, code): max_pool2d(relu(bn(x)), kernel, stride, pad) and one uint8 per pooled output for bn_relu_maxpool_bwd (the
+    window-local arg-max, or 255 for a closed ReLU gate); x (N,C,H,W) -> (N,C,PH,PW) twice."""
+    _need(x, F32, "x")
+    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
+        _need(t, F32, name)
+    N, Cc, H, W = x.shape
+    PH = (H + 2 * pad - kernel) // stride + 1
+    PW = (W + 2 * pad - kernel) // stride + 1
+    y = torch.empty((N, Cc, PH, PW), dtype=F32, device=x.device)
+    code = torch.empty((N, Cc, PH, PW), dtype=torch.uint8, device=x.device)
+    _call("xai_bn_relu_maxpool_fwd_code_f32", x.device, _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(var), float(eps), int(variant),
+          N, Cc, H, W, PH, PW, int(kernel), int(stride), int(pad), _ptr(y), _ptr(code))
+    return y, code
+
+
+def bn_relu_maxpool_bwd(gy, code, weight, var, eps, variant, H, W, kernel, stride, pad, gy2=None):
+    """Input gradient (N,C,H,W) of the fused stem from the gradient(s) gy (+ gy2) of its pooled output and the forward's codes."""
+    _need(gy, F32, "gy"); _need(code, torch.uint8, "code"); _need(weight, F32, "weight"); _need(var, F32, "var")
+    if code.shape != gy.shape:
+        raise ValueError("code must have the shape of gy")
+    if gy2 is not None:
+        _need(gy2, F32, "gy2")
+        if gy2.shape != gy.shape:
+            raise ValueError("gy2 must have the shape of gy")
+    N, Cc, PH, PW = gy.shape
+    gx = torch.empty((N, Cc, int(H), int(W)), dtype=F32, device=gy.device)
+    _call("xai_bn_relu_maxpool_bwd_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(code), _ptr(weight), _ptr(var), float(eps), int(variant),
+          N, Cc, int(H), int(W), PH, PW, int(kernel), int(stride), int(pad), _ptr(gx))
+    return gx
+
+
 # ------------------------------------------------------------------------------ ViT explainers (K17-K21)
 def _image0(t, name, dim):
     """(B, *rest) or (*rest) float32 device tensor -> image 0 as a contiguous (*rest) tensor (a copy only if it is strided)"""

@@ -81,10 +81,15 @@ def _make_function():
         their gradients separately and sums them inside the kernel -- otherwise autograd adds them in a kernel of its own."""
 
         @staticmethod
-        def forward(ctx, x, identity, w, b, mean, var, eps, fork, bn2):
-            y = K.bn_act_fwd(x.contiguous(), None if identity is None else identity.contiguous(), w, b, mean, var, eps, BN_VARIANT, relu=True,
-                             bn2=bn2)
-            ctx.save_for_backward(y, w, var)
+        def forward(ctx, x, identity, w, b, mean, var, eps, fork, bn2, gated):
+            x, identity = x.contiguous(), None if identity is None else identity.contiguous()
+            if gated:
+                # a gradient will be taken: the forward also writes the ReLU gates, one bit per element, and the backward
+                # reads them instead of y (torch.empty inside: the mask lives in a capturing graph's pool like y does)
+                y, mask = K.bn_relu_fwd_mask(x, identity, w, b, mean, var, eps, BN_VARIANT, bn2=bn2)
+                ctx.save_for_backward(mask, w, var)
+            else:
+                y = K.bn_act_fwd(x, identity, w, b, mean, var, eps, BN_VARIANT, relu=True, bn2=bn2)
             ctx.eps, ctx.has_identity = eps, identity is not None
             ctx.bn2 = None if bn2 is None else (bn2[0], bn2[3], bn2[4])          # weight2, var2, eps2
             ctx.set_materialize_grads(False)
@@ -92,13 +97,13 @@ def _make_function():
 
         @staticmethod
         def backward(ctx, *grads):
-            y, w, var = ctx.saved_tensors
+            mask, w, var = ctx.saved_tensors
             live = [g.contiguous() for g in grads if g is not None]
             if not live:
-                return (None,) * 9
-            gx, gid = K.bn_relu_bwd(live[0], y, w, var, ctx.eps, BN_VARIANT, want_identity=ctx.has_identity,
-                                    gy2=live[1] if len(live) > 1 else None, bn2=ctx.bn2)
-            return gx, gid, None, None, None, None, None, None, None
+                return (None,) * 10
+            gx, gid = K.bn_relu_bwd_mask(live[0], mask, w, var, ctx.eps, BN_VARIANT, want_identity=ctx.has_identity,
+                                         gy2=live[1] if len(live) > 1 else None, bn2=ctx.bn2)
+            return gx, gid, None, None, None, None, None, None, None, None
     return BnReluFunction
 
 
@@ -164,9 +169,11 @@ def bn_relu(x, bn, identity=None, fork=False, identity_bn=None):
 
     def fused_fn(xx, ii, forked=None):
         forked = (fork and torch.is_grad_enabled() and xx.requires_grad) if forked is None else forked
+        # forward-only calls (grad mode off, or nothing upstream wants a gradient) write no gate mask
+        gated = torch.is_grad_enabled() and (xx.requires_grad or (ii is not None and ii.requires_grad))
         if not forked:
-            return _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), False, bn2)
-        y, alias = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), True, bn2)
+            return _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), False, bn2, gated)
+        y, alias = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), True, bn2, gated)
         y._xai_alias = alias
         return y
     if _CHECK["on"]:
@@ -265,12 +272,90 @@ def stem_inference(x, bn, pool):
     return y
 
 
+_STEM_FN = None
+
+
+def stem_autograd(x, bn, pool, fork=False):
+    """max_pool(relu(bn(x))) with autograd as one kernel per direction (the un-pooled activation is never stored; the backward
+    is max-pool backward + ReLU gate + BatchNorm gradient in one pass); None when no gradient is needed or the geometry is not
+    covered -- the caller then takes bn_relu + max_pool.  fork: the pooled tensor carries a second handle as `._xai_alias`
+    (see bn_relu), so that the first block's convolution and its down-sample branch deliver their gradients separately and
+    the backward kernel sums them."""
+    global _STEM_FN
+    import torch
+    import torch.nn as nn
+    from . import kernels as K
+
+    def one(v):
+        return v if isinstance(v, int) else (v[0] if v[0] == v[1] else None)
+    needs_grad = torch.is_grad_enabled() and x.requires_grad
+    if not (needs_grad or _CHECK["on"]) or not (isinstance(pool, nn.MaxPool2d) and _bn_usable(bn, x)):
+        return None
+    k, s, p, d = one(pool.kernel_size), one(pool.stride), one(pool.padding), one(pool.dilation)
+    if None in (k, s, p) or d != 1 or pool.ceil_mode or pool.return_indices or x.shape[0] * x.shape[1] > 65535 or 2 * p > k:
+        return None
+    H, W = x.shape[2], x.shape[3]
+    if k > 15 or -(-k // s) > 2 or H + 2 * p < k or W + 2 * p < k:
+        return None
+    PW = (W + 2 * p - k) // s + 1
+    if (7 * s + k) * (W + 2 * p) * 4 > 48 * 1024 or ((14 + k) // s + 2) * PW * 8 > 48 * 1024:      # the two kernels' LDS tiles
+        return None
+    if _STEM_FN is None:
+        class StemFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, inp, w, b, mean, var, eps, kk, ss, pp, forked):
+                y, code = K.bn_relu_maxpool_fwd_code(inp.contiguous(), w, b, mean, var, eps, BN_VARIANT, kk, ss, pp)
+                ctx.save_for_backward(code, w, var)
+                ctx.geom = (eps, inp.shape[2], inp.shape[3], kk, ss, pp)
+                ctx.set_materialize_grads(False)
+                return (y, y.detach()) if forked else y
+
+            @staticmethod
+            def backward(ctx, *grads):
+                code, w, var = ctx.saved_tensors
+                live = [g.contiguous() for g in grads if g is not None]
+                if not live:
+                    return (None,) * 10
+                eps, H_, W_, kk, ss, pp = ctx.geom
+                gx = K.bn_relu_maxpool_bwd(live[0], code, w, var, eps, BN_VARIANT, H_, W_, kk, ss, pp, gy2=live[1] if len(live) > 1 else None)
+                return (gx,) + (None,) * 9
+        _STEM_FN = StemFunction
+    w, b, mean, var = _bn_tensors(bn, x)
+
+    def fused_fn(xx, forked):
+        if not forked:
+            return _STEM_FN.apply(xx, w, b, mean, var, float(bn.eps), k, s, p, False)
+        y, alias = _STEM_FN.apply(xx, w, b, mean, var, float(bn.eps), k, s, p, True)
+        y._xai_alias = alias
+        return y
+    if _CHECK["on"]:
+        xa, xb = x.detach().clone().requires_grad_(True), x.detach().clone().requires_grad_(True)
+        with torch.enable_grad():
+            ya, yb = pool(_eager(xa, bn, None)), fused_fn(xb, fork)
+            g1, g2 = torch.randn_like(ya), torch.randn_like(ya)
+            if fork:                                  # the pooled tensor is used twice: autograd adds the two gradients, the kernel sums them
+                (ga,), (gb,) = torch.autograd.grad([ya, ya], xa, [g1, g2]), torch.autograd.grad([yb, yb._xai_alias], xb, [g1, g2])
+            else:
+                (ga,), (gb,) = torch.autograd.grad(ya, xa, g1), torch.autograd.grad(yb, xb, g1)
+        if not (torch.equal(ya, yb) and torch.equal(ga, gb)):
+            raise ValueError(f"fuse_bn_relu: the fused stem differs from the PyTorch kernels for input {tuple(x.shape)} "
+                             f"(forward equal: {torch.equal(ya, yb)})")
+        _CHECK["sites"] += 1
+    if not needs_grad:
+        return None
+    return fused_fn(x, fork)
+
+
 def _fused_resnet_forward(self, x):
     import torch
     stem = self.conv1(x)
     pooled = stem_inference(stem, self.bn1, self.maxpool)
-    if pooled is None or _CHECK["on"]:                    # (a verification pass walks both forms of the stem)
-        pooled = max_pool(bn_relu(stem, self.bn1), self.maxpool)
+    if pooled is None or _CHECK["on"]:                    # (a verification pass walks every form of the stem)
+        fused = stem_autograd(stem, self.bn1, self.maxpool, getattr(self, "_xai_fork", False))
+        if fused is None or _CHECK["on"]:
+            pooled = max_pool(bn_relu(stem, self.bn1), self.maxpool)
+        if fused is not None:
+            pooled = fused
     x = pooled
     x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
     return self.fc(torch.flatten(self.avgpool(x), 1))
@@ -295,7 +380,10 @@ def fuse_bn_relu(model, verify=None, fork_residual=False):
     and the fused backward kernel sums their gradients itself.  Values are unchanged, but the gradient with respect to an
     inner block's output is then split over the two handles: code that takes `autograd.grad(score, hooked_activation)` on
     such an output must add the gradient of `hooked_activation._xai_alias` (xai_engine.gradcam.LayerGradCam does); the
-    output of the last block, which no fused block consumes, is not affected.  Off by default for that reason."""
+    output of the last block, which no fused block consumes, is not affected.  Off by default for that reason.
+    When a gradient is taken, the fused sites save a 1-bit ReLU gate per element instead of their output, and the stem
+    (bn1 + relu + maxpool) runs as one kernel per direction (`stem_autograd`); with `fork_residual=True` the pooled tensor is
+    forked like a block output, so the same holds for a gradient taken with respect to the first layer's input."""
     import types
     import torch
     import torch.nn as nn
@@ -309,6 +397,7 @@ def fuse_bn_relu(model, verify=None, fork_residual=False):
     stem = all(hasattr(m, n) for n in ("conv1", "bn1", "relu", "maxpool", "layer1", "layer2", "layer3", "layer4", "avgpool", "fc"))
     if stem and isinstance(m.bn1, nn.BatchNorm2d):
         m.forward = types.MethodType(_fused_resnet_forward, m)
+        m._xai_fork = bool(fork_residual)
     if n_blocks == 0:
         raise ValueError("fuse_bn_relu: no ResNet-style blocks (conv1/bn1/conv2/bn2/relu/downsample) found in the model")
     for p in m.parameters():

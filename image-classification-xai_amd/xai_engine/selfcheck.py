@@ -120,6 +120,17 @@ def run(device="cuda:0", verbose=True):
     check("maxpool_bwd (bitwise vs PyTorch)", float((K.maxpool_bwd(gp, ip, 15, 17, 3, 2, 1) != xp.grad).sum()), 0.0)
     want = F.max_pool2d(F.relu(F.batch_norm(xb_, mv, vv, wv, bv, False, 0.0, 1e-5)), 3, 2, 1)
     check("bn_relu_maxpool_fwd (bitwise vs PyTorch)", float((K.bn_relu_maxpool_fwd(xb_, wv, bv, mv, vv, 1e-5, BN_VARIANT, 3, 2, 1) != want).sum()), 0.0)
+    ym, gate = K.bn_relu_fwd_mask(xb_, idt_, wv, bv, mv, vv, 1e-5, BN_VARIANT)
+    gxm, gidm = K.bn_relu_bwd_mask(gy_, gate, wv, vv, 1e-5, BN_VARIANT, want_identity=True)
+    check("bn_relu_fwd_mask / bn_relu_bwd_mask (bitwise vs PyTorch)",
+          float((ym != yv.detach()).sum() + (gxm != xr.grad).sum() + (gidm != ir.grad).sum()), 0.0)
+    xs = xb_.clone().requires_grad_(True)
+    ys = F.max_pool2d(F.relu(F.batch_norm(xs, mv, vv, wv, bv, False, 0.0, 1e-5)), 3, 2, 1)
+    gs1, gs2 = rnd(*ys.shape), rnd(*ys.shape)
+    (gxs,) = torch.autograd.grad([ys, ys], xs, [gs1, gs2])
+    yc, code = K.bn_relu_maxpool_fwd_code(xb_, wv, bv, mv, vv, 1e-5, BN_VARIANT, 3, 2, 1)
+    gxc = K.bn_relu_maxpool_bwd(gs1, code, wv, vv, 1e-5, BN_VARIANT, 14, 14, 3, 2, 1, gy2=gs2)
+    check("bn_relu_maxpool_fwd_code / bn_relu_maxpool_bwd (bitwise vs PyTorch)", float((yc != ys.detach()).sum() + (gxc != gxs).sum()), 0.0)
     # K16 and the stream workers
     rows, wts = rnd(37, 200).abs(), rnd(37)
     wsum, psum = K.masked_sums(rows, wts)

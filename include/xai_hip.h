@@ -41,9 +41,11 @@ typedef void* xai_stream_t; /* hipStream_t */
  *         xai_residual_shares_f32, xai_attn_cam_f32;
  *   5 = + xai_gig_init_f32, xai_gig_step_f32;
  *   6 = + xai_agi_init_f32, xai_agi_step_f32, xai_agi_heatmap_f32;
- *   7 = + xai_ablate_features_f32, xai_ablate_windows_f32, xai_ablation_finish_features_f32, xai_ablation_finish_windows_f32 */
+ *   7 = + xai_ablate_features_f32, xai_ablate_windows_f32, xai_ablation_finish_features_f32, xai_ablation_finish_windows_f32;
+ *   8 = + xai_bn_gate_mask_bytes, xai_bn_relu_fwd_mask_f32, xai_bn_relu_bwd_mask_f32, xai_bn_relu_maxpool_fwd_code_f32,
+ *         xai_bn_relu_maxpool_bwd_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 7
+#define XAI_ABI_MINOR 8
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -429,6 +431,48 @@ int xai_maxpool_bwd_f32(const float* gy, const int64_t* indices, int planes, int
 int xai_bn_relu_maxpool_fwd_f32(const float* x, const float* weight, const float* bias, const float* mean,
                                 const float* var, float eps, int variant, int N, int C, int H, int W, int PH,
                                 int PW, int kernel, int stride, int pad, float* y, xai_stream_t stream);
+
+/* ---- the same fusion when a gradient will be taken: 1-bit ReLU gates, and the stem as one kernel per direction ---- */
+
+/* bytes of the gate mask of an n-element activation: one bit per element, in 64-bit words, four per group of 256
+ * consecutive elements (flat index e: bit (e % 256) / 4 of word (e / 256) * 4 + e % 4; a partial last group is a whole
+ * group).  The layout is private to the two entry points below, which serve the autograd.grad of saliencyMethods.py:213. */
+size_t xai_bn_gate_mask_bytes(int64_t n);
+
+/* xai_bn_act_fwd_f32 with relu != 0 that also writes the gate `y > 0` (NaN -> 0) of every element into `mask`
+ * (xai_bn_gate_mask_bytes(N*C*HW) bytes, 8-byte aligned; every word is written, nothing needs a zero-fill), for the
+ * backward pass of saliencyMethods.py:213 through the classifiers of evaluatePerturbation.py:627-640.  Same y, bit for bit. */
+int xai_bn_relu_fwd_mask_f32(const float* x, const float* identity, const float* weight, const float* bias,
+                             const float* mean, const float* var, float eps, const float* weight2,
+                             const float* bias2, const float* mean2, const float* var2, float eps2, int variant,
+                             int N, int C, int HW, float* y, void* mask, xai_stream_t stream);
+
+/* xai_bn_relu_bwd_f32 with the gate mask written by xai_bn_relu_fwd_mask_f32 in place of y (1/32 of its bytes): same gx and
+ * g_identity, bit for bit; reached through the autograd.grad of saliencyMethods.py:213 (getGradientsParallel) */
+int xai_bn_relu_bwd_mask_f32(const float* gy, const float* gy2, const void* mask, const float* weight,
+                             const float* var, float eps, const float* weight2, const float* var2, float eps2,
+                             int variant, int N, int C, int HW, float* gx, float* g_identity, xai_stream_t stream);
+
+/* the stem with autograd, forward: y = max_pool2d( relu( bn(x) ), kernel, stride, pad ) as xai_bn_relu_maxpool_fwd_f32, plus
+ * one byte per pooled output for the backward: the arg-max position a * kernel + b inside its window (PyTorch's rule: h
+ * then w ascending, update on val > max || isnan(val)), or 255 when the pooled value is <= 0 (ReLU gate closed; a NaN
+ * passes the ReLU and keeps its gate open, as in PyTorch).  Classifiers of evaluatePerturbation.py:627-640 under the
+ * gradient passes of saliencyMethods.py:213.   x : [N][C][H*W];  y, code : [N][C][PH*PW]
+ * Accepted: 2*pad <= kernel, kernel <= 15, ceil(kernel/stride) <= 2, N*C <= 65535, PH / PW the pooled extents of H / W,
+ * a tile of 7*stride+kernel padded rows within 48 KiB of LDS; anything else XAI_E_SHAPE / XAI_E_UNSUPPORTED */
+int xai_bn_relu_maxpool_fwd_code_f32(const float* x, const float* weight, const float* bias, const float* mean,
+                                     const float* var, float eps, int variant, int N, int C, int H, int W, int PH,
+                                     int PW, int kernel, int stride, int pad, float* y, uint8_t* code,
+                                     xai_stream_t stream);
+
+/* the stem with autograd, backward, one kernel for max_pool_backward + threshold_backward + the BatchNorm gradient:
+ * gx[p] = ( (sum over the windows q whose code selects p, (ph, pw) ascending, from +0, of gy[q] [+ gy2[q]]) * weight ) * invstd;
+ * a window with code 255 contributes nothing.  gy2 (nullable): the second gradient of the pooled tensor (it feeds the first
+ * block's convolution AND its down-sample branch).  Reached through the autograd.grad of saliencyMethods.py:213.
+ * Same geometry as the forward.   gy, gy2, code : [N][C][PH*PW];  gx : [N][C][H*W] */
+int xai_bn_relu_maxpool_bwd_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight,
+                                const float* var, float eps, int variant, int N, int C, int H, int W, int PH,
+                                int PW, int kernel, int stride, int pad, float* gx, xai_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -152,7 +152,37 @@ def main():
     rep("bn_relu_bwd", 3 * nb, ms)
     ms = timeit(lambda: K.bn_relu_bwd(gy, yv, wv, vv, 1e-5, BN_VARIANT, want_identity=True))
     rep("bn_relu_bwd + g_identity", 4 * nb, ms)
-    del act, idt, gy, yv
+    # the gradient-pass forms: the forward also writes 1 gate bit per element, the backward reads those bits instead of y
+    ym, gate = K.bn_relu_fwd_mask(act, idt, wv, bv, mv, vv, 1e-5, BN_VARIANT)
+    ms = timeit(lambda: K.bn_relu_fwd_mask(act, None, wv, bv, mv, vv, 1e-5, BN_VARIANT, mask=gate))
+    rep("bn_relu_fwd_mask  relu(bn(x))", 2 * nb + nb // 32, ms)
+    ms = timeit(lambda: K.bn_relu_fwd_mask(act, idt, wv, bv, mv, vv, 1e-5, BN_VARIANT, mask=gate))
+    rep("bn_relu_fwd_mask  relu(bn(x)+id)", 3 * nb + nb // 32, ms)
+    ms = timeit(lambda: K.bn_relu_bwd_mask(gy, gate, wv, vv, 1e-5, BN_VARIANT))
+    rep("bn_relu_bwd_mask", 2 * nb + nb // 32, ms)
+    ms = timeit(lambda: K.bn_relu_bwd_mask(gy, gate, wv, vv, 1e-5, BN_VARIANT, want_identity=True))
+    rep("bn_relu_bwd_mask + g_identity", 3 * nb + nb // 32, ms)
+    del act, idt, gy, yv, ym, gate
+    # the stem of one benchmark pass (50 x 64 x 112 x 112 -> 56 x 56) with autograd, and the five-kernel chain it replaces
+    sx = torch.randn(50, 64, 112, 112, device=DEV)
+    sw, sb, sm, sv = (torch.rand(64, device=DEV) + 0.5 for _ in range(4))
+    sn = sx.numel() * 4
+    ms = timeit(lambda: K.bn_relu_maxpool_fwd_code(sx, sw, sb, sm, sv, 1e-5, BN_VARIANT, 3, 2, 1))
+    rep("bn_relu_maxpool_fwd_code 3/2/1", sn + sn // 4 + sn // 16, ms)
+    sy, scode = K.bn_relu_maxpool_fwd_code(sx, sw, sb, sm, sv, 1e-5, BN_VARIANT, 3, 2, 1)
+    sg1, sg2 = torch.randn_like(sy), torch.randn_like(sy)
+    ms = timeit(lambda: K.bn_relu_maxpool_bwd(sg1, scode, sw, sv, 1e-5, BN_VARIANT, 112, 112, 3, 2, 1, gy2=sg2))
+    rep("bn_relu_maxpool_bwd (2 grads)", 2 * (sn // 4) + sn // 16 + sn, ms)
+
+    def stem_chain_fwd():
+        return torch.nn.functional.max_pool2d(K.bn_act_fwd(sx, None, sw, sb, sm, sv, 1e-5, BN_VARIANT), 3, 2, 1, 1, False, True)
+    ms = timeit(stem_chain_fwd)
+    rep("stem chain fwd (bn_act_fwd, torch max_pool)", 2 * sn + sn + sn // 4 + sn // 2, ms, "two kernels, int64 indices")
+    sya = K.bn_act_fwd(sx, None, sw, sb, sm, sv, 1e-5, BN_VARIANT)
+    _, sidx = stem_chain_fwd()
+    ms = timeit(lambda: K.bn_relu_bwd(K.maxpool_bwd(sg1 + sg2, sidx, 112, 112, 3, 2, 1), sya, sw, sv, 1e-5, BN_VARIANT))
+    rep("stem chain bwd (add, maxpool_bwd, bn_relu_bwd)", 3 * (sn // 4) + sn // 4 + sn // 2 + sn + 3 * sn, ms, "three kernels")
+    del sx, sy, scode, sg1, sg2, sya, sidx
     # K9
     lg = torch.randn(50, 1000, device=DEV)
     ms = timeit(lambda: K.softmax_stats(lg, 3))

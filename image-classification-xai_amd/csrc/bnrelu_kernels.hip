@@ -255,7 +255,13 @@ __global__ __launch_bounds__(kBlock) void bn_relu_fwd_mask_kernel(const float* _
   store_gate_words(mask, group, lane, o[0] > 0.f, o[1] > 0.f, o[2] > 0.f, o[3] > 0.f);
 }
 
-template <bool VEC, bool ADD>
+// Guided Backprop's rule at a ReLU (captum 0.7.0 GuidedBackprop, evaluatePerturbation.py:154-158): the COMPLETE gradient of the
+// ReLU's output -- all consumers summed -- is clamped with relu() before the gate.  g <= 0 ? +0 : g keeps a NaN like F.relu and
+// hands exactly +0 on, the value a closed gate hands on.
+__device__ __forceinline__ float guided_clamp(float g) { return g <= 0.f ? 0.f : g; }
+
+// GUIDED: the clamp above on g = gy (+ gy2), then the gate; nothing else differs
+template <bool VEC, bool ADD, bool GUIDED>
 __global__ __launch_bounds__(kBlock) void bn_relu_bwd_mask_kernel(const float* __restrict__ gy, const float* __restrict__ gy2,
                                                                   const uint64_t* __restrict__ mask, const float* __restrict__ w,
                                                                   const float* __restrict__ var, float eps, BnParams bn2, int variant,
@@ -279,6 +285,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_bwd_mask_kernel(const float* _
       const float4 h = ld4_nt(gy2 + i);
       g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
     }
+    if (GUIDED) g = make_float4(guided_clamp(g.x), guided_clamp(g.y), guided_clamp(g.z), guided_clamp(g.w));
     const float4 g1 = make_float4(open[0] ? g.x : 0.f, open[1] ? g.y : 0.f, open[2] ? g.z : 0.f, open[3] ? g.w : 0.f);
     st4(gx + i, make_float4(bn_grad(g1.x, is, wc, variant), bn_grad(g1.y, is, wc, variant), bn_grad(g1.z, is, wc, variant),
                             bn_grad(g1.w, is, wc, variant)));
@@ -294,6 +301,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_bwd_mask_kernel(const float* _
         const int c = static_cast<int>((e / HW) % C);
         float g = gy[e];
         if (gy2 != nullptr) g += gy2[e];
+        if (GUIDED) g = guided_clamp(g);
         const float g1 = open[k] ? g : 0.f;
         gx[e] = bn_grad(g1, inv_std(var[c], eps, variant), w[c], variant);
         if (ADD) gid[e] = second ? bn_grad(g1, inv_std(bn2.var[c], bn2.eps, variant), bn2.w[c], variant) : g1;
@@ -336,9 +344,10 @@ XAI_EXPORT int xai_bn_relu_fwd_mask_f32(const float* x, const float* identity, c
   return xai_launch_status();
 }
 
-XAI_EXPORT int xai_bn_relu_bwd_mask_f32(const float* gy, const float* gy2, const void* mask, const float* weight, const float* var,
-                                        float eps, const float* weight2, const float* var2, float eps2, int variant, int N, int C, int HW,
-                                        float* gx, float* g_identity, xai_stream_t stream) {
+template <bool GUIDED>
+static int bn_relu_bwd_mask_launch(const float* gy, const float* gy2, const void* mask, const float* weight, const float* var, float eps,
+                                   const float* weight2, const float* var2, float eps2, int variant, int N, int C, int HW, float* gx,
+                                   float* g_identity, xai_stream_t stream) {
   XAI_REQUIRE_PTR(gy); XAI_REQUIRE_PTR(mask); XAI_REQUIRE_PTR(weight); XAI_REQUIRE_PTR(var); XAI_REQUIRE_PTR(gx);
   XAI_REQUIRE(N > 0 && C > 0 && HW > 0 && variant >= 0 && variant < 16, XAI_E_SHAPE);
   XAI_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 7u) == 0, XAI_E_SHAPE);
@@ -353,7 +362,7 @@ XAI_EXPORT int xai_bn_relu_bwd_mask_f32(const float* gy, const float* gy2, const
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint64_t* mk = static_cast<const uint64_t*>(mask);
 #define XAI_BN_BWDM(V, A) \
-  hipLaunchKernelGGL((bn_relu_bwd_mask_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, mk, weight, var, eps, bn2, variant, C, HW, n, gx, g_identity)
+  hipLaunchKernelGGL((bn_relu_bwd_mask_kernel<V, A, GUIDED>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, mk, weight, var, eps, bn2, variant, C, HW, n, gx, g_identity)
   if (g_identity != nullptr) {
     if (vec) XAI_BN_BWDM(true, true); else XAI_BN_BWDM(false, true);
   } else {
@@ -361,6 +370,18 @@ XAI_EXPORT int xai_bn_relu_bwd_mask_f32(const float* gy, const float* gy2, const
   }
 #undef XAI_BN_BWDM
   return xai_launch_status();
+}
+
+XAI_EXPORT int xai_bn_relu_bwd_mask_f32(const float* gy, const float* gy2, const void* mask, const float* weight, const float* var,
+                                        float eps, const float* weight2, const float* var2, float eps2, int variant, int N, int C, int HW,
+                                        float* gx, float* g_identity, xai_stream_t stream) {
+  return bn_relu_bwd_mask_launch<false>(gy, gy2, mask, weight, var, eps, weight2, var2, eps2, variant, N, C, HW, gx, g_identity, stream);
+}
+
+XAI_EXPORT int xai_bn_relu_bwd_mask_guided_f32(const float* gy, const float* gy2, const void* mask, const float* weight, const float* var,
+                                               float eps, const float* weight2, const float* var2, float eps2, int variant, int N, int C,
+                                               int HW, float* gx, float* g_identity, xai_stream_t stream) {
+  return bn_relu_bwd_mask_launch<true>(gy, gy2, mask, weight, var, eps, weight2, var2, eps2, variant, N, C, HW, gx, g_identity, stream);
 }
 
 // ---- MaxPool2d backward (stem) ------------------------------------------------------------------------------------
@@ -682,7 +703,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_code_kernel(const float* 
   }
 }
 
-template <int NW>
+// GUIDED: guided_clamp on the position's SUM over the windows that selected it (the complete gradient of the ReLU's output, as the
+// pool's backward scatters it), not per window: overlapping windows can bring gradients of both signs to one position.
+template <int NW, bool GUIDED>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ gy2,
                                                                   const uint8_t* __restrict__ code, const float* __restrict__ w,
                                                                   const float* __restrict__ var, float eps, int variant, int C, int H,
@@ -736,6 +759,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel(const float* _
           if (lds_i[t] == mine) g += lds_g[t];
         }
       }
+    if (GUIDED) g = guided_clamp(g);
     gx[static_cast<int64_t>(blockIdx.y) * H * W + h * W + ww] = bn_grad(g, is, wc, variant);
   }
 }
@@ -770,9 +794,10 @@ XAI_EXPORT int xai_bn_relu_maxpool_fwd_code_f32(const float* x, const float* wei
   return xai_launch_status();
 }
 
-XAI_EXPORT int xai_bn_relu_maxpool_bwd_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight, const float* var,
-                                           float eps, int variant, int N, int C, int H, int W, int PH, int PW, int kernel, int stride,
-                                           int pad, float* gx, xai_stream_t stream) {
+template <bool GUIDED>
+static int bn_relu_maxpool_bwd_launch(const float* gy, const float* gy2, const uint8_t* code, const float* weight, const float* var, float eps,
+                                      int variant, int N, int C, int H, int W, int PH, int PW, int kernel, int stride, int pad, float* gx,
+                                      xai_stream_t stream) {
   XAI_REQUIRE_PTR(gy); XAI_REQUIRE_PTR(code); XAI_REQUIRE_PTR(weight); XAI_REQUIRE_PTR(var); XAI_REQUIRE_PTR(gx);
   const int rc = stem_geometry_status(N, C, H, W, PH, PW, kernel, stride, pad, variant);
   if (rc != XAI_OK) return rc;
@@ -782,10 +807,22 @@ XAI_EXPORT int xai_bn_relu_maxpool_bwd_f32(const float* gy, const float* gy2, co
   dim3 grid(static_cast<unsigned>(xai_ceil_div(H, kBwdRows)), N * C);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if ((kernel + stride - 1) / stride == 1)
-    hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<1>, grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
+    hipLaunchKernelGGL((bn_relu_maxpool_bwd_kernel<1, GUIDED>), grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
                        kernel, stride, pad, gx);
   else
-    hipLaunchKernelGGL(bn_relu_maxpool_bwd_kernel<2>, grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
+    hipLaunchKernelGGL((bn_relu_maxpool_bwd_kernel<2, GUIDED>), grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
                        kernel, stride, pad, gx);
   return xai_launch_status();
+}
+
+XAI_EXPORT int xai_bn_relu_maxpool_bwd_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight, const float* var,
+                                           float eps, int variant, int N, int C, int H, int W, int PH, int PW, int kernel, int stride,
+                                           int pad, float* gx, xai_stream_t stream) {
+  return bn_relu_maxpool_bwd_launch<false>(gy, gy2, code, weight, var, eps, variant, N, C, H, W, PH, PW, kernel, stride, pad, gx, stream);
+}
+
+XAI_EXPORT int xai_bn_relu_maxpool_bwd_guided_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight,
+                                                  const float* var, float eps, int variant, int N, int C, int H, int W, int PH, int PW,
+                                                  int kernel, int stride, int pad, float* gx, xai_stream_t stream) {
+  return bn_relu_maxpool_bwd_launch<true>(gy, gy2, code, weight, var, eps, variant, N, C, H, W, PH, PW, kernel, stride, pad, gx, stream);
 }

@@ -152,3 +152,82 @@ XAI_EXPORT int xai_bilinear_up_f32(const float* src, int B, int h, int w, int H,
   hipLaunchKernelGGL(bilinear_up_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), src, h, w, H, W, scale, take_abs, dst);
   return xai_launch_status();
 }
+
+// ---- K28: Guided Backprop / Guided Grad-CAM map ------------------------------------------------------------------------
+// attr[b][c][y][x] = grad[b][c][y][x] * cam[b][sy][sx] (captum's GuidedGradCam: guided gradient times the layer's Grad-CAM,
+// F.interpolate(..., mode="nearest") to the input size; without a cam the factor is absent) and the harness's
+// map[b][y][x] = |((a_0 + a_1) + a_2 + ...)| over the channels, the order of NumPy's sum over the leading axis.
+// sy, sx: PyTorch's legacy `nearest` rule, min(int(floorf(dst * scale)), in - 1) with scale = (float)in / out.
+// A lane owns PX consecutive pixels of one row for all channels: one pass over grad, coalesced per channel; the (at most
+// 32 x 32) cam is a few cache lines per image and comes from L2.  Product and sums round separately (-ffp-contract=off).
+namespace {
+
+__device__ __forceinline__ int nearest_src(int dst, float scale, int in) { return min(static_cast<int>(floorf(dst * scale)), in - 1); }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void guided_map_kernel(const float* __restrict__ grad, const float* __restrict__ cam, int C, int H, int W,
+                                                         int h, int w, int64_t n_units, float* __restrict__ attr, float* __restrict__ map) {
+  constexpr int PX = VEC ? 4 : 1;
+  const int64_t u = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;     // unit = PX pixels of one row (VEC: W % 4 == 0)
+  if (u >= n_units) return;
+  const int wu = W / PX;
+  const int x0 = static_cast<int>(u % wu) * PX;
+  const int64_t row = u / wu;                                                  // b * H + y
+  const int y = static_cast<int>(row % H);
+  const int64_t b = row / H;
+  float f[4] = {1.f, 1.f, 1.f, 1.f}, a[4] = {0.f, 0.f, 0.f, 0.f}, acc[4] = {0.f, 0.f, 0.f, 0.f};      // PX of each are live
+  if (cam != nullptr) {
+    const float sh = static_cast<float>(h) / static_cast<float>(H), sw = static_cast<float>(w) / static_cast<float>(W);
+    const float* crow = cam + (b * h + nearest_src(y, sh, h)) * w;
+#pragma unroll
+    for (int k = 0; k < PX; ++k) f[k] = crow[nearest_src(x0 + k, sw, w)];
+  }
+  const int64_t hw = static_cast<int64_t>(H) * W;
+  const int64_t pix = static_cast<int64_t>(y) * W + x0;
+  for (int c = 0; c < C; ++c) {
+    const int64_t at = (b * C + c) * hw + pix;
+    if (VEC) {
+      const float4 g = ld4(grad + at);
+      a[0] = g.x; a[1] = g.y; a[2] = g.z; a[3] = g.w;
+    } else {
+      a[0] = grad[at];
+    }
+    if (cam != nullptr) {
+#pragma unroll
+      for (int k = 0; k < PX; ++k) a[k] = a[k] * f[k];
+    }
+    if (attr != nullptr) {
+      if (VEC) st4(attr + at, make_float4(a[0], a[1], a[2], a[3]));
+      else attr[at] = a[0];
+    }
+#pragma unroll
+    for (int k = 0; k < PX; ++k) acc[k] = c == 0 ? a[k] : acc[k] + a[k];
+  }
+  if (map != nullptr) {
+    const int64_t at = b * hw + pix;
+    if (VEC) st4(map + at, make_float4(fabsf(acc[0]), fabsf(acc[1]), fabsf(acc[2]), fabsf(acc[3])));
+    else map[at] = fabsf(acc[0]);
+  }
+}
+
+}  // namespace
+
+XAI_EXPORT int xai_guided_map_f32(const float* grad, const float* cam, int B, int C, int H, int W, int h, int w, float* attr, float* map,
+                                  xai_stream_t stream) {
+  XAI_REQUIRE_PTR(grad);
+  XAI_REQUIRE(attr != nullptr || map != nullptr, XAI_E_NULL);
+  XAI_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, XAI_E_SHAPE);
+  XAI_REQUIRE(cam == nullptr || (h > 0 && w > 0), XAI_E_SHAPE);
+  const bool vec = W % 4 == 0 && xai_aligned16(grad) && (attr == nullptr || xai_aligned16(attr)) && (map == nullptr || xai_aligned16(map));
+  const int64_t n_units = static_cast<int64_t>(B) * H * (W / (vec ? 4 : 1));
+  const int64_t blocks = xai_ceil_div(n_units, 256);
+  XAI_REQUIRE(blocks <= INT32_MAX, XAI_E_UNSUPPORTED);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL(guided_map_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, grad, cam, C, H, W, h, w, n_units, attr,
+                       map);
+  else
+    hipLaunchKernelGGL(guided_map_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, grad, cam, C, H, W, h, w, n_units, attr,
+                       map);
+  return xai_launch_status();
+}

@@ -482,8 +482,9 @@ def bn_relu_fwd_mask(x, identity, weight, bias, mean, var, eps, variant, bn2=Non
     return y, mask
 
 
-def bn_relu_bwd_mask(gy, mask, weight, var, eps, variant, want_identity=False, gy2=None, bn2=None):
-    """bn_relu_bwd with the gate mask of bn_relu_fwd_mask in place of y; gy (N,C,H,W) gives the shape."""
+def bn_relu_bwd_mask(gy, mask, weight, var, eps, variant, want_identity=False, gy2=None, bn2=None, guided=False):
+    """bn_relu_bwd with the gate mask of bn_relu_fwd_mask in place of y; gy (N,C,H,W) gives the shape.
+    guided: Guided Backprop's rule -- the summed gradient gy (+ gy2) goes through g <= 0 ? +0 : g before the gate."""
     _need(gy, F32, "gy"); _need(mask, torch.uint8, "mask"); _need(weight, F32, "weight"); _need(var, F32, "var")
     if gy.dim() < 3:
         raise ValueError("gy must be (N, C, ...)")
@@ -503,7 +504,7 @@ def bn_relu_bwd_mask(gy, mask, weight, var, eps, variant, want_identity=False, g
     HW = gy[0, 0].numel()
     gx = torch.empty_like(gy)
     gid = torch.empty_like(gy) if want_identity else None
-    _call("xai_bn_relu_bwd_mask_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(mask), _ptr(weight), _ptr(var), float(eps), _ptr(w2), _ptr(v2),
+    _call("xai_bn_relu_bwd_mask_guided_f32" if guided else "xai_bn_relu_bwd_mask_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(mask), _ptr(weight), _ptr(var), float(eps), _ptr(w2), _ptr(v2),
           float(eps2), int(variant), N, Cc, HW, _ptr(gx), _ptr(gid))
     return gx, gid
 
@@ -524,8 +525,9 @@ def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, s
     return y, code
 
 
-def bn_relu_maxpool_bwd(gy, code, weight, var, eps, variant, H, W, kernel, stride, pad, gy2=None):
-    """Input gradient (N,C,H,W) of the fused stem from the gradient(s) gy (+ gy2) of its pooled output and the forward's codes."""
+def bn_relu_maxpool_bwd(gy, code, weight, var, eps, variant, H, W, kernel, stride, pad, gy2=None, guided=False):
+    """Input gradient (N,C,H,W) of the fused stem from the gradient(s) gy (+ gy2) of its pooled output and the forward's codes.
+    guided: Guided Backprop's rule -- each position's sum over the windows that selected it goes through g <= 0 ? +0 : g."""
     _need(gy, F32, "gy"); _need(code, torch.uint8, "code"); _need(weight, F32, "weight"); _need(var, F32, "var")
     if code.shape != gy.shape:
         raise ValueError("code must have the shape of gy")
@@ -535,9 +537,40 @@ def bn_relu_maxpool_bwd(gy, code, weight, var, eps, variant, H, W, kernel, strid
             raise ValueError("gy2 must have the shape of gy")
     N, Cc, PH, PW = gy.shape
     gx = torch.empty((N, Cc, int(H), int(W)), dtype=F32, device=gy.device)
-    _call("xai_bn_relu_maxpool_bwd_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(code), _ptr(weight), _ptr(var), float(eps), int(variant),
+    _call("xai_bn_relu_maxpool_bwd_guided_f32" if guided else "xai_bn_relu_maxpool_bwd_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(code), _ptr(weight), _ptr(var), float(eps), int(variant),
           N, Cc, int(H), int(W), PH, PW, int(kernel), int(stride), int(pad), _ptr(gx))
     return gx
+
+
+# ------------------------------------------------------------------------------ Guided Backprop / Guided Grad-CAM (K28)
+def guided_map(grad, cam=None, want_attr=True, want_map=False, attr=None, map=None):
+    """K28: grad (B,C,H,W) [x cam (B,h,w), nearest-upsampled to (H,W)] -> attr (B,C,H,W) and/or the harness map (B,H,W) =
+    |sum over channels, left to right|.  -> attr, map, or (attr, map).  `attr` / `map`: preallocated outputs."""
+    _need(grad, F32, "grad")
+    if grad.dim() != 4:
+        raise ValueError("grad must be (B,C,H,W)")
+    B, Cc, H, W = grad.shape
+    h = w = 0
+    if cam is not None:
+        _need(cam, F32, "cam")
+        if cam.dim() != 3 or cam.shape[0] != B:
+            raise ValueError(f"cam must be ({B},h,w), got {tuple(cam.shape)}")
+        h, w = cam.shape[1], cam.shape[2]
+    if not (want_attr or want_map):
+        raise ValueError("nothing to compute: neither the attribution nor the map")
+    if want_attr:
+        attr = torch.empty_like(grad) if attr is None else _need(attr, F32, "attr")
+        if attr.numel() != grad.numel():
+            raise ValueError("attr has the wrong size")
+    if want_map:
+        map = torch.empty((B, H, W), dtype=F32, device=grad.device) if map is None else _need(map, F32, "map")
+        if map.numel() != B * H * W:
+            raise ValueError("map has the wrong size")
+    _call("xai_guided_map_f32", grad.device, _ptr(grad), _ptr(cam), B, Cc, H, W, int(h), int(w), _ptr(attr if want_attr else None),
+          _ptr(map if want_map else None))
+    if want_attr and want_map:
+        return attr, map
+    return attr if want_attr else map
 
 
 # ------------------------------------------------------------------------------ ViT explainers (K17-K21)

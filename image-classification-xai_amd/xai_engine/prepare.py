@@ -15,7 +15,9 @@ exact algebraic identity, but it changes fp32 rounding inside the classifier (~1
 logits), which for ReLU networks moves individual gates -- so it is opt-in and reported
 separately (bench.py --fold-bn 1); parity tests always run the classifier as given.
 """
+import contextlib
 import copy
+import threading
 
 
 
@@ -71,6 +73,53 @@ def _bn_tensors(bn, like):
     return w.detach().float().contiguous(), b.detach().float().contiguous(), bn.running_mean.float().contiguous(), bn.running_var.float().contiguous()
 
 
+# ------------------------------------------------------------------------------ guided mode (Guided Backprop)
+_GUIDED = threading.local()
+_GUIDED_RELU_FN = None
+
+
+@contextlib.contextmanager
+def guided_relu():
+    """While active on the calling thread, every ReLU of a `fuse_bn_relu` classifier built in a FORWARD pass backpropagates by
+    Guided Backprop's rule (captum 0.7.0 GuidedBackprop, the reference's evaluatePerturbation.py:154-158): the complete gradient
+    of the ReLU's output is clamped, g <= 0 ? +0 : g, before the gate.  The flag is read when the forward builds a site and kept
+    in that site's autograd context: the backward may run later, on autograd's device thread or inline inside a hipGraph capture,
+    where this thread-local is not visible.  Sites that fall back to the PyTorch modules get the same rule.  Outside the context
+    nothing changes."""
+    before = getattr(_GUIDED, "on", False)
+    _GUIDED.on = True
+    try:
+        yield
+    finally:
+        _GUIDED.on = before
+
+
+def guided_active():
+    return getattr(_GUIDED, "on", False)
+
+
+def _guided_relu_fn():
+    """relu(x) whose backward is Guided Backprop's, in torch ops (the sites the fused kernels do not cover)."""
+    global _GUIDED_RELU_FN
+    if _GUIDED_RELU_FN is None:
+        import torch
+
+        class GuidedReluFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x):
+                y = torch.relu(x)
+                ctx.save_for_backward(y)
+                return y
+
+            @staticmethod
+            def backward(ctx, g):
+                (y,) = ctx.saved_tensors
+                zero = torch.zeros((), dtype=g.dtype, device=g.device)
+                return torch.where(y > 0, torch.where(g <= 0, zero, g), zero)       # the kernels' expression: clamp, then the gate
+        _GUIDED_RELU_FN = GuidedReluFunction
+    return _GUIDED_RELU_FN
+
+
 def _make_function():
     import torch
     from . import kernels as K
@@ -81,7 +130,7 @@ def _make_function():
         their gradients separately and sums them inside the kernel -- otherwise autograd adds them in a kernel of its own."""
 
         @staticmethod
-        def forward(ctx, x, identity, w, b, mean, var, eps, fork, bn2, gated):
+        def forward(ctx, x, identity, w, b, mean, var, eps, fork, bn2, gated, guided):
             x, identity = x.contiguous(), None if identity is None else identity.contiguous()
             if gated:
                 # a gradient will be taken: the forward also writes the ReLU gates, one bit per element, and the backward
@@ -90,7 +139,7 @@ def _make_function():
                 ctx.save_for_backward(mask, w, var)
             else:
                 y = K.bn_act_fwd(x, identity, w, b, mean, var, eps, BN_VARIANT, relu=True, bn2=bn2)
-            ctx.eps, ctx.has_identity = eps, identity is not None
+            ctx.eps, ctx.has_identity, ctx.guided = eps, identity is not None, bool(guided)
             ctx.bn2 = None if bn2 is None else (bn2[0], bn2[3], bn2[4])          # weight2, var2, eps2
             ctx.set_materialize_grads(False)
             return (y, y.detach()) if fork else y
@@ -100,10 +149,10 @@ def _make_function():
             mask, w, var = ctx.saved_tensors
             live = [g.contiguous() for g in grads if g is not None]
             if not live:
-                return (None,) * 10
+                return (None,) * 11
             gx, gid = K.bn_relu_bwd_mask(live[0], mask, w, var, ctx.eps, BN_VARIANT, want_identity=ctx.has_identity,
-                                         gy2=live[1] if len(live) > 1 else None, bn2=ctx.bn2)
-            return gx, gid, None, None, None, None, None, None, None, None
+                                         gy2=live[1] if len(live) > 1 else None, bn2=ctx.bn2, guided=ctx.guided)
+            return (gx, gid) + (None,) * 9
     return BnReluFunction
 
 
@@ -116,6 +165,8 @@ def _eager(x, bn, identity, identity_bn=None):
     out = bn(x)
     if identity is not None:
         out = out + (identity if identity_bn is None else identity_bn(identity))
+    if guided_active() and out.requires_grad:
+        return _guided_relu_fn().apply(out)
     return F.relu(out)
 
 
@@ -171,9 +222,10 @@ def bn_relu(x, bn, identity=None, fork=False, identity_bn=None):
         forked = (fork and torch.is_grad_enabled() and xx.requires_grad) if forked is None else forked
         # forward-only calls (grad mode off, or nothing upstream wants a gradient) write no gate mask
         gated = torch.is_grad_enabled() and (xx.requires_grad or (ii is not None and ii.requires_grad))
+        guided = guided_active()                     # read here, in the forward: BnReluFunction keeps it for its backward
         if not forked:
-            return _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), False, bn2, gated)
-        y, alias = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), True, bn2, gated)
+            return _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), False, bn2, gated, guided)
+        y, alias = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), True, bn2, gated, guided)
         y._xai_alias = alias
         return y
     if _CHECK["on"]:
@@ -303,10 +355,10 @@ def stem_autograd(x, bn, pool, fork=False):
     if _STEM_FN is None:
         class StemFunction(torch.autograd.Function):
             @staticmethod
-            def forward(ctx, inp, w, b, mean, var, eps, kk, ss, pp, forked):
+            def forward(ctx, inp, w, b, mean, var, eps, kk, ss, pp, forked, guided):
                 y, code = K.bn_relu_maxpool_fwd_code(inp.contiguous(), w, b, mean, var, eps, BN_VARIANT, kk, ss, pp)
                 ctx.save_for_backward(code, w, var)
-                ctx.geom = (eps, inp.shape[2], inp.shape[3], kk, ss, pp)
+                ctx.geom, ctx.guided = (eps, inp.shape[2], inp.shape[3], kk, ss, pp), bool(guided)
                 ctx.set_materialize_grads(False)
                 return (y, y.detach()) if forked else y
 
@@ -315,17 +367,19 @@ def stem_autograd(x, bn, pool, fork=False):
                 code, w, var = ctx.saved_tensors
                 live = [g.contiguous() for g in grads if g is not None]
                 if not live:
-                    return (None,) * 10
+                    return (None,) * 11
                 eps, H_, W_, kk, ss, pp = ctx.geom
-                gx = K.bn_relu_maxpool_bwd(live[0], code, w, var, eps, BN_VARIANT, H_, W_, kk, ss, pp, gy2=live[1] if len(live) > 1 else None)
-                return (gx,) + (None,) * 9
+                gx = K.bn_relu_maxpool_bwd(live[0], code, w, var, eps, BN_VARIANT, H_, W_, kk, ss, pp, gy2=live[1] if len(live) > 1 else None,
+                                           guided=ctx.guided)
+                return (gx,) + (None,) * 10
         _STEM_FN = StemFunction
     w, b, mean, var = _bn_tensors(bn, x)
 
     def fused_fn(xx, forked):
+        guided = guided_active()                     # (as in bn_relu: the backward cannot see the caller's thread-local)
         if not forked:
-            return _STEM_FN.apply(xx, w, b, mean, var, float(bn.eps), k, s, p, False)
-        y, alias = _STEM_FN.apply(xx, w, b, mean, var, float(bn.eps), k, s, p, True)
+            return _STEM_FN.apply(xx, w, b, mean, var, float(bn.eps), k, s, p, False, guided)
+        y, alias = _STEM_FN.apply(xx, w, b, mean, var, float(bn.eps), k, s, p, True, guided)
         y._xai_alias = alias
         return y
     if _CHECK["on"]:
@@ -381,6 +435,8 @@ def fuse_bn_relu(model, verify=None, fork_residual=False):
     inner block's output is then split over the two handles: code that takes `autograd.grad(score, hooked_activation)` on
     such an output must add the gradient of `hooked_activation._xai_alias` (xai_engine.gradcam.LayerGradCam does); the
     output of the last block, which no fused block consumes, is not affected.  Off by default for that reason.
+    Inside `guided_relu()` the ReLUs of the copy backpropagate by Guided Backprop's rule (xai_engine/guided.py); the fused path
+    never calls the nn.ReLU modules, so in-place ReLUs are no obstacle there.
     When a gradient is taken, the fused sites save a 1-bit ReLU gate per element instead of their output, and the stem
     (bn1 + relu + maxpool) runs as one kernel per direction (`stem_autograd`); with `fork_residual=True` the pooled tensor is
     forked like a block output, so the same holds for a gradient taken with respect to the first layer's input."""

@@ -131,6 +131,24 @@ def run(device="cuda:0", verbose=True):
     yc, code = K.bn_relu_maxpool_fwd_code(xb_, wv, bv, mv, vv, 1e-5, BN_VARIANT, 3, 2, 1)
     gxc = K.bn_relu_maxpool_bwd(gs1, code, wv, vv, 1e-5, BN_VARIANT, 14, 14, 3, 2, 1, gy2=gs2)
     check("bn_relu_maxpool_fwd_code / bn_relu_maxpool_bwd (bitwise vs PyTorch)", float((yc != ys.detach()).sum() + (gxc != gxs).sum()), 0.0)
+    # guided forms (Guided Backprop): the clamp g <= 0 ? +0 : g on the complete gradient of the ReLU's output, then the same kernels
+    clamp = lambda t: torch.where(t <= 0, torch.zeros((), device=dev), t)      # noqa: E731
+    gy2_ = rnd(*gy_.shape)
+    gxg, gidg = K.bn_relu_bwd_mask(gy_, gate, wv, vv, 1e-5, BN_VARIANT, want_identity=True, gy2=gy2_, guided=True)
+    gxw, gidw = K.bn_relu_bwd_mask(clamp(gy_ + gy2_), gate, wv, vv, 1e-5, BN_VARIANT, want_identity=True)
+    check("bn_relu_bwd_mask guided (bitwise vs clamp + unguided)", float((gxg != gxw).sum() + (gidg != gidw).sum()), 0.0)
+    xs = xb_.clone().requires_grad_(True)
+    act_ = F.relu(F.batch_norm(xs, mv, vv, wv, bv, False, 0.0, 1e-5))
+    act_.register_hook(clamp)
+    (gxs,) = torch.autograd.grad([F.max_pool2d(act_, 3, 2, 1)] * 2, xs, [gs1, gs2])
+    gxc = K.bn_relu_maxpool_bwd(gs1, code, wv, vv, 1e-5, BN_VARIANT, 14, 14, 3, 2, 1, gy2=gs2, guided=True)
+    check("bn_relu_maxpool_bwd guided (bitwise vs PyTorch + hook)", float((gxc != gxs).sum()), 0.0)
+    # K28: Guided Grad-CAM's product with the nearest-upsampled cam, and the harness's |sum over channels|
+    for shp, hw_ in (((2, 3, 56, 56), (7, 7)), ((1, 3, 37, 53), (5, 4))):
+        gg, cm = rnd(*shp), rnd(shp[0], *hw_).relu()
+        at, mp = K.guided_map(gg, cm, want_attr=True, want_map=True)
+        want = gg * F.interpolate(cm[:, None], shp[2:], mode="nearest")
+        check(f"guided_map {shp[2]}x{shp[3]} (bitwise vs torch)", float((at != want).sum() + (mp != ((want[:, 0] + want[:, 1]) + want[:, 2]).abs()).sum()), 0.0)
     # K16 and the stream workers
     rows, wts = rnd(37, 200).abs(), rnd(37)
     wsum, psum = K.masked_sums(rows, wts)

@@ -31,7 +31,7 @@ from .smooth import smoothGrad
 from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "gc", "fa", "occ")
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "gc", "gbp", "ggc", "fa", "occ")
 TRANS_ATTR_FUNCS = ("agi",)          # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
@@ -100,6 +100,15 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
             sal = cache[key](x, target_class)[0]
         else:
             sal = gradcam_saliency(model, model.layer4, x, target_class, (img_hw, img_hw))[0]
+        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
+    elif attr_function in ("gbp", "ggc"):
+        # :154-163: captum's GuidedBackprop / GuidedGradCam(model, model.layer4) on models[1] (:84; the reference's copy without
+        # in-place ReLUs -- a fused classifier needs none), then |sum over channels| (:181) straight from K28
+        from .guided import guided_backprop_batch
+        models = testing_dict["models"]
+        guided_model = models[1] if len(models) > 1 else models[0]
+        sal = guided_backprop_batch(input_tensor.to(dev), guided_model, target_class,
+                                    layer=guided_model.layer4 if attr_function == "ggc" else None, want_attr=False, want_map=True)[0]
         return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     elif attr_function in ("fa", "occ"):
         # :171-176: captum's FeatureAblation over the 14 x 14 patch mask (:94-97) / Occlusion with window (3, 64, 64), stride 32;

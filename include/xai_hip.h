@@ -43,9 +43,10 @@ typedef void* xai_stream_t; /* hipStream_t */
  *   6 = + xai_agi_init_f32, xai_agi_step_f32, xai_agi_heatmap_f32;
  *   7 = + xai_ablate_features_f32, xai_ablate_windows_f32, xai_ablation_finish_features_f32, xai_ablation_finish_windows_f32;
  *   8 = + xai_bn_gate_mask_bytes, xai_bn_relu_fwd_mask_f32, xai_bn_relu_bwd_mask_f32, xai_bn_relu_maxpool_fwd_code_f32,
- *         xai_bn_relu_maxpool_bwd_f32 */
+ *         xai_bn_relu_maxpool_bwd_f32;
+ *   9 = + xai_bn_relu_bwd_mask_guided_f32, xai_bn_relu_maxpool_bwd_guided_f32, xai_guided_map_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 8
+#define XAI_ABI_MINOR 9
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -473,6 +474,34 @@ int xai_bn_relu_maxpool_fwd_code_f32(const float* x, const float* weight, const 
 int xai_bn_relu_maxpool_bwd_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight,
                                 const float* var, float eps, int variant, int N, int C, int H, int W, int PH,
                                 int PW, int kernel, int stride, int pad, float* gx, xai_stream_t stream);
+
+/* ---- Guided Backprop / Guided Grad-CAM (xai_engine/guided.py) ---------------------------- */
+
+/* xai_bn_relu_bwd_mask_f32 in guided mode: the backward of captum's GuidedBackprop(model).attribute(x, target) behind
+ * evaluatePerturbation.py:154-158 at a fused BN(+add)+ReLU site.  g = gy [+ gy2] (one fp32 add), g = g <= 0 ? +0 : g (relu of the
+ * COMPLETE gradient of the ReLU's output: at a residual join the sum of both branches; NaN kept as by F.relu), then the gate and
+ * the BatchNorm gradients exactly as the unguided entry.  Same arguments. */
+int xai_bn_relu_bwd_mask_guided_f32(const float* gy, const float* gy2, const void* mask, const float* weight,
+                                    const float* var, float eps, const float* weight2, const float* var2, float eps2,
+                                    int variant, int N, int C, int HW, float* gx, float* g_identity, xai_stream_t stream);
+
+/* xai_bn_relu_maxpool_bwd_f32 in guided mode (the stem's ReLU under evaluatePerturbation.py:154-158): the sum over the windows
+ * whose code selects p -- the max-pool's complete scattered gradient at p -- is clamped, g <= 0 ? +0 : g, AFTER the last window
+ * was added and before (g * weight) * invstd; never per window.  Same arguments. */
+int xai_bn_relu_maxpool_bwd_guided_f32(const float* gy, const float* gy2, const uint8_t* code, const float* weight,
+                                       const float* var, float eps, int variant, int N, int C, int H, int W, int PH,
+                                       int PW, int kernel, int stride, int pad, float* gx, xai_stream_t stream);
+
+/* K28 attr[b][c][y][x] = grad[b][c][y][x] * cam[b][sy][sx]          (cam NULL: attr = grad)
+ *     map[b][y][x]     = | ((a_0 + a_1) + a_2 + ...) |,  a_c = attr[b][c][y][x], channels left to right from the first
+ *     sy = min((int)floorf(y * ((float)h / H)), h - 1), sx likewise: F.interpolate(mode="nearest"), the legacy rule
+ * replaces  captum's GuidedGradCam product gbp * interpolate(cam) behind evaluatePerturbation.py:159-163 and the harness's
+ *           np.abs(np.sum(., axis=0)), :181 (for gbp, :154-158, with cam NULL)
+ *   grad : [B][C][H][W];  cam : [B][h][w] or NULL (h, w then ignored);  attr : [B][C][H][W] or NULL;  map : [B][H][W] or NULL
+ *   (one of the two outputs required); product and sums round separately; 16-byte accesses when W % 4 == 0 and grad, attr, map
+ *   are 16-byte aligned */
+int xai_guided_map_f32(const float* grad, const float* cam, int B, int C, int H, int W, int h, int w, float* attr,
+                       float* map, xai_stream_t stream);
 
 #ifdef __cplusplus
 }

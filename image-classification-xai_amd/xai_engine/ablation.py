@@ -23,9 +23,8 @@ import threading
 import torch
 
 from . import kernels as K
-from ._lib import XaiHipError
-from .ig import _logits_of
-from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs, on_worker, run_on_streams
+from .ig import _logits_of, abs_channel_sum, check_input, class_targets
+from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs, run_passes
 
 PASS_SIZE = 98                     # rows per classifier pass: the harness's 196 patches are two passes, its 36 windows one
 NUM_PATCHES = 14                   # the harness's patch grid (evaluatePerturbation.py:94)
@@ -50,26 +49,6 @@ class _ScorePass(CapturedCall):
     def step(self):
         with torch.no_grad():
             return (_logits_of(self.model(self.x)).float().gather(1, self.tgt).squeeze(1),)
-
-
-def _check_input(x, name):
-    if isinstance(x, (tuple, list)):
-        raise NotImplementedError(f"{name}: a tuple of input tensors is not supported, pass one (B, C, H, W) tensor")
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise XaiHipError(f"{name} needs its input on a HIP device ('cuda:N'); there is no CPU fallback")
-    if x.dim() != 4:
-        raise ValueError(f"{name}: inputs must be (B, C, H, W), got {tuple(x.shape)}")
-    return x.detach().float().contiguous()
-
-
-def _targets(targets, B, dev, name):
-    """-> (B,) int64 on the device, without reading a device value"""
-    if targets is None:
-        raise NotImplementedError(f"{name}: target=None (a forward function with one output per example) is not supported")
-    t = targets if torch.is_tensor(targets) else torch.tensor(targets)
-    if t.is_floating_point() or t.dim() > 1 or (t.numel() not in (1, B)):
-        raise NotImplementedError(f"{name}: target must be one class index or one per image, got {tuple(t.shape)} {t.dtype}")
-    return t.to(dev, torch.int64, non_blocking=True).reshape(-1).expand(B).contiguous()
 
 
 def _baseline(baselines, x, name):
@@ -158,11 +137,7 @@ def _harness_map(samples, H, W, shared):
     B, C, g, _ = samples.shape
     if shared and C <= 3:
         return K.bilinear_up(samples[:, 0].contiguous(), H, W, scale=float(C), take_abs=True)
-    up = K.bilinear_up(samples.reshape(B * C, g, g), H, W).view(B, C, H, W)
-    m = up[:, 0]
-    for c in range(1, C):
-        m = m + up[:, c]
-    return m.abs()
+    return abs_channel_sum(K.bilinear_up(samples.reshape(B * C, g, g), H, W).view(B, C, H, W))
 
 
 def _run(x, model, tgt, n_total, fill, pass_size, streams, graphs):
@@ -170,7 +145,6 @@ def _run(x, model, tgt, n_total, fill, pass_size, streams, graphs):
     `pass_size` rows of the flat list); `fill(first, n, out)` is the K26 launch."""
     B, dev, img_shape = x.shape[0], x.device, tuple(x.shape[1:])
     N = B * n_total
-    ps = max(1, min(int(pass_size), N))
     rows_tgt = tgt.repeat_interleave(n_total).view(N, 1)
     scores = torch.empty(N, dtype=torch.float32, device=dev)
     eager = {}
@@ -198,14 +172,7 @@ def _run(x, model, tgt, n_total, fill, pass_size, streams, graphs):
         p.tgt.copy_(rows_tgt[lo:hi])
         scores[lo:hi].copy_(score(p))
 
-    spans = [(lo, min(lo + ps, N)) for lo in range(0, N, ps)]
-    n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))
-    if n_streams == 1:
-        for lo, hi in spans:
-            one_pass(lo, hi)
-    else:
-        kind = ("ablation", id(model), ps, img_shape, bool(graphs))
-        run_on_streams(dev, n_streams, [lambda lo=lo, hi=hi: one_pass(lo, hi) for lo, hi in spans], kind=kind)
+    run_passes(dev, N, pass_size, one_pass, streams, kind=("ablation", id(model), int(pass_size), img_shape, bool(graphs)))
     ABLATION_COUNTS["rows"] += N
     return s0, scores.view(B, n_total)
 
@@ -228,9 +195,9 @@ def feature_ablation_batch(x, model, targets, feature_mask, baseline=0, pass_siz
     (evaluatePerturbation.py:92-97, :181) with a g x g nearest-exact `downsize`.
     `pass_size`: rows of the flat list of altered images per classifier pass; `streams` > 1: the passes run on that many stream
     workers; `graphs`: replay each distinct pass size from a hipGraph."""
-    x = _check_input(x, "feature_ablation_batch")
+    x = check_input(x, "feature_ablation_batch")
     B, C, H, W = x.shape
-    tgt = _targets(targets, B, x.device, "feature_ablation_batch")
+    tgt = class_targets(targets, B, x.device, "feature_ablation_batch")
     base = _baseline(baseline, x, "feature_ablation_batch")
     pm = prepare_mask(feature_mask, x.shape, x.device)
     if want_map is None and not attribution:
@@ -249,9 +216,9 @@ def occlusion_batch(x, model, targets, sliding_window_shapes, strides=None, base
     an int (every dimension), a (c, h, w) tuple or None (= the window).  Windows are enumerated in captum's order (the row shift
     fastest), overhanging ones clipped to the image; -> (B, C, H, W): per element the sum of s0 - score(window k) over the windows
     covering it, ascending k, divided by their number.  The other arguments as `feature_ablation_batch`."""
-    x = _check_input(x, "occlusion_batch")
+    x = check_input(x, "occlusion_batch")
     B, C, H, W = x.shape
-    tgt = _targets(targets, B, x.device, "occlusion_batch")
+    tgt = class_targets(targets, B, x.device, "occlusion_batch")
     base = _baseline(baseline, x, "occlusion_batch")
     win, st = _window_args(sliding_window_shapes, strides, x, "occlusion_batch")
     ch, cw = K.window_counts(H, W, win, st)

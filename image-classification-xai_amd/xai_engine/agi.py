@@ -20,7 +20,7 @@ import torch.nn as nn
 from . import kernels as K
 from ._lib import XaiHipError
 from .ig import _logits_of, hip_device
-from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_on_streams
+from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn, cat_parts, read_back, run_passes
 
 PERCENTILE, UPPERBOUND = 80, 99                   # the harness's percentiles (evaluatePerturbation.py:130-131)
 # how the passes ran (diagnostics); pair_iterations: pair-iterations the replays computed, pair_iterations_used: those a pair needed
@@ -156,36 +156,21 @@ def _attack(data, model, classes, epsilon, max_iter, normalize, images_per_pass,
     """-> (step_grad, init_pred, state (B*K, 4) int32 on the host, map)"""
     data = data.detach().float().contiguous()
     B, dev, img_shape = data.shape[0], data.device, tuple(data.shape[1:])
-    k = B if images_per_pass is None else max(1, min(int(images_per_pass), B))
-    spans = [(lo, min(lo + k, B)) for lo in range(0, B, k)]
     norm = None if normalize is None else (tuple(float(v) for v in normalize[0]), tuple(float(v) for v in normalize[1]))
     use_graphs = bool(graphs)
 
     def one_pass(lo, hi):
-        make = lambda: _AgiPass(model, hi - lo, classes, img_shape, dev, epsilon, max_iter, norm)  # noqa: E731
-        if use_graphs:
-            key = (hi - lo, img_shape, tuple(classes), float(epsilon), int(max_iter), norm)
-            p = _PASSES.get(model, dev, key, make)
-        else:
-            p = make()
+        key = (hi - lo, img_shape, tuple(classes), float(epsilon), int(max_iter), norm)
+        p = _PASSES.get(model, dev, key, lambda: _AgiPass(model, hi - lo, classes, img_shape, dev, epsilon, max_iter, norm), cached=use_graphs)
         return p(data[lo:hi], use_graphs)[:4]
 
-    n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))
-    if n_streams == 1:
-        parts = [one_pass(lo, hi) for lo, hi in spans]
-    else:
-        kind = ("agi_batch", id(model), k, img_shape, tuple(classes), float(epsilon), int(max_iter), norm, bool(use_graphs))
-        parts = run_on_streams(dev, n_streams, [lambda lo=lo, hi=hi: one_pass(lo, hi) for lo, hi in spans], kind=kind)
-    out = [p[0] if len(parts) == 1 else torch.cat(p) for p in zip(*parts)]
-    host = torch.empty(out[2].shape, dtype=out[2].dtype, pin_memory=True)
-    host.copy_(out[2], non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()          # the calling stream only
-    out[2] = host
-    P = host.shape[0]
-    AGI_COUNTS["pair_iterations"] += P * int(max_iter)
+    kind = ("agi_batch", id(model), images_per_pass, img_shape, tuple(classes), float(epsilon), int(max_iter), norm, use_graphs)
+    step_grad, init_pred, state, hm = cat_parts(run_passes(dev, B, images_per_pass, one_pass, streams, kind))
+    host = read_back(state)
+    AGI_COUNTS["pair_iterations"] += host.shape[0] * int(max_iter)
     done, reason = host[:, 1], host[:, 2]
     AGI_COUNTS["pair_iterations_used"] += int((done + (reason == 1).int()).sum())
-    return tuple(out)
+    return step_grad, init_pred, host, hm
 
 
 def agi_batch(data, model, false_classes, epsilon=0.05, max_iter=20, normalize=None, images_per_pass=None, streams=1, graphs=True,

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from . import kernels as K
 from . import prepare
 from ._lib import XaiHipError
-from .ig import _logits_of
+from .ig import _logits_of, check_input, class_targets
 from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn
 
 GUIDED_COUNTS = {"captures": 0, "captures_refused": 0, "replayed": 0, "eager": 0}
@@ -157,26 +157,6 @@ class _GuidedPass(CapturedCall):
         return tuple(t.clone() for t in out)             # a replay overwrites the graph's own outputs
 
 
-def _check_input(x, name):
-    if isinstance(x, (tuple, list)):
-        raise NotImplementedError(f"{name}: a tuple of input tensors is not supported, pass one (B, C, H, W) tensor")
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise XaiHipError(f"{name} needs its input on a HIP device ('cuda:N'); there is no CPU fallback")
-    if x.dim() != 4:
-        raise ValueError(f"{name}: inputs must be (B, C, H, W), got {tuple(x.shape)}")
-    return x.detach().float().contiguous()
-
-
-def _targets(targets, B, dev, name):
-    """-> (B, 1) int64 on the device, without reading a device value"""
-    if targets is None:
-        raise NotImplementedError(f"{name}: target=None is not supported, pass one class index or one per image")
-    t = targets if torch.is_tensor(targets) else torch.tensor(targets)
-    if t.is_floating_point() or t.dim() > 1 or t.numel() not in (1, B):
-        raise NotImplementedError(f"{name}: target must be one class index or one per image, got {tuple(t.shape)} {t.dtype}")
-    return t.to(dev, torch.int64, non_blocking=True).reshape(-1).expand(B).contiguous().view(B, 1)
-
-
 def guided_backprop_batch(x, model, targets, layer=None, want_attr=True, want_map=False, graphs=True):
     """Guided Backprop of B images in one classifier pass: x (B, C, H, W) on a HIP device, `targets` one class index or one per
     image (a device tensor is not read back); score = sum_b logits[b, targets[b]], so every image gets the guided gradient of its
@@ -184,17 +164,14 @@ def guided_backprop_batch(x, model, targets, layer=None, want_attr=True, want_ma
     times the nearest-upsampled Grad-CAM of the layer, from the same single backward.
     -> the attribution (B, C, H, W) (`want_attr`), the harness's map |sum over channels| (B, H, W) (`want_map`), or (attr, map).
     `graphs`: replay the pass from a hipGraph, kept per thread, model, input shape and layer."""
-    x = _check_input(x, "guided_backprop_batch")
+    x = check_input(x, "guided_backprop_batch")
     if not (want_attr or want_map):
         raise ValueError("guided_backprop_batch: nothing to return (neither want_attr nor want_map)")
     dev, shape = x.device, tuple(x.shape)
-    tgt = _targets(targets, shape[0], dev, "guided_backprop_batch")
+    tgt = class_targets(targets, shape[0], dev, "guided_backprop_batch").view(-1, 1)
     _refuse_inplace(model)                                # before any buffer or graph is made
-    make = lambda: _GuidedPass(model, layer, shape, dev, bool(want_attr), bool(want_map))  # noqa: E731
-    if graphs:
-        p = _PASSES.get(model, dev, (shape, None if layer is None else id(layer), bool(want_attr), bool(want_map)), make)
-    else:
-        p = make()
+    key = (shape, None if layer is None else id(layer), bool(want_attr), bool(want_map))
+    p = _PASSES.get(model, dev, key, lambda: _GuidedPass(model, layer, shape, dev, bool(want_attr), bool(want_map)), cached=bool(graphs))
     out = p(x, tgt, bool(graphs))
     return out if len(out) > 1 else out[0]
 
@@ -243,10 +220,10 @@ class GuidedGradCam:
         if interpolate_mode == "nearest" and not attribute_to_layer_input:
             return guided_backprop_batch(inputs, model, target, layer=self.layer, graphs=additional_forward_args is None)
         from .gradcam import LayerGradCam
-        x = _check_input(inputs, "GuidedGradCam.attribute")
-        tgt = _targets(target, x.shape[0], x.device, "GuidedGradCam.attribute")
-        gx, _, _ = guided_gradients(x, model, tgt)
-        cam = LayerGradCam(model, self.layer).attribute(x, tgt.view(-1), attribute_to_layer_input=attribute_to_layer_input, relu_attributions=True)
+        x = check_input(inputs, "GuidedGradCam.attribute")
+        tgt = class_targets(target, x.shape[0], x.device, "GuidedGradCam.attribute")
+        gx, _, _ = guided_gradients(x, model, tgt.view(-1, 1))
+        cam = LayerGradCam(model, self.layer).attribute(x, tgt, attribute_to_layer_input=attribute_to_layer_input, relu_attributions=True)
         return gx * F.interpolate(cam, x.shape[2:], mode=interpolate_mode)
 
 

@@ -14,8 +14,8 @@ import torch
 
 from . import kernels as K
 from ._lib import XaiHipError
-from .ig import _logits_of, hip_device
-from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_on_streams
+from .ig import _logits_of, abs_channel_sum, hip_device
+from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn, cat_parts, read_back, run_passes
 
 INPUT_OUTPUT_GRADIENTS = "INPUT_OUTPUT_GRADIENTS"      # the key of GIGBuilder.py:15
 GIG_COUNTS = {"captures": 0, "captures_refused": 0, "replayed": 0, "eager": 0}     # how the passes ran (diagnostics)
@@ -100,33 +100,18 @@ def guided_ig_batch(x, model, targets, steps=50, fraction=0.25, max_dist=0.02, b
     else:
         base = torch.full_like(x, float(baseline))
     targets = targets.to(dev).long().reshape(B)
-    k = B if images_per_pass is None else max(1, min(int(images_per_pass), B))
-    spans = [(lo, min(lo + k, B)) for lo in range(0, B, k)]
 
     def one_pass(lo, hi):
-        if graphs:
-            key = (hi - lo, img_shape, int(steps), float(fraction), float(max_dist))
-            p = _PASSES.get(model, dev, key, lambda: _GigPass(model, hi - lo, img_shape, dev, steps, fraction, max_dist))
-        else:
-            p = _GigPass(model, hi - lo, img_shape, dev, steps, fraction, max_dist)
+        key = (hi - lo, img_shape, int(steps), float(fraction), float(max_dist))
+        p = _PASSES.get(model, dev, key, lambda: _GigPass(model, hi - lo, img_shape, dev, steps, fraction, max_dist), cached=graphs)
         return p(x[lo:hi], base[lo:hi], targets[lo:hi], graphs)
 
-    n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))
-    if n_streams == 1:
-        parts = [one_pass(lo, hi) for lo, hi in spans]
-    else:
-        kind = ("guided_ig_batch", id(model), k, img_shape, int(steps), float(fraction), float(max_dist), bool(graphs))
-        parts = run_on_streams(dev, n_streams, [lambda lo=lo, hi=hi: one_pass(lo, hi) for lo, hi in spans], kind=kind)
-    attr = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
-    state = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
-    host = torch.empty(state.shape, dtype=state.dtype, pin_memory=True)
-    host.copy_(state, non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()          # the calling stream only
-    _raise_on_status(host)
+    kind = ("guided_ig_batch", id(model), images_per_pass, img_shape, int(steps), float(fraction), float(max_dist), bool(graphs))
+    attr, state = cat_parts(run_passes(dev, B, images_per_pass, one_pass, streams, kind))
+    _raise_on_status(read_back(state))
     if not want_abs:
         return attr
-    m = ((attr[:, 0] + attr[:, 1]) + attr[:, 2]).abs() if attr.shape[1] == 3 else attr.sum(1).abs()
-    return attr, m
+    return attr, (abs_channel_sum(attr) if attr.shape[1] == 3 else attr.sum(1).abs())
 
 
 def _is_builtin(fn):

@@ -12,7 +12,7 @@ import torch
 
 from . import kernels as K
 from ._lib import XaiHipError
-from .streams import GRAD_RTOL, LOGIT_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_on_streams
+from .streams import GRAD_RTOL, LOGIT_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_passes
 
 
 def hip_device(device):
@@ -28,6 +28,37 @@ def hip_device(device):
 
 def _logits_of(output):
     return output if isinstance(output, torch.Tensor) else output.logits
+
+
+def check_input(x, name):
+    """A driver's (B, C, H, W) input on a HIP device -> detached, float32, contiguous."""
+    if isinstance(x, (tuple, list)):
+        raise NotImplementedError(f"{name}: a tuple of input tensors is not supported, pass one (B, C, H, W) tensor")
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise XaiHipError(f"{name} needs its input on a HIP device ('cuda:N'); there is no CPU fallback")
+    if x.dim() != 4:
+        raise ValueError(f"{name}: inputs must be (B, C, H, W), got {tuple(x.shape)}")
+    return x.detach().float().contiguous()
+
+
+def class_targets(targets, B, dev, name):
+    """One class index or one per image (int, list or tensor) -> (B,) int64 on the device, without reading a device value."""
+    if targets is None:
+        raise NotImplementedError(f"{name}: target=None (a forward function with one output per example) is not supported, "
+                                  "pass one class index or one per image")
+    t = targets if torch.is_tensor(targets) else torch.tensor(targets)
+    if t.is_floating_point() or t.dim() > 1 or t.numel() not in (1, B):
+        raise NotImplementedError(f"{name}: target must be one class index or one per image, got {tuple(t.shape)} {t.dtype}")
+    return t.to(dev, torch.int64, non_blocking=True).reshape(-1).expand(B).contiguous()
+
+
+def abs_channel_sum(a):
+    """The harness's map |sum over channels| of a (..., C, H, W) tensor, added left to right -- (c0 + c1) + c2, the order NumPy's
+    sum over a leading axis uses and the bit-exact tests depend on."""
+    m = a[..., 0, :, :]
+    for c in range(1, a.shape[-3]):
+        m = m + a[..., c, :, :]
+    return m.abs()
 
 
 def _select_class(output, target_class):
@@ -253,15 +284,10 @@ class _CapturedPass(CapturedCall):
         self.t = torch.zeros(k, dtype=torch.int64, device=dev)
         self.base = torch.zeros_like(self.x) if torch.is_tensor(base) else None
         self.base_scalar = None if torch.is_tensor(base) else float(base)
-        self.alphas, self.model, self.steps, self.img_shape = alphas, model, steps, img_shape
+        self.alphas, self.model = alphas, model
 
     def step(self):
-        imgs = K.ig_interp(self.x, self.base if self.base is not None else self.base_scalar, self.alphas)
-        flat = imgs.view((-1,) + self.img_shape).requires_grad_(True)
-        out = _logits_of(self.model(flat))
-        scores = out.gather(1, self.t.repeat_interleave(self.steps).unsqueeze(1)).squeeze(1)
-        (g,) = torch.autograd.grad(scores, flat, grad_outputs=torch.ones_like(scores))
-        return g.contiguous(), scores.detach()
+        return _pass_grads(self.x, self.base if self.base is not None else self.base_scalar, self.alphas, self.t, self.model)
 
     def __call__(self, x, targets, base):
         self.x.copy_(x, non_blocking=True)
@@ -269,6 +295,16 @@ class _CapturedPass(CapturedCall):
         if self.base is not None:
             self.base.copy_(base, non_blocking=True)
         return self.run()
+
+
+def _pass_grads(x, base, alphas, targets, model):
+    """One classifier pass of k images x `steps` interpolants: K1, forward, every interpolant's target logit, backward
+    -> (gradients (k * steps, C,H,W), logits (k * steps,)).  (`backward_turn` does nothing on a stream worker, where captures run.)"""
+    flat = K.ig_interp(x, base, alphas).view((-1,) + tuple(x.shape[1:])).requires_grad_(True)
+    scores = _logits_of(model(flat)).gather(1, targets.repeat_interleave(alphas.shape[0]).unsqueeze(1)).squeeze(1)
+    with backward_turn(x.device):
+        (g,) = torch.autograd.grad(scores, flat, grad_outputs=torch.ones_like(scores))
+    return g.contiguous(), scores.detach()
 
 
 def _thread_pass(model, k, steps, img_shape, dev, alphas, base):
@@ -325,37 +361,27 @@ def ig_batch(x, model, targets, steps=50, alpha_star=1, baseline=0, images_per_p
         acc = torch.zeros_like(x)
     img_shape = tuple(x.shape[1:])
     use_graphs = (graphs if graphs is not None else True)
+    nested = on_worker()          # called from a stream worker: all passes run eagerly on that thread; only passes THIS call fans out replay
 
-    def one_pass(lo, hi, on_worker=False):
+    def one_pass(lo, hi):
         b = base[lo:hi] if torch.is_tensor(base) else base
-        cp = _thread_pass(model, hi - lo, steps, img_shape, dev, alphas, base) if (on_worker and use_graphs and hi - lo == images_per_pass) else None
+        fanned_out = on_worker() and not nested
+        cp = _thread_pass(model, hi - lo, steps, img_shape, dev, alphas, base) if (fanned_out and use_graphs and hi - lo == images_per_pass) else None
         if cp is not None:
             g, scores = cp(x[lo:hi], targets[lo:hi], b if torch.is_tensor(base) else None)
         else:
             PASS_COUNTS["eager"] += 1
-            imgs = K.ig_interp(x[lo:hi], b, alphas)                              # (k, steps, C,H,W)
-            flat = imgs.view((-1,) + img_shape).requires_grad_(True)
-            out = _logits_of(model(flat))
-            scores = out.gather(1, targets[lo:hi].repeat_interleave(steps).unsqueeze(1)).squeeze(1)
-            with backward_turn(dev):
-                (g,) = torch.autograd.grad(scores, flat, grad_outputs=torch.ones_like(scores))
-            g = g.contiguous()
+            g, scores = _pass_grads(x[lo:hi], b, alphas, targets[lo:hi], model)
         if buffered:
             K.store_grads(g, grads_buffer[lo:hi])
-            logits[lo:hi] = scores.detach().view(hi - lo, steps)
+            logits[lo:hi] = scores.view(hi - lo, steps)
         else:
             g = g.view((hi - lo, steps) + tuple(x.shape[1:]))
             for j in range(hi - lo):
                 K.ig_accum_add(g[j], acc[lo + j])
 
-    spans = [(lo, min(lo + images_per_pass, B)) for lo in range(0, B, images_per_pass)]
-    n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))      # (called from a stream worker: that thread is the stream)
-    if n_streams == 1:
-        for lo, hi in spans:
-            one_pass(lo, hi)
-    else:
-        kind = ("ig_batch", id(model), images_per_pass, steps, img_shape, buffered, use_graphs)
-        run_on_streams(dev, n_streams, [lambda lo=lo, hi=hi: one_pass(lo, hi, on_worker=True) for lo, hi in spans], kind=kind)
+    kind = ("ig_batch", id(model), images_per_pass, steps, img_shape, buffered, use_graphs)
+    run_passes(dev, B, images_per_pass, one_pass, streams, kind)
     if not buffered:
         return K.ig_finish(acc, steps, x, base, want_abs=want_abs)
     n_use = None if alpha_star == 1 else K.ig_cutoff(logits, alpha_star)

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from . import kernels as K
 from .ig import hip_device
+from .streams import run_passes
 
 
 def draw_masks(input_size, N, s, p1, rng=np.random):
@@ -71,12 +72,13 @@ def rise(model, image, txt_embedding, device, N=2000, s=8, p1=0.5, *, score_fn=N
         sh_all = torch.from_numpy(np.ascontiguousarray(shifts[lo:hi])).to(dev)
     n = hi - lo
     scores = torch.empty(n, dtype=torch.float32, device=dev)
-    spans = [(i, min(i + batch_size, n)) for i in range(0, n, batch_size)]
-    from .streams import on_worker
-    n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))
-    bufs = [torch.empty((min(batch_size, max(n, 1)),) + tuple(img.shape), dtype=torch.float32, device=dev) for _ in range(n_streams)]
+    bufs = {}                      # one batch buffer per stream, made by the thread that drives it at its first (= its largest) batch
 
-    def one_batch(i, j, buf):
+    def one_batch(i, j):
+        cur = torch.cuda.current_stream(dev)
+        if cur not in bufs:
+            bufs[cur] = torch.empty((j - i,) + tuple(img.shape), dtype=torch.float32, device=dev)
+        buf = bufs[cur]
         masked = K.rise_apply(g_all[i:j], sh_all[i:j], cell, img, out=buf[:j - i])
         if score_fn is not None:
             scores[i:j] = score_fn(masked).reshape(-1).float()
@@ -84,17 +86,11 @@ def rise(model, image, txt_embedding, device, N=2000, s=8, p1=0.5, *, score_fn=N
             feats = F.normalize(model.encode_image(masked), dim=-1)
             scores[i:j] = (feats @ txt_embedding.T).reshape(-1).float()
 
-    def job(k, i, j):
+    def job(i, j):
         with torch.no_grad():                                   # grad mode is thread-local: a stream worker starts with it enabled
-            one_batch(i, j, bufs[k % n_streams])
+            one_batch(i, j)
 
-    if n_streams == 1:
-        for k, (i, j) in enumerate(spans):
-            job(k, i, j)
-    else:
-        from .streams import run_on_streams                     # one host thread per stream (streams.py); forward only
-        run_on_streams(dev, n_streams, [lambda k=k, i=i, j=j: job(k, i, j) for k, (i, j) in enumerate(spans)],
-                       kind=("rise", id(model), batch_size, tuple(img.shape)))
+    run_passes(dev, n, batch_size, job, streams, kind=("rise", id(model), batch_size, tuple(img.shape)))   # forward only
     acc = torch.zeros((H, W), dtype=torch.float64, device=dev)
     if n > 0:
         K.rise_accum(g_all, sh_all, scores, cell, H, W, 1.0 / N / p1, acc=acc)

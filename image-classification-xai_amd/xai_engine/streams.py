@@ -157,6 +157,33 @@ def run_on_streams(dev, n, jobs, kind=None):
     return [f.result() for f in futs]
 
 
+def run_passes(dev, n, k, one_pass, streams, kind):
+    """Cut `range(n)` into passes of `k` (None: all of `n`; clamped to [1, n]; the last one may be ragged) and call `one_pass(lo, hi)`
+    for each: on the calling thread, in order, or with `streams` > 1 and more than one pass through `run_on_streams` on
+    min(streams, passes) workers.  A caller that is itself a stream worker IS its stream and never fans out.  -> the results in
+    pass order.  THE place where a driver's batch is cut and fanned out; `kind` as for `run_on_streams`."""
+    k = max(1, n if k is None else min(int(k), n))
+    spans = [(lo, min(lo + k, n)) for lo in range(0, n, k)]
+    n_streams = 1 if on_worker() else max(1, min(int(streams), len(spans)))
+    if n_streams == 1:
+        return [one_pass(lo, hi) for lo, hi in spans]
+    return run_on_streams(dev, n_streams, [lambda lo=lo, hi=hi: one_pass(lo, hi) for lo, hi in spans], kind=kind)
+
+
+def cat_parts(parts):
+    """The passes' tuples of tensors as one tuple: a single pass's own tensors as they are (no cat, no copy), else torch.cat per
+    position."""
+    return tuple(parts[0]) if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
+
+
+def read_back(t):
+    """A small device tensor on the host, through pinned memory; waits for the calling thread's current stream only."""
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    return host
+
+
 def join(dev, ws, main=None):
     """The current stream of the calling thread (or `main`) waits for everything queued so far on the workers' streams."""
     main = main if main is not None else torch.cuda.current_stream(dev)
@@ -317,8 +344,11 @@ class ThreadGraphs:
         """this thread's {key: (model, entry)}"""
         return self._local.__dict__.setdefault("entries", {})
 
-    def get(self, model, dev, key, make):
-        """this thread's entry for (model, dev, key), created by `make()` on first use"""
+    def get(self, model, dev, key, make, cached=True):
+        """this thread's entry for (model, dev, key), created by `make()` on first use; `cached=False` (the caller's graphs are
+        off): a fresh `make()` that is not kept"""
+        if not cached:
+            return make()
         entries = self.entries()
         key = (id(model), str(dev), bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark)) + tuple(key)
         if key not in entries:

@@ -25,7 +25,7 @@ from . import kernels as K
 from .blur import GaussianBlur
 from .gradcam import gradcam_saliency, CapturedGradCam
 from .guided_ig import guided_ig_batch
-from .ig import IG, IDG, getGradientsParallel, hip_device, _logits_of
+from .ig import IG, IDG, abs_channel_sum, getGradientsParallel, hip_device, _logits_of
 from .perturb import (AICMetric, MASMetric, MonotonicityMetric, PositiveNegativePerturbation, _Probe, sequence_stats)
 from .smooth import smoothGrad
 from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
@@ -49,6 +49,7 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
     attr_function = testing_dict["attr_func"]
     steps, baseline = 50, 0
     dev = hip_device(device)
+    sal = None                    # a branch leaves either `sal`, the finished (H, W) device map, or `saliency_map`, a (C, H, W) attribution
     if attr_function == "grad":
         x = input_tensor.to(dev).detach().requires_grad_(True)
         saliency_map, _ = getGradientsParallel(x, model, target_class)
@@ -84,7 +85,6 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
             raise ValueError(f"agi: the image predicted as class {int(init_pred[0])} has no attribution: every selected class "
                              "equals its prediction or no attack made an update (the reference crashes here)")
         sal = hm[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     elif attr_function == "sg":
         saliency_map = smoothGrad("IG", input_tensor, model, 50, baseline, target_class, device)
     elif attr_function == "gc":
@@ -100,7 +100,6 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
             sal = cache[key](x, target_class)[0]
         else:
             sal = gradcam_saliency(model, model.layer4, x, target_class, (img_hw, img_hw))[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     elif attr_function in ("gbp", "ggc"):
         # :154-163: captum's GuidedBackprop / GuidedGradCam(model, model.layer4) on models[1] (:84; the reference's copy without
         # in-place ReLUs -- a fused classifier needs none), then |sum over channels| (:181) straight from K28
@@ -109,7 +108,6 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         guided_model = models[1] if len(models) > 1 else models[0]
         sal = guided_backprop_batch(input_tensor.to(dev), guided_model, target_class,
                                     layer=guided_model.layer4 if attr_function == "ggc" else None, want_attr=False, want_map=True)[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     elif attr_function in ("fa", "occ"):
         # :171-176: captum's FeatureAblation over the 14 x 14 patch mask (:94-97) / Occlusion with window (3, 64, 64), stride 32;
         # resize(downsize(.)) and |sum over channels| (:92-95, :181) come from K27's 14 x 14 samples and the up-sample kernel
@@ -125,15 +123,16 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         else:
             sal = ablation.occlusion_batch(x, model, target_class, ablation.OCC_WINDOW, ablation.OCC_STRIDE,
                                            want_map=ablation.NUM_PATCHES, attribution=False)[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     else:
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit
-    if testing_dict.get("device_maps"):
-        # (a + b) + c per pixel, the order NumPy's sum over the leading axis uses: bit-identical to the host expression
+    device_maps = testing_dict.get("device_maps")
+    if sal is None and not device_maps:
+        return np.abs(np.sum(saliency_map.detach().cpu().numpy(), axis=0))       # the reference's expression, on the host
+    if sal is None:               # (a + b) + c per pixel: bit-identical to the host expression
         m = saliency_map.detach()
-        return ((m[0] + m[1]) + m[2]).abs() if m.shape[0] == 3 else m.sum(0).abs()
-    return np.abs(np.sum(saliency_map.detach().cpu().numpy(), axis=0))
+        sal = abs_channel_sum(m) if m.shape[0] == 3 else m.sum(0).abs()
+    return sal if device_maps else sal.cpu().numpy()
 
 
 def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):

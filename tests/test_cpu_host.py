@@ -651,3 +651,85 @@ def test_only_streams_py_captures_hip_graphs():
                 if "torch.cuda.graph(" in src or "CUDAGraph(" in src:
                     capturing.append(os.path.relpath(os.path.join(d, f), PKG))
     assert capturing == [os.path.join("xai_engine", "streams.py")]
+
+
+@pytest.mark.parametrize("n, k, spans", [(7, 3, [(0, 3), (3, 6), (6, 7)]), (7, 7, [(0, 7)]), (7, 99, [(0, 7)]), (7, None, [(0, 7)]),
+                                         (1, 1, [(0, 1)])])
+def test_run_passes_cuts_a_batch_into_spans_on_the_calling_thread(n, k, spans):
+    """streams.run_passes with one stream needs no device: the spans of `k` (None = all, clamped to [1, n], a ragged last one), the
+    results in span order."""
+    from xai_engine import streams
+    seen = []
+
+    def one_pass(lo, hi):
+        seen.append((lo, hi))
+        return hi * 100 + lo
+    assert streams.run_passes("cpu", n, k, one_pass, 1, "test") == [hi * 100 + lo for lo, hi in spans]
+    assert seen == spans
+
+
+def test_run_passes_propagates_an_exception_of_a_pass():
+    from xai_engine import streams
+
+    def one_pass(lo, hi):
+        if lo == 3:
+            raise KeyError("pass 2")
+    with pytest.raises(KeyError, match="pass 2"):
+        streams.run_passes("cpu", 7, 3, one_pass, 1, None)
+
+
+def test_cat_parts_hands_a_single_pass_through_and_concatenates_several():
+    from xai_engine import streams
+    a, b = torch.arange(6.).view(2, 3), torch.arange(2)
+    one = streams.cat_parts([(a, b)])
+    assert one[0] is a and one[1] is b and len(one) == 2
+    c, d = torch.ones(1, 3), torch.tensor([7])
+    both = streams.cat_parts([(a, b), (c, d)])
+    assert len(both) == 2 and torch.equal(both[0], torch.cat([a, c])) and torch.equal(both[1], torch.cat([b, d]))
+
+
+def test_class_targets_and_check_input_are_the_drivers_one_argument_check():
+    from xai_engine import XaiHipError
+    from xai_engine.ig import check_input, class_targets
+    B = 3
+    for given, want in ((2, [2, 2, 2]), (torch.tensor(2), [2, 2, 2]), ([4, 0, 1], [4, 0, 1]), (torch.tensor([4, 0, 1], dtype=torch.int32), [4, 0, 1])):
+        t = class_targets(given, B, "cpu", "test")
+        assert t.shape == (B,) and t.dtype == torch.int64 and t.is_contiguous() and t.tolist() == want
+    for bad in (None, torch.tensor([1., 2., 3.]), torch.tensor([[4], [0], [1]]), [1, 2], torch.tensor([1, 2, 3, 4])):
+        with pytest.raises(NotImplementedError):
+            class_targets(bad, B, "cpu", "test")
+    with pytest.raises(NotImplementedError):
+        check_input((torch.zeros(1, 3, 4, 4),), "test")
+    with pytest.raises(XaiHipError):
+        check_input(torch.zeros(1, 3, 4, 4), "test")
+
+
+def test_abs_channel_sum_adds_the_channels_left_to_right_on_either_layout():
+    """One function serves the (C, H, W) attribution of the sweep and the (B, C, H, W) batches of the drivers, in the association
+    order (c0 + c1) + c2 of NumPy's sum over a leading axis."""
+    from xai_engine.ig import abs_channel_sum
+    a = (torch.randn(2, 3, 5, 7, generator=torch.Generator().manual_seed(3)) * 1e3).float()
+    want = ((a[:, 0] + a[:, 1]) + a[:, 2]).abs()
+    assert torch.equal(abs_channel_sum(a), want)
+    for i in range(2):
+        assert torch.equal(abs_channel_sum(a[i]), want[i])
+        np.testing.assert_array_equal(abs_channel_sum(a[i]).numpy(), np.abs(np.sum(a[i].numpy(), axis=0)))
+    five = torch.randn(5, 4, 4, generator=torch.Generator().manual_seed(4))
+    assert torch.equal(abs_channel_sum(five), ((((five[0] + five[1]) + five[2]) + five[3]) + five[4]).abs())
+    assert torch.equal(abs_channel_sum(five[:1]), five[0].abs())
+
+
+def test_only_streams_py_fans_passes_out_and_no_driver_keeps_a_private_argument_check():
+    """Where a batch is cut and handed to stream workers is decided in one module (streams.run_passes), and the input / target
+    checks of the drivers have one home (ig.check_input, ig.class_targets)."""
+    fanning, private = [], []
+    for d, _, files in os.walk(PKG):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(d, f)).read()
+                if "run_on_streams(" in src:
+                    fanning.append(os.path.relpath(os.path.join(d, f), PKG))
+                if re.search(r"def (_check_input|_targets)\b", src):
+                    private.append(os.path.relpath(os.path.join(d, f), PKG))
+    assert fanning == [os.path.join("xai_engine", "streams.py")]
+    assert private == []

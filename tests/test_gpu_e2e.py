@@ -190,6 +190,27 @@ def test_ig_batch_on_stream_workers_with_and_without_graphs_and_with_an_uncaptur
     np.testing.assert_array_equal(torch.stack(maps).cpu().numpy(), ig_batch(xs, model, ts, steps=50, images_per_pass=1).cpu().numpy())
 
 
+def test_ig_batch_called_from_a_stream_worker_runs_its_passes_eagerly_on_that_thread():
+    """A caller that is already a stream worker IS its stream: ig_batch fans nothing out there and replays nothing (only passes that
+    the call itself hands to workers replay) -- two eager passes, no capture, the bits of the same call from the main thread."""
+    from xai_engine import ig as igmod
+    from xai_engine.streams import run_on_streams
+    model = tiny_from(load_golden("ig_small.npz"), DEV)
+    xs = torch.randn(2, 3, 32, 32, generator=torch.Generator().manual_seed(13)).to(DEV)
+    with torch.no_grad():
+        ts = model(xs).argmax(1)
+
+    def call():
+        return igmod.ig_batch(xs, model, ts, steps=4, images_per_pass=1, streams=3)
+    main = call()
+    before = dict(igmod.PASS_COUNTS)
+    (nested,) = run_on_streams(DEV, 1, [call], kind="nested ig_batch test")
+    after = dict(igmod.PASS_COUNTS)
+    assert after["eager"] - before["eager"] == 2
+    assert after["replayed"] == before["replayed"] and after["captures"] == before["captures"]
+    assert torch.equal(nested, main)
+
+
 def _refusals(cache, model):
     """the refusal reasons of `model`'s entries in a driver's graph cache, on each of three stream workers"""
     from xai_engine.streams import run_on_streams

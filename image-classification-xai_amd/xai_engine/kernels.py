@@ -885,3 +885,62 @@ def ablation_finish_windows(s0, scores, window, strides, shape, g=None, want_att
     _call("xai_ablation_finish_windows_f32", s0.device, _ptr(s0), _ptr(scores), int(window[0]), int(window[1]), int(strides[0]),
           int(strides[1]), B, Cc, H, W, int(g or 0), _ptr(attr), _ptr(samples))
     return attr, samples
+
+
+# ------------------------------------------------------------------------------ XRAI (K29, K30)
+U8 = torch.uint8
+XRAI_STATUS = {1: "masks remain but none has a gain above -inf (NaN or -inf in the attribution): the reference crashes at this "
+                  "point with KeyError on remaining_masks[None] (XRAIBuilder.py:682)",
+               2: "a full-mask gain is NaN: the order of the reference's sort (XRAIBuilder.py:754-755) is undefined"}
+
+
+def xrai_words(H, W):
+    return (H * W + 63) // 64
+
+
+def xrai_pack(H, W, radius, M, labels=None, label_min=None, label_max=None, masks=None):
+    """K29: label maps (S, H, W) int32 with per-map label_min / label_max (S,) int32, or masks (M, H, W) uint8 -> the dilated
+    bit planes (M, n_words) int64 and span (M, 2) int32 (first, last non-empty word).  `M` in label mode: the sum of
+    label_max - label_min + 1 (the caller knows the ranges; nothing is read back here)."""
+    if (labels is None) == (masks is None):
+        raise ValueError("xrai_pack: pass label maps or masks, not both")
+    if labels is not None:
+        _need(labels, I32, "labels"); _need(label_min, I32, "label_min"); _need(label_max, I32, "label_max")
+        S, src = labels.shape[0], labels
+        if labels.dim() != 3 or tuple(labels.shape[1:]) != (H, W) or label_min.numel() != S or label_max.numel() != S:
+            raise ValueError("xrai_pack: labels must be (S, H, W) and label_min, label_max (S,)")
+    else:
+        _need(masks, U8, "masks")
+        S, src = 0, masks
+        if masks.dim() != 3 or tuple(masks.shape) != (M, H, W):
+            raise ValueError("xrai_pack: masks must be (M, H, W)")
+    bits = torch.empty((M, xrai_words(H, W)), dtype=I64, device=src.device)
+    span = torch.empty((M, 2), dtype=I32, device=src.device)
+    if M:
+        _call("xai_xrai_pack_u64", src.device, _ptr(labels), _ptr(label_min), _ptr(label_max), S, _ptr(masks), M, H, W, int(radius),
+              _ptr(bits), _ptr(span))
+    return bits, span
+
+
+def xrai_rank(attr, bits, span, mask_first, min_pixel_diff, area_threshold, fast=False):
+    """K30: attr (B, H, W), the planes of all images and mask_first (B + 1,) int32 -> out (B, H, W) fp32, pixel_iter (B, H, W)
+    int32, sel_key (M,) int32, sel_gain (M,) fp32, state (B, 4) int32 = selections, uncomputed pixels, status, covered pixels."""
+    _need(attr, F32, "attr"); _need(bits, I64, "bits"); _need(span, I32, "span"); _need(mask_first, I32, "mask_first")
+    if attr.dim() != 3:
+        raise ValueError("xrai_rank: attr must be (B, H, W)")
+    B, H, W = attr.shape
+    M = bits.shape[0]
+    if bits.dim() != 2 or bits.shape[1] != xrai_words(H, W) or span.numel() != 2 * M or mask_first.numel() != B + 1:
+        raise ValueError("xrai_rank: bits must be (M, ceil(H*W/64)), span (M, 2) and mask_first (B + 1,)")
+    dev = attr.device
+    out = torch.empty((B, H, W), dtype=F32, device=dev)
+    pixel_iter = torch.empty((B, H, W), dtype=I32, device=dev)
+    sel_key = torch.empty(M, dtype=I32, device=dev)
+    sel_gain = torch.empty(M, dtype=F32, device=dev)
+    state = torch.empty((B, 4), dtype=I32, device=dev)
+    nbytes = _lib.load().xai_xrai_workspace_bytes(B, H, W, M)
+    ws = torch.empty(nbytes, dtype=U8, device=dev)
+    _call("xai_xrai_rank_f32", dev, _ptr(attr), _ptr(bits) if M else None, _ptr(span) if M else None, _ptr(mask_first), B, M, H, W,
+          int(min_pixel_diff), float(area_threshold), int(bool(fast)), _ptr(out), _ptr(pixel_iter), _ptr(sel_key) if M else None,
+          _ptr(sel_gain) if M else None, _ptr(state), _ptr(ws), nbytes)
+    return out, pixel_iter, sel_key, sel_gain, state

@@ -224,8 +224,47 @@ def run(device="cuda:0", verbose=True):
     attr, _ = K.ablation_finish_windows(s0_, sc_, (12, 12), (8, 8), xa_.shape)
     want = ((s0_[:, None] - sc_).double()[:, :, None, None, None] * wm[None].double()).sum(1) / wm.double().sum(0)
     check("ablation_finish_windows", _rel(attr, want.expand(2, 3, 28, 28)), 2e-6)
+    # K29 / K30: XRAI's segments as dilated bit planes, and its greedy ranking
+    Hx, Wx, rad = 33, 31, 3                                              # 1023 pixels: one dead tail bit
+    labels = torch.randint(0, 7, (2, Hx // 3 + 1, Wx // 4 + 1), device=dev, generator=gen, dtype=torch.int32)
+    labels = labels.repeat_interleave(3, 1).repeat_interleave(4, 2)[:, :Hx, :Wx].contiguous()
+    lo = torch.zeros(2, dtype=torch.int32, device=dev)
+    bits, span = K.xrai_pack(Hx, Wx, rad, 14, labels=labels, label_min=lo, label_max=lo + 6)
+    ax = torch.arange(-rad, rad + 1, device=dev)
+    disk = ((ax[:, None] ** 2 + ax[None, :] ** 2) <= rad * rad).float()[None, None]
+    masks = (labels[:, None] == torch.arange(7, device=dev).view(1, -1, 1, 1)).flatten(0, 1)          # (14, H, W), map by map
+    dil = F.conv2d(masks[:, None].float(), disk, padding=rad)[:, 0] > 0
+    flat = F.pad(dil.flatten(1), (0, bits.shape[1] * 64 - Hx * Wx)).view(14, -1, 64).long()
+    want = (flat << torch.arange(64, device=dev)).sum(2)                 # int64 wraps at bit 63 like the words
+    check("xrai_pack (bitwise vs torch)", float((bits != want).sum()), 0.0)
+    nz = want != 0
+    idx = torch.arange(want.shape[1], device=dev)
+    first = torch.where(nz, idx, want.shape[1]).amin(1)
+    last = torch.where(nz, idx, -1).amax(1)
+    check("xrai_pack span", float((span.long() - torch.stack([first, last], 1)).abs().max()), 0.0)
+    xattr = F.avg_pool2d(rnd(1, 1, Hx + 4, Wx + 4), 5, 1)[0]             # (1, H, W), smooth
+    mf = torch.tensor([0, 14], dtype=torch.int32).to(dev)
+    xo, piter, skey, sgain, xstate = K.xrai_rank(xattr, bits, span, mf, 20, 1.0)
+    cur = torch.zeros(Hx, Wx, dtype=torch.bool, device=dev)
+    alive, keys, a64, want = list(range(14)), [], xattr[0].double(), torch.zeros(Hx, Wx, dtype=torch.float64, device=dev)
+    while alive:
+        diffs = {m: dil[m] & ~cur for m in alive}
+        alive = [m for m in alive if int(diffs[m].sum()) >= 20]
+        if not alive:
+            break
+        gains = [float((a64 * diffs[m]).sum() / diffs[m].sum()) for m in alive]
+        b = alive[max(range(len(alive)), key=lambda i: (gains[i], -i))]
+        want[diffs[b]] = max(gains)
+        cur |= dil[b]
+        keys.append(b)
+        alive.remove(b)
+    if not bool(cur.all()):
+        want[~cur] = a64[~cur].mean()
+    n_sel = int(xstate[0, 0])
+    check("xrai_rank selections", float(n_sel != len(keys) or skey[:n_sel].tolist() != keys), 0.0)
+    check("xrai_rank map", _rel(xo[0], want), 2e-6)
     wrong = unprotected = 0.0
-    for _ in range(3):         # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
+    for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)
         wrong, unprotected = max(wrong, w), max(unprotected, u)
     check("stream workers (wrong results)", float(wrong), 0.0)

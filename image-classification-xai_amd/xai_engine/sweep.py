@@ -31,7 +31,7 @@ from .smooth import smoothGrad
 from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "gc", "gbp", "ggc", "fa", "occ")
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "xrai", "gc", "gbp", "ggc", "fa", "occ")
 TRANS_ATTR_FUNCS = ("agi",)          # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
@@ -87,6 +87,14 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         sal = hm[0]
     elif attr_function == "sg":
         saliency_map = smoothGrad("IG", input_tensor, model, 50, baseline, target_class, device)
+    elif attr_function == "xrai":
+        # :142-146: IG (50 steps, the engine's K1 / K2), max over the channels, Felzenszwalb's six label maps of the image on the
+        # host (skimage; testing_dict["xrai_label_maps"], not a reference key, replaces the segmenter), K29 at radius 5, K30;
+        # |.| of the one-channel map (:181)
+        from . import xrai
+        ig = IG(input_tensor, model, steps, batch_size, 1, baseline, device, target_class)
+        label_maps = (testing_dict.get("xrai_label_maps") or xrai.felzenszwalb_label_maps)(input_tensor.squeeze().permute(1, 2, 0).cpu())
+        sal = xrai.xrai_batch(ig.detach().to(dev)[None], xrai.pack_segments(label_maps, dilation_rad=5, device=dev))[0].abs()
     elif attr_function == "gc":
         # |cam_up + cam_up + cam_up| fused into the up-sample kernel (scale 3, abs); with testing_dict["capture_gradcam"] the
         # launch-bound one-image pass is one hipGraph replay (captured once per model and input shape)

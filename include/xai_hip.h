@@ -44,9 +44,10 @@ typedef void* xai_stream_t; /* hipStream_t */
  *   7 = + xai_ablate_features_f32, xai_ablate_windows_f32, xai_ablation_finish_features_f32, xai_ablation_finish_windows_f32;
  *   8 = + xai_bn_gate_mask_bytes, xai_bn_relu_fwd_mask_f32, xai_bn_relu_bwd_mask_f32, xai_bn_relu_maxpool_fwd_code_f32,
  *         xai_bn_relu_maxpool_bwd_f32;
- *   9 = + xai_bn_relu_bwd_mask_guided_f32, xai_bn_relu_maxpool_bwd_guided_f32, xai_guided_map_f32 */
+ *   9 = + xai_bn_relu_bwd_mask_guided_f32, xai_bn_relu_maxpool_bwd_guided_f32, xai_guided_map_f32;
+ *  10 = + xai_xrai_workspace_bytes, xai_xrai_pack_u64, xai_xrai_rank_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 9
+#define XAI_ABI_MINOR 10
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -502,6 +503,53 @@ int xai_bn_relu_maxpool_bwd_guided_f32(const float* gy, const float* gy2, const 
  *   are 16-byte aligned */
 int xai_guided_map_f32(const float* grad, const float* cam, int B, int C, int H, int W, int h, int w, float* attr,
                        float* map, xai_stream_t stream);
+
+/* ---- XRAI (xai_engine/xrai.py) ---------------------------------------------------------- */
+
+/* Bit planes: mask m is n_words = ceil(H*W / 64) uint64 words; pixel p = y*W + x is bit p % 64 of word p / 64; the bits at
+ * positions >= H*W are zero.
+ *
+ * K29 bits[m] = dilate(mask m, disk(radius)), span[m] = (first, last) non-empty word of it, (n_words, -1) when it is empty
+ * replaces  XRAIBuilder.py:287-292 (_unpack_segs_to_masks) and the dilation of :256-258
+ *   label mode (labels != NULL, masks == NULL): labels : [S][H][W] int32;  label_min, label_max : [S] (device).  Map s gives one
+ *     mask per integer l in [label_min[s], label_max[s]], in that order, the maps one after the other; an absent label is an
+ *     empty mask that keeps its index; a label outside the stated range of its map belongs to no mask.
+ *     M must be the sum of label_max[s] - label_min[s] + 1.
+ *   mask mode (masks != NULL, labels == NULL): masks : [M][H][W] uint8, non-zero = set
+ *   out[y][x] = OR of in[y + dy][x + dx] over the offsets dx*dx + dy*dy <= radius*radius that stay inside the image (skimage's
+ *     disk(radius) footprint, 81 offsets at radius 5; a neighbour outside the image counts as false, which for this footprint
+ *     equals skimage's reflecting border); radius 0 only packs; radius <= 64, above it XAI_E_UNSUPPORTED
+ *   bits : [M][n_words] (zeroed here);  span : [M][2] int32 */
+int xai_xrai_pack_u64(const int32_t* labels, const int32_t* label_min, const int32_t* label_max, int S, const uint8_t* masks,
+                      int64_t M, int H, int W, int radius, uint64_t* bits, int32_t* span, xai_stream_t stream);
+
+/* bytes of workspace xai_xrai_rank_f32 needs (16-byte aligned; nothing has to be zeroed); 0 for a non-positive extent.  It holds
+ * what the reference keeps in `remaining_masks` (XRAIBuilder.py:656): per mask a cached remainder count and gain, and the order of
+ * the fast mode (:754-755) */
+size_t xai_xrai_workspace_bytes(int n_img, int H, int W, int64_t M_total);
+
+/* K30 the greedy region ranking of n_img images in one launch, one workgroup per image
+ * replaces  XRAIBuilder.py:619-711 (XRAI._xrai; fast != 0: _xrai_fast, :714-789) with _gain_density / _get_diff_cnt, :266-284
+ *   attr : [n_img][H*W];  bits, span : the planes of all images, image i owns the masks [mask_first[i], mask_first[i + 1])
+ *   (mask_first : [n_img + 1] int32 on the device, ascending, last entry M_total; an image may own none)
+ *   Every iteration takes the remaining masks in ascending index: cnt = popcount(mask & ~current); cnt < min_pixel_diff drops
+ *   the mask for good; else gain = (float)(fp64 sum of attr over those pixels / cnt).  The FIRST mask with the strictly
+ *   greatest gain is selected (a tie goes to the lowest index): out over its remainder = gain, pixel_iter = the selection's
+ *   number, current |= mask.  The loop ends when no mask remains or count(current) / (H*W) > area_threshold (fp64).  The pixels
+ *   never covered get (float)(fp64 sum of attr over them / their count) and keep pixel_iter -1.
+ *   fast: full-mask gains once, stable order by descending gain, one pass with the same drop rule; area_threshold is ignored.
+ *   out : [n_img][H*W] fp32;  pixel_iter : [n_img][H*W] int32;  sel_key, sel_gain : [M_total], image i's selections in order from
+ *   mask_first[i] on, keys relative to the image's first mask;  state : [n_img][4] int32 = selections, uncomputed pixels,
+ *   status, covered pixels.  status 1: masks remain but none has a gain above -inf (NaN or -inf attr) -- the reference dies
+ *   there with KeyError (remaining_masks[None], :682); status 2 (fast): a full-mask gain is NaN, the reference's sort order is
+ *   then undefined.  The sums are taken in one fixed order, there are no floating-point atomics: two runs give the same bits.
+ *   Limits: H*W <= 262144 (512 x 512: `current` is held in 32 KiB of LDS), above it XAI_E_UNSUPPORTED; min_pixel_diff < 1
+ *   (the reference then loops over empty masks and crashes) XAI_E_UNSUPPORTED; bits, span, sel_key, sel_gain may be NULL when
+ *   M_total == 0. */
+int xai_xrai_rank_f32(const float* attr, const uint64_t* bits, const int32_t* span, const int32_t* mask_first, int n_img,
+                      int64_t M_total, int H, int W, int min_pixel_diff, double area_threshold, int fast, float* out,
+                      int32_t* pixel_iter, int32_t* sel_key, float* sel_gain, int32_t* state, void* workspace,
+                      size_t workspace_bytes, xai_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -153,8 +153,7 @@ int launch_ablate(const float* x, const int32_t* ids, int ids_C, int id_min, con
   XAI_REQUIRE(static_cast<int64_t>(B) * n_total <= INT32_MAX, XAI_E_UNSUPPORTED);
   XAI_REQUIRE(first + n <= static_cast<int64_t>(B) * n_total, XAI_E_SHAPE);
   const int64_t hw = static_cast<int64_t>(H) * W;
-  const bool vec = (hw % 4 == 0) && xai_aligned16(x) && xai_aligned16(out) && (ids == nullptr || xai_aligned16(ids)) &&
-                   (baseline == nullptr || xai_aligned16(baseline));
+  const bool vec = xai_can_vec4(hw, {x, out, ids, baseline});
   const int64_t tiles = xai_ceil_div(hw, kBlock * (vec ? 4 : 1));
   int per, zdim = 1;
   if (static_cast<int64_t>(n) * C * hw * 4 >= (int64_t(64) << 20) && C <= 64) {

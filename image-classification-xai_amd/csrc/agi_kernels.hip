@@ -41,58 +41,6 @@ constexpr int kMaxChunks = 1024;             // grid-stride beyond this
 
 enum : int32_t { kRunning = 0, kReached = 1, kSkipped = 2, kMaxIter = 3 };
 
-// torch.max on the CPU: the first NaN if there is one, else the first maximal value.  -> true if (v2, i2) beats (v1, i1).
-__device__ __forceinline__ bool beats(float v1, int i1, float v2, int i2) {
-  const bool n1 = v1 != v1, n2 = v2 != v2;
-  if (n1) return n2 && i2 < i1;
-  if (n2) return true;
-  return v2 > v1 || (v2 == v1 && i2 < i1);
-}
-
-// argmax of row[0..n) over one wave; every lane gets the result.
-__device__ __forceinline__ int wave_argmax(const float* row, int n) {
-  const int lane = threadIdx.x & (kWave - 1);
-  float bv = 0.f;
-  int bi = -1;
-  for (int j = lane; j < n; j += kWave) {
-    const float v = row[j];
-    if (bi < 0 || beats(bv, bi, v, j)) { bv = v; bi = j; }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(bv, off, kWave);
-    const int oi = __shfl_xor(bi, off, kWave);
-    if (oi >= 0 && (bi < 0 || beats(bv, bi, ov, oi))) { bv = ov; bi = oi; }
-  }
-  return bi;
-}
-
-template <int V>
-struct Pack {
-  float v[V];
-};
-
-template <int V>
-__device__ __forceinline__ Pack<V> ldp(const float* p) {
-  Pack<V> r;
-  if constexpr (V == 4) {
-    const float4 t = ld4(p);
-    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ void stp(float* p, const Pack<V>& a) {
-  if constexpr (V == 4) {
-    st4(p, make_float4(a.v[0], a.v[1], a.v[2], a.v[3]));
-  } else {
-    *p = a.v[0];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ K23
 template <int V>
 __global__ __launch_bounds__(kBlock) void agi_init_kernel(const float* __restrict__ logits, const float* __restrict__ data,
@@ -113,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void agi_init_kernel(const float* __restric
     stp<V>(cd + i, z);
   }
   if (blockIdx.x == 0 && threadIdx.x < kWave) {
-    const int pred = wave_argmax(logits + static_cast<int64_t>(b) * n_out, n_out);
+    const int pred = wave_argmax(logits + static_cast<int64_t>(b) * n_out, n_out).i;
     if (threadIdx.x == 0) {
       const bool skip = classes[k] == pred;                       // AGI.py:97-98
       int32_t* st = state + 4 * static_cast<int64_t>(p);
@@ -134,7 +82,7 @@ __global__ __launch_bounds__(kDecideBlock) void agi_decide_kernel(const float* _
   if (p >= n_pair) return;                                        // whole waves leave together
   int32_t* st = state + 4 * static_cast<int64_t>(p);
   const int32_t active = st[0];
-  const int pred = wave_argmax(logits + static_cast<int64_t>(p) * n_out, n_out);
+  const int pred = wave_argmax(logits + static_cast<int64_t>(p) * n_out, n_out).i;
   if ((threadIdx.x & (kWave - 1)) != 0) return;
   if (!active) {
     st[3] = 0;
@@ -192,32 +140,6 @@ __device__ __forceinline__ uint32_t okey(float f) {
 
 __device__ __forceinline__ float unkey(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-// Digit d of `hist` with count(< d) <= k < count(<= d); k becomes the rank inside that digit.  Lane t owns bins 2t, 2t+1.
-__device__ __forceinline__ uint32_t find_digit(const uint32_t* hist, uint32_t& k, uint32_t* wsum, uint32_t* pick) {
-  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-  const uint32_t c0 = hist[2 * t], c1 = hist[2 * t + 1], c = c0 + c1;
-  uint32_t incl = c;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const uint32_t up = __shfl_up(incl, off, kWave);
-    if (lane >= off) incl += up;
-  }
-  if (lane == kWave - 1) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t pre = incl - c;
-  for (int w = 0; w < wave; ++w) pre += wsum[w];
-  if (k >= pre && k < pre + c0) {
-    pick[0] = 2 * t; pick[1] = k - pre;
-  } else if (k >= pre + c0 && k < pre + c) {
-    pick[0] = 2 * t + 1; pick[1] = k - pre - c0;
-  }
-  __syncthreads();
-  const uint32_t d = pick[0];
-  k = pick[1];
-  __syncthreads();
-  return d;
 }
 
 // NumPy's _lerp in float32 (numpy/lib/_function_base_impl.py): a + (b - a) * t, or b - (b - a) * (1 - t) where t >= 0.5
@@ -278,7 +200,7 @@ __global__ __launch_bounds__(kMapThreads) void agi_heatmap_kernel(const float* _
   for (int j = 0; j < 4; ++j) kr[j] = pct.rank[j];
   uint32_t d1[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) d1[j] = find_digit(hist[0], kr[j], wsum, pick);
+  for (int j = 0; j < 4; ++j) d1[j] = select_digit<kMapThreads>(hist[0], kr[j], wsum, pick);
   for (int j = tid; j < 4 * kBins; j += kMapThreads) (&hist[0][0])[j] = 0u;
   __syncthreads();
   for (int64_t i = tid; i < HW; i += kMapThreads) {
@@ -290,7 +212,7 @@ __global__ __launch_bounds__(kMapThreads) void agi_heatmap_kernel(const float* _
   __syncthreads();
   uint32_t hi[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) hi[j] = (d1[j] << 11) | find_digit(hist[j], kr[j], wsum, pick);
+  for (int j = 0; j < 4; ++j) hi[j] = (d1[j] << 11) | select_digit<kMapThreads>(hist[j], kr[j], wsum, pick);
   for (int j = tid; j < 4 * kBins; j += kMapThreads) (&hist[0][0])[j] = 0u;
   __syncthreads();
   for (int64_t i = tid; i < HW; i += kMapThreads) {
@@ -302,7 +224,7 @@ __global__ __launch_bounds__(kMapThreads) void agi_heatmap_kernel(const float* _
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const uint32_t d = find_digit(hist[j], kr[j], wsum, pick);
+    const uint32_t d = select_digit<kMapThreads>(hist[j], kr[j], wsum, pick);
     if (tid == 0) digit[j] = (hi[j] << 10) | d;
   }
   if (tid == 0) {
@@ -342,10 +264,6 @@ void np_percentile_plan(double q, int64_t n, uint32_t* rank, float* gamma) {
   *gamma = static_cast<float>(static_cast<double>(v) - prev);
 }
 
-bool vec4_ok(int64_t N, const void* a, const void* b, const void* c, const void* d, const void* e) {
-  return N % 4 == 0 && xai_aligned16(a) && xai_aligned16(b) && xai_aligned16(c) && xai_aligned16(d) && xai_aligned16(e);
-}
-
 unsigned chunks_for(int64_t N, int V) {
   const int64_t c = xai_ceil_div(N, static_cast<int64_t>(kBlock) * V);
   return static_cast<unsigned>(c < kMaxChunks ? c : kMaxChunks);
@@ -362,7 +280,7 @@ XAI_EXPORT int xai_agi_init_f32(const float* logits, const float* data, const in
   XAI_REQUIRE(static_cast<int64_t>(n_img) * n_cls <= 65535 && n_elem < (int64_t{1} << 31), XAI_E_UNSUPPORTED);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const int n_pair = n_img * n_cls;
-  if (vec4_ok(n_elem, data, x_cur, c_delta, x_cur, c_delta))
+  if (xai_can_vec4(n_elem, {data, x_cur, c_delta}))
     hipLaunchKernelGGL(agi_init_kernel<4>, dim3(chunks_for(n_elem, 4), n_pair), dim3(kBlock), 0, st, logits, data, classes, n_cls,
                        n_out, n_elem, init_pred, x_cur, c_delta, state);
   else
@@ -386,7 +304,7 @@ XAI_EXPORT int xai_agi_step_f32(const float* logits, const float* g_adv, const f
                      n_out, max_iter, state);
   int rc = xai_launch_status();
   if (rc != XAI_OK) return rc;
-  if (vec4_ok(n_elem, g_adv, g_lab, data, x_cur, c_delta))
+  if (xai_can_vec4(n_elem, {g_adv, g_lab, data, x_cur, c_delta}))
     hipLaunchKernelGGL(agi_update_kernel<4>, dim3(chunks_for(n_elem, 4), n_pair), dim3(kBlock), 0, st, g_adv, g_lab, data, n_cls,
                        n_elem, epsilon, state, x_cur, c_delta);
   else

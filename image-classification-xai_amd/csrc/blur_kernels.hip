@@ -81,11 +81,10 @@ __global__ __launch_bounds__(kBlock) void blur_sep_kernel(const float* __restric
       float w[KLEN + 5];                               // KLEN + 3 values are used; 36 = nine quads for KLEN = 31
       // explicit LDS address space + 16-byte vector type: left to itself the compiler re-splits these loads into
       // ds_read2_b32 / ds_read2_b64 (which bring the 2-way conflict back)
-      typedef float lds_f4 __attribute__((ext_vector_type(4)));
-      const __attribute__((address_space(3))) lds_f4* seg = (const __attribute__((address_space(3))) lds_f4*)row;
+      const __attribute__((address_space(3))) xai_f32x4* seg = (const __attribute__((address_space(3))) xai_f32x4*)row;
 #pragma unroll
       for (int v = 0; v < (KLEN + 5) / 4; ++v) {
-        const lds_f4 t = __builtin_nontemporal_load(seg + v);
+        const xai_f32x4 t = __builtin_nontemporal_load(seg + v);
         w[4 * v] = t.x; w[4 * v + 1] = t.y; w[4 * v + 2] = t.z; w[4 * v + 3] = t.w;
       }
 #pragma unroll

@@ -15,12 +15,7 @@ namespace {
 constexpr int kBlock = 256;
 
 // every activation / gradient tensor here is read exactly once by these kernels: non-temporal loads keep them from pushing
-// the just-written outputs (which the next convolution reads at once) out of L2 / Infinity Cache
-typedef float fx4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4_nt(const float* p) {
-  const fx4 v = __builtin_nontemporal_load(reinterpret_cast<const fx4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
+// the just-written outputs (which the next convolution reads at once) out of L2 / Infinity Cache (ld4_nt, xai_common.h)
 
 __device__ __forceinline__ float inv_std(float var, float eps, int variant) {
   return (variant & 1) ? rsqrtf(var + eps) : 1.f / sqrtf(var + eps);
@@ -143,7 +138,7 @@ XAI_EXPORT int xai_bn_act_fwd_f32(const float* x, const float* identity, const f
   }
   const BnParams bn2{weight2, bias2, mean2, var2, eps2};
   const int64_t n = static_cast<int64_t>(N) * C * HW;
-  const bool vec = HW % 4 == 0 && xai_aligned16(x) && xai_aligned16(y) && (identity == nullptr || xai_aligned16(identity));
+  const bool vec = xai_can_vec4(HW, {x, y, identity});
   const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * (vec ? 4 : 1)));
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define XAI_BN_FWD(V, A, R) \
@@ -170,8 +165,7 @@ XAI_EXPORT int xai_bn_relu_bwd_f32(const float* gy, const float* gy2, const floa
     XAI_REQUIRE_PTR(g_identity); XAI_REQUIRE_PTR(var2);
   }
   const BnParams bn2{weight2, nullptr, nullptr, var2, eps2};
-  const bool vec = HW % 4 == 0 && xai_aligned16(gy) && xai_aligned16(y) && xai_aligned16(gx) &&
-                   (g_identity == nullptr || xai_aligned16(g_identity)) && (gy2 == nullptr || xai_aligned16(gy2));
+  const bool vec = xai_can_vec4(HW, {gy, y, gx, g_identity, gy2});
   const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * (vec ? 4 : 1)));
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define XAI_BN_BWD(V, A) \
@@ -329,7 +323,7 @@ XAI_EXPORT int xai_bn_relu_fwd_mask_f32(const float* x, const float* identity, c
   }
   const BnParams bn2{weight2, bias2, mean2, var2, eps2};
   const int64_t n = static_cast<int64_t>(N) * C * HW;
-  const bool vec = HW % 4 == 0 && xai_aligned16(x) && xai_aligned16(y) && (identity == nullptr || xai_aligned16(identity));
+  const bool vec = xai_can_vec4(HW, {x, y, identity});
   const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * 4));
   hipStream_t st = static_cast<hipStream_t>(stream);
   uint64_t* mk = static_cast<uint64_t*>(mask);
@@ -356,8 +350,7 @@ static int bn_relu_bwd_mask_launch(const float* gy, const float* gy2, const void
     XAI_REQUIRE_PTR(g_identity); XAI_REQUIRE_PTR(var2);
   }
   const BnParams bn2{weight2, nullptr, nullptr, var2, eps2};
-  const bool vec = HW % 4 == 0 && xai_aligned16(gy) && xai_aligned16(gx) && (g_identity == nullptr || xai_aligned16(g_identity)) &&
-                   (gy2 == nullptr || xai_aligned16(gy2));
+  const bool vec = xai_can_vec4(HW, {gy, gx, g_identity, gy2});
   const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * 4));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint64_t* mk = static_cast<const uint64_t*>(mask);

@@ -218,7 +218,7 @@ XAI_EXPORT int xai_guided_map_f32(const float* grad, const float* cam, int B, in
   XAI_REQUIRE(attr != nullptr || map != nullptr, XAI_E_NULL);
   XAI_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, XAI_E_SHAPE);
   XAI_REQUIRE(cam == nullptr || (h > 0 && w > 0), XAI_E_SHAPE);
-  const bool vec = W % 4 == 0 && xai_aligned16(grad) && (attr == nullptr || xai_aligned16(attr)) && (map == nullptr || xai_aligned16(map));
+  const bool vec = xai_can_vec4(W, {grad, attr, map});
   const int64_t n_units = static_cast<int64_t>(B) * H * (W / (vec ? 4 : 1));
   const int64_t blocks = xai_ceil_div(n_units, 256);
   XAI_REQUIRE(blocks <= INT32_MAX, XAI_E_UNSUPPORTED);

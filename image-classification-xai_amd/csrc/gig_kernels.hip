@@ -34,32 +34,6 @@ constexpr int64_t kMaxElems = int64_t{1} << 24;   // torch.quantile's own limit;
 
 enum : int32_t { kOk = 0, kNanKey = 1, kCap = 2, kGamma = 3, kSteps = 4 };
 
-template <int V>
-struct Pack {
-  float v[V];
-};
-
-template <int V>
-__device__ __forceinline__ Pack<V> ldp(const float* p) {
-  Pack<V> r;
-  if constexpr (V == 4) {
-    const float4 t = ld4(p);
-    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ void stp(float* p, const Pack<V>& a) {
-  if constexpr (V == 4) {
-    st4(p, make_float4(a.v[0], a.v[1], a.v[2], a.v[3]));
-  } else {
-    *p = a.v[0];
-  }
-}
-
 // x after the clamp of :249-253, and x_max (translate_alpha_to_x, :183).  torch rounds every operation to fp32 and
 // compares with the fp32 value of a python-float scalar; -ffp-contract=off keeps a*b+c two roundings.
 __device__ __forceinline__ float clamped_x(float x, float xi, float xb, float amin, float amax, float& xmax) {
@@ -74,49 +48,6 @@ __device__ __forceinline__ float clamped_x(float x, float xi, float xb, float am
 __device__ __forceinline__ uint32_t sel_key(float xc, float xmax, float g) {
   const uint32_t b = __float_as_uint(g);
   return xc == xmax ? kOutKey : (b << 1) | (b >> 31);          // +x and -x are neighbours: 2k and 2k + 1
-}
-
-// Sum over the workgroup of one fp64 value per lane, in one fixed order; every lane gets the same bits.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);                          // xor butterfly: a+b on both partners, so all lanes agree
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
-
-// Digit d of `hist` with count(< d) <= k < count(<= d); k becomes the rank inside that digit.  Lane t owns bins 2t, 2t+1.
-__device__ __forceinline__ uint32_t find_digit(const uint32_t* hist, uint32_t& k, uint32_t* wsum, uint32_t* pick) {
-  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-  const uint32_t c0 = hist[2 * t], c1 = hist[2 * t + 1], c = c0 + c1;
-  uint32_t incl = c;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const uint32_t up = __shfl_up(incl, off, kWave);
-    if (lane >= off) incl += up;
-  }
-  if (lane == kWave - 1) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t pre = incl - c;
-  for (int w = 0; w < wave; ++w) pre += wsum[w];
-  if (k >= pre && k < pre + c0) {
-    pick[0] = 2 * t; pick[1] = k - pre;
-  } else if (k >= pre + c0 && k < pre + c) {
-    pick[0] = 2 * t + 1; pick[1] = k - pre - c0;
-  }
-  __syncthreads();
-  const uint32_t d = pick[0];
-  k = pick[1];
-  __syncthreads();
-  return d;
-}
-
-__device__ __forceinline__ void zero_hist(uint32_t* hist) {
-  hist[2 * threadIdx.x] = 0u;
-  hist[2 * threadIdx.x + 1] = 0u;
 }
 
 // Python's math.isclose(a, b, rel_tol=1e-9, abs_tol=1e-9) on the fp32 values, in double (:258)
@@ -148,7 +79,7 @@ __global__ __launch_bounds__(kThreads) void gig_init_kernel(const float* __restr
     stp<V>(x_all + off + i, b);
     stp<V>(attr_all + off + i, z);
   }
-  const double tot = block_sum(s, red);
+  const double tot = block_sum<kWaves>(s, red);
   if (threadIdx.x == 0) {
     l1_total[blockIdx.x] = static_cast<float>(tot);
     int32_t* st = state + 4 * blockIdx.x;
@@ -197,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
   int selections = 0;
   for (;;) {
     // ---- A: clamp, l1_current, top digit
-    zero_hist(hist);
+    select_zero_hist(hist);
     if (tid == 0) nan_seen = 0u;
     __syncthreads();
     double s = 0.0;
@@ -213,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
         else atomicAdd(&hist[key >> 21], 1u);
       }
     }
-    const float l1_current = static_cast<float>(block_sum(s, red));   // (block_sum synchronises: hist and nan_seen are complete)
+    const float l1_current = static_cast<float>(block_sum<kWaves>(s, red));   // (block_sum synchronises: hist and nan_seen are complete)
     const bool close = py_isclose(l1_target, l1_current);
     if (!close) {
       int32_t err = kOk;
@@ -230,8 +161,8 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
       ++selections;
       // ---- B, C: radix select of the key of rank `rank`
       uint32_t k = rank;
-      const uint32_t d1 = find_digit(hist, k, wsum, pick);
-      zero_hist(hist);
+      const uint32_t d1 = select_digit<kThreads>(hist, k, wsum, pick);
+      select_zero_hist(hist);
       __syncthreads();
       for (int64_t i = i0; i < N; i += di) {
         const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
@@ -244,9 +175,9 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
         }
       }
       __syncthreads();
-      const uint32_t d2 = find_digit(hist, k, wsum, pick);
+      const uint32_t d2 = select_digit<kThreads>(hist, k, wsum, pick);
       const uint32_t hi = (d1 << 11) | d2;
-      zero_hist(hist);
+      select_zero_hist(hist);
       __syncthreads();
       for (int64_t i = i0; i < N; i += di) {
         const Pack<V> px = ldp<V>(x + i), pi = ldp<V>(xin + i), pb = ldp<V>(xb + i), pg = ldp<V>(g + i);
@@ -259,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
         }
       }
       __syncthreads();
-      thr = (hi << 10) | find_digit(hist, k, wsum, pick) | 1u;   // | 1: |grad| <= threshold takes -x with +x
+      thr = (hi << 10) | select_digit<kThreads>(hist, k, wsum, pick) | 1u;   // | 1: |grad| <= threshold takes -x with +x
       // ---- D: l1_s = sum |x - x_max| over the selection s = |grad| <= threshold && grad != inf (:268, :272)
       s = 0.0;
       for (int64_t i = i0; i < N; i += di) {
@@ -272,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
           if (key <= thr && key != kOutKey) s += static_cast<double>(fabsf(xc - xmax));
         }
       }
-      const float l1_s = static_cast<float>(block_sum(s, red));
+      const float l1_s = static_cast<float>(block_sum<kWaves>(s, red));
       gamma = l1_s > 0.f ? (l1_current - l1_target) / l1_s : __builtin_inff();    // :277-280
       if (!(gamma > 1.f) && !(gamma > 0.f)) {                                      // the reference's assert (:287)
         if (tid == 0) { st[1] = kGamma; st[2] = selections; st[3] = step; }
@@ -304,10 +235,6 @@ __global__ __launch_bounds__(kThreads) void gig_step_kernel(const float* __restr
   if (tid == 0) { st[0] = step + 1; st[2] = selections; }
 }
 
-bool vec4_ok(int64_t N, const void* a, const void* b, const void* c, const void* d, const void* e) {
-  return N % 4 == 0 && xai_aligned16(a) && xai_aligned16(b) && xai_aligned16(c) && xai_aligned16(d) && xai_aligned16(e);
-}
-
 }  // namespace
 
 XAI_EXPORT int xai_gig_init_f32(const float* x_input, const float* x_baseline, int n_img, int64_t n_elem, float* x, float* attr,
@@ -317,7 +244,7 @@ XAI_EXPORT int xai_gig_init_f32(const float* x_input, const float* x_baseline, i
   XAI_REQUIRE(n_img > 0 && n_elem > 0, XAI_E_SHAPE);
   XAI_REQUIRE(n_img <= 65535 && n_elem <= kMaxElems, XAI_E_UNSUPPORTED);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec4_ok(n_elem, x_input, x_baseline, x, attr, x))
+  if (xai_can_vec4(n_elem, {x_input, x_baseline, x, attr}))
     hipLaunchKernelGGL(gig_init_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
   else
     hipLaunchKernelGGL(gig_init_kernel<1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
@@ -337,7 +264,7 @@ XAI_EXPORT int xai_gig_step_f32(const float* x_input, const float* x_baseline, c
   const float r = fraction * static_cast<float>(n_elem - 1);
   const uint32_t rank = static_cast<uint32_t>(floorf(r));
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec4_ok(n_elem, x_input, x_baseline, grad, x, attr))
+  if (xai_can_vec4(n_elem, {x_input, x_baseline, grad, x, attr}))
     hipLaunchKernelGGL(gig_step_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, grad, n_elem, steps, max_dist, rank, x,
                        attr, l1_total, state);
   else

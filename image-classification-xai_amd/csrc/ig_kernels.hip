@@ -21,29 +21,22 @@ namespace {
 constexpr int kBlock = 256;
 
 // ---- tiny vector algebra so that every kernel exists in a float4 and a scalar flavour ----
+// (load_nt / store_nt: for streamed-once data, see ld4_nt in xai_common.h)
 template <int W> struct Vec;
-typedef float fx4 __attribute__((ext_vector_type(4)));
 template <> struct Vec<4> {
   using T = float4;
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  // streamed-once data: non-temporal (nt) load, does not displace x/out lines in L2 / Infinity Cache
-  static __device__ __forceinline__ T load_nt(const float* p) {
-    const fx4 v = __builtin_nontemporal_load(reinterpret_cast<const fx4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-  }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
-  static __device__ __forceinline__ void store_nt(float* p, T v) {
-    const fx4 t = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<fx4*>(p));
-  }
+  static __device__ __forceinline__ T load(const float* p) { return ld4(p); }
+  static __device__ __forceinline__ T load_nt(const float* p) { return ld4_nt(p); }
+  static __device__ __forceinline__ void store(float* p, T v) { st4(p, v); }
+  static __device__ __forceinline__ void store_nt(float* p, T v) { st4_nt(p, v); }
   static __device__ __forceinline__ T splat(float s) { return make_float4(s, s, s, s); }
 };
 template <> struct Vec<1> {
   using T = float;
   static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ T load_nt(const float* p) { return __builtin_nontemporal_load(p); }
+  static __device__ __forceinline__ T load_nt(const float* p) { return ld_nt(p); }
   static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-  static __device__ __forceinline__ void store_nt(float* p, T v) { __builtin_nontemporal_store(v, p); }
+  static __device__ __forceinline__ void store_nt(float* p, T v) { st_nt(p, v); }
   static __device__ __forceinline__ T splat(float s) { return s; }
 };
 __device__ __forceinline__ float4 vadd(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
@@ -95,8 +88,7 @@ __global__ __launch_bounds__(kWave) void ig_cutoff_kernel(const float* __restric
   int first = INT32_MAX;
   for (int s = lane; s < n_steps; s += kWave)
     if (lg[s] > thr) { first = s; break; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, kWave));
+  first = wave_min(first);
   if (lane == 0) {
     int cut = (first == INT32_MAX) ? 1 : first;   // nothing above the threshold -> 1
     if (cut == 0) cut = 1;                        // "avoid rare case where no attribution is returned"
@@ -292,15 +284,12 @@ __global__ __launch_bounds__(BLOCK) void ig_accum_stream_kernel(const float* __r
 // 60 MB copy vs 155 us after an nt-store copy -- tune/tune_copy_then_accum.hip).
 __global__ __launch_bounds__(kBlock) void store_stream_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n4) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-  const fx4* s4 = reinterpret_cast<const fx4*>(src);
-  fx4* d4 = reinterpret_cast<fx4*>(dst);
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n4; i += stride)
-    __builtin_nontemporal_store(s4[i], d4 + i);
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n4; i += stride) st4_nt(dst + 4 * i, ld4(src + 4 * i));
 }
 __global__ __launch_bounds__(kBlock) void store_stream_scalar_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride)
-    __builtin_nontemporal_store(src[i], dst + i);
+    st_nt(dst + i, src[i]);
 }
 
 // streaming form: acc += sum over the batch rows
@@ -364,14 +353,8 @@ __global__ __launch_bounds__(1024) void sumsq_kernel(const float* __restrict__ g
   } else {
     for (int64_t i = threadIdx.x; i < n_elem; i += 1024) acc += row[i] * row[i];
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float v = threadIdx.x < 16 ? part[threadIdx.x] : 0.f;
-    v = wave_sum(v);
-    if (threadIdx.x == 0) out[blockIdx.x] = v;
-  }
+  acc = block_sum_lane0<16>(acc, part);
+  if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
 template <int W>
@@ -391,13 +374,6 @@ __global__ __launch_bounds__(kBlock) void idgi_accum_kernel(const float* __restr
   V::store(out + e, acc);
 }
 
-inline bool can_vec4(int64_t n, std::initializer_list<const void*> ptrs) {
-  if (n & 3) return false;
-  for (const void* p : ptrs)
-    if (p && !xai_aligned16(p)) return false;
-  return true;
-}
-
 }  // namespace
 
 // ============================================================================== C ABI
@@ -410,7 +386,7 @@ XAI_EXPORT int xai_ig_interp_f32(const float* x, const float* baseline, float ba
   hipStream_t st = static_cast<hipStream_t>(stream);
   // two step rows per lane: on this part HBM writes like MANY concurrent row streams (5.98 TB/s at 2 rows per
   // lane vs 5.42 TB/s at 50, tune/tune_write.hip); x and b re-reads hit L2
-  const bool vec = can_vec4(n_elem, {x, baseline, out});
+  const bool vec = xai_can_vec4(n_elem, {x, baseline, out});
   const int64_t tiles = xai_ceil_div(n_elem, kBlock * (vec ? 4 : 1));
   int per, chunks;
   const bool hbm_sized = static_cast<int64_t>(n_img) * n_alpha * n_elem * 4 >= (int64_t(256) << 20);
@@ -452,7 +428,7 @@ static int ig_accum_impl(const float* grads, int n_img, int n_steps, const int32
   XAI_REQUIRE(step_w1 != nullptr || step_w2 == nullptr, XAI_E_SHAPE);
   XAI_REQUIRE(n_img <= 65535, XAI_E_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = can_vec4(hw, {grads, x, baseline, out_chw, out_abs_hw});
+  const bool vec = xai_can_vec4(hw, {grads, x, baseline, out_chw, out_abs_hw});
   if (vec && (C == 3 || C == 1)) {
     // step-outer balanced mapping.  Big problems: 2 workgroups of 256 lanes per CU, 4 items per lane
     // and round; small ones: one wave per 64 items so that a single image still spreads over the chip.
@@ -508,7 +484,7 @@ XAI_EXPORT int xai_ig_store_grads_f32(const float* src, float* dst, int64_t n_el
   XAI_REQUIRE(n_elem > 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = static_cast<unsigned>(xai_cu_count() * 8);
-  if (can_vec4(n_elem, {src, dst}))
+  if (xai_can_vec4(n_elem, {src, dst}))
     hipLaunchKernelGGL(store_stream_kernel, dim3(grid), dim3(kBlock), 0, st, src, dst, n_elem / 4);
   else
     hipLaunchKernelGGL(store_stream_scalar_kernel, dim3(grid), dim3(kBlock), 0, st, src, dst, n_elem);
@@ -519,7 +495,7 @@ XAI_EXPORT int xai_ig_accum_add_f32(const float* grads, int n_batch, float* acc,
   XAI_REQUIRE_PTR(grads); XAI_REQUIRE_PTR(acc);
   XAI_REQUIRE(n_batch > 0 && n_elem > 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = can_vec4(n_elem, {grads, acc});
+  const bool vec = xai_can_vec4(n_elem, {grads, acc});
   dim3 grid(static_cast<unsigned>(xai_ceil_div(n_elem, kBlock * (vec ? 4 : 1))));
   if (vec) hipLaunchKernelGGL(ig_accum_add_kernel<4>, grid, dim3(kBlock), 0, st, grads, n_batch, acc, n_elem);
   else     hipLaunchKernelGGL(ig_accum_add_kernel<1>, grid, dim3(kBlock), 0, st, grads, n_batch, acc, n_elem);
@@ -533,7 +509,7 @@ XAI_EXPORT int xai_ig_finish_f32(const float* acc, int n_img, int n_steps, const
   XAI_REQUIRE(n_img > 0 && n_steps > 0 && C > 0 && hw > 0, XAI_E_SHAPE);
   XAI_REQUIRE(n_img <= 65535, XAI_E_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = can_vec4(hw, {acc, x, baseline, out_chw, out_abs_hw});
+  const bool vec = xai_can_vec4(hw, {acc, x, baseline, out_chw, out_abs_hw});
   dim3 grid(static_cast<unsigned>(xai_ceil_div(hw, kBlock * (vec ? 4 : 1))), n_img);
   if (vec) hipLaunchKernelGGL(ig_finish_kernel<4>, grid, dim3(kBlock), 0, st, acc, n_steps, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw);
   else     hipLaunchKernelGGL(ig_finish_kernel<1>, grid, dim3(kBlock), 0, st, acc, n_steps, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw);
@@ -552,7 +528,7 @@ XAI_EXPORT int xai_idgi_accum_f32(const float* grads, int n_steps, const float* 
   XAI_REQUIRE_PTR(grads); XAI_REQUIRE_PTR(logits); XAI_REQUIRE_PTR(sumsq); XAI_REQUIRE_PTR(out);
   XAI_REQUIRE(n_steps > 1 && n_elem > 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = can_vec4(n_elem, {grads, out});
+  const bool vec = xai_can_vec4(n_elem, {grads, out});
   dim3 grid(static_cast<unsigned>(xai_ceil_div(n_elem, kBlock * (vec ? 4 : 1))));
   if (vec) hipLaunchKernelGGL(idgi_accum_kernel<4>, grid, dim3(kBlock), 0, st, grads, n_steps, logits, sumsq, n_elem, out);
   else     hipLaunchKernelGGL(idgi_accum_kernel<1>, grid, dim3(kBlock), 0, st, grads, n_steps, logits, sumsq, n_elem, out);

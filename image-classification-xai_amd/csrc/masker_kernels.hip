@@ -20,33 +20,8 @@ constexpr int kMaxSrc = 4096;       // h*w floats of one feature map held in LDS
 constexpr int kMaxStretch = 8192;   // h*W floats of its horizontally stretched copy (dynamic LDS, 32 KB)
 constexpr int kMaxTaps = 1024;      // H vertical taps of 16 B behind it (16 KB): 64 KB per workgroup with `s`
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
-// min / max over the workgroup; every lane gets the result.  `red` holds 2 * waves floats.
-__device__ __forceinline__ void block_min_max(float& lo, float& hi, float* red) {
-  lo = wave_min(lo);
-  hi = wave_max(hi);
-  const int wave = threadIdx.x >> 6, n_waves = kBlock >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    red[wave] = lo;
-    red[n_waves + wave] = hi;
-  }
-  __syncthreads();
-  lo = red[0];
-  hi = red[n_waves];
-  for (int i = 1; i < n_waves; ++i) {
-    lo = fminf(lo, red[i]);
-    hi = fmaxf(hi, red[n_waves + i]);
-  }
-}
-
-// NaN-propagating variants are not needed: the reference's torch.min / torch.max propagate NaN, fminf / fmaxf drop it;
-// feature maps and cluster sums are finite, and a NaN row would stay NaN in the reference only.
+// NaN-propagating variants of block_min_max are not needed: the reference's torch.min / torch.max propagate NaN, fminf / fmaxf
+// drop it; feature maps and cluster sums are finite, and a NaN row would stay NaN in the reference only.
 
 struct Tap {
   int i0, i1;
@@ -114,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void up_rownorm_kernel(const float* __restr
       oy += d_row; c += d_col;
       if (c >= W4) { c -= W4; ++oy; }
     }
-    block_min_max(lo, hi, red);
+    block_min_max<kBlock / kWave>(lo, hi, red);
     const float span = hi - lo, y = 1.f / span;
     oy = threadIdx.x / W4; c = threadIdx.x % W4;
 #pragma unroll 2
@@ -141,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void up_rownorm_kernel(const float* __restr
         hi = fmaxf(hi, v);
       }
     }
-    block_min_max(lo, hi, red);
+    block_min_max<kBlock / kWave>(lo, hi, red);
     const float span = hi - lo, y = 1.f / span;
     for (int oy = 0; oy < H; ++oy) {
       const float4 t = taps[oy];
@@ -183,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void rownorm_kernel(const float* __restrict
       hi = fmaxf(hi, v);
     }
   }
-  block_min_max(lo, hi, red);
+  block_min_max<kBlock / kWave>(lo, hi, red);
   const float span = hi - lo;
   float* dst = out + static_cast<int64_t>(r) * P;
   // `out` may alias `x`: all reads of the scan above are complete for THIS workgroup, but a neighbour slice may still be
@@ -239,7 +214,7 @@ __global__ __launch_bounds__(kBlock) void causal_apply_kernel(const float* __res
   const float inv = 1.f - m;
   for (int c = 0; c < C; ++c) {
     const int64_t e = (static_cast<int64_t>(n) * C + c) * HW + p;
-    const float add = (__builtin_nontemporal_load(noise + e) * noise_scale) * inv;
+    const float add = (ld_nt(noise + e) * noise_scale) * inv;
     const float xv = x[static_cast<int64_t>(c) * HW + p];
     stack[e] = xv * m + add;
     stack[static_cast<int64_t>(N) * C * HW + e] = xv + add;
@@ -247,7 +222,6 @@ __global__ __launch_bounds__(kBlock) void causal_apply_kernel(const float* __res
 }
 
 // the same, 4 pixels per lane (HW % 4 == 0, 16-byte aligned planes): 16-byte loads and stores, identical per-element arithmetic
-typedef float masker_f4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(kBlock) void causal_apply_kernel_v4(const float* __restrict__ x, const float* __restrict__ masks,
                                                                  const float* __restrict__ noise, int N, int C, int64_t HW,
                                                                  float noise_scale, float* __restrict__ stack) {
@@ -258,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void causal_apply_kernel_v4(const float* __
   const float4 inv = make_float4(1.f - m.x, 1.f - m.y, 1.f - m.z, 1.f - m.w);
   for (int c = 0; c < C; ++c) {
     const int64_t e = (static_cast<int64_t>(n) * C + c) * HW + p;
-    const masker_f4 nz = __builtin_nontemporal_load(reinterpret_cast<const masker_f4*>(noise + e));
+    const float4 nz = ld4_nt(noise + e);
     const float4 add = make_float4((nz.x * noise_scale) * inv.x, (nz.y * noise_scale) * inv.y, (nz.z * noise_scale) * inv.z, (nz.w * noise_scale) * inv.w);
     const float4 xv = ld4(x + static_cast<int64_t>(c) * HW + p);
     st4(stack + e, make_float4(xv.x * m.x + add.x, xv.y * m.y + add.y, xv.z * m.z + add.z, xv.w * m.w + add.w));
@@ -322,7 +296,7 @@ XAI_EXPORT int xai_masked_sums_f32(const float* rows, const float* weights, int 
                                    xai_stream_t stream) {
   XAI_REQUIRE_PTR(rows); XAI_REQUIRE_PTR(weights); XAI_REQUIRE_PTR(out_weighted); XAI_REQUIRE_PTR(out_plain);
   XAI_REQUIRE(N > 0 && P > 0, XAI_E_SHAPE);
-  if (P % 4 == 0 && xai_aligned16(rows)) {
+  if (xai_can_vec4(P, {rows})) {
     hipLaunchKernelGGL(masked_sums_kernel<4>, dim3(static_cast<unsigned>(xai_ceil_div(P, kBlock * 4))), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), rows, weights, N, P, out_weighted, out_plain);
   } else {
@@ -339,7 +313,7 @@ XAI_EXPORT int xai_up_rownorm_f32(const float* src, int R, int h, int w, int H, 
               static_cast<int64_t>(h) * W <= kMaxStretch, XAI_E_UNSUPPORTED);
   XAI_REQUIRE(H <= kMaxTaps, XAI_E_UNSUPPORTED);
   const size_t lds = (static_cast<size_t>((h * W + 3) & ~3) + 4 * static_cast<size_t>(H)) * sizeof(float);
-  if (W % 4 == 0 && xai_aligned16(out))
+  if (xai_can_vec4(W, {out}))
     hipLaunchKernelGGL(up_rownorm_kernel<true>, dim3(R), dim3(kBlock), lds, static_cast<hipStream_t>(stream), src, h, w, H, W, out);
   else
     hipLaunchKernelGGL(up_rownorm_kernel<false>, dim3(R), dim3(kBlock), lds, static_cast<hipStream_t>(stream), src, h, w, H, W, out);
@@ -359,7 +333,7 @@ XAI_EXPORT int xai_rownorm_f32(const float* x, int R, int64_t P, float* out, xai
     if (slices > 32) slices = 32;
   }
   const unsigned grid = static_cast<unsigned>(kXcds * slices * xai_ceil_div(R, kXcds));
-  if (P % 4 == 0 && xai_aligned16(x) && xai_aligned16(out))
+  if (xai_can_vec4(P, {x, out}))
     hipLaunchKernelGGL(rownorm_kernel<true>, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, R, P, slices, out);
   else
     hipLaunchKernelGGL(rownorm_kernel<false>, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, R, P, slices, out);
@@ -371,7 +345,7 @@ XAI_EXPORT int xai_cluster_sum_f32(const float* rows, const int32_t* members, co
   XAI_REQUIRE_PTR(rows); XAI_REQUIRE_PTR(members); XAI_REQUIRE_PTR(offs); XAI_REQUIRE_PTR(out);
   XAI_REQUIRE(K > 0 && P > 0, XAI_E_SHAPE);
   XAI_REQUIRE(K <= 65535, XAI_E_UNSUPPORTED);
-  const bool vec = (P % 4 == 0) && xai_aligned16(rows) && xai_aligned16(out);
+  const bool vec = xai_can_vec4(P, {rows, out});
   if (vec) {
     dim3 grid(static_cast<unsigned>(xai_ceil_div(P / 4, kBlock)), K);
     hipLaunchKernelGGL(cluster_sum_kernel<true>, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), rows, members, offs, P, out);
@@ -387,7 +361,7 @@ XAI_EXPORT int xai_causal_apply_f32(const float* x, const float* masks, const fl
   XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(masks); XAI_REQUIRE_PTR(noise); XAI_REQUIRE_PTR(stack);
   XAI_REQUIRE(N > 0 && C > 0 && HW > 0, XAI_E_SHAPE);
   XAI_REQUIRE(N <= 65535, XAI_E_UNSUPPORTED);
-  if (HW % 4 == 0 && xai_aligned16(x) && xai_aligned16(masks) && xai_aligned16(noise) && xai_aligned16(stack)) {
+  if (xai_can_vec4(HW, {x, masks, noise, stack})) {
     dim3 grid(static_cast<unsigned>(xai_ceil_div(HW, kBlock * 4)), N);
     hipLaunchKernelGGL(causal_apply_kernel_v4, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, masks, noise, N, C, HW,
                        noise_scale, stack);

@@ -61,14 +61,8 @@ __global__ __launch_bounds__(1024) void segment_sums_kernel(const float* __restr
   if (static_cast<int>(blockIdx.x) == (n_steps + 15) / 16) {   // the "total" block
     float acc = 0.f;
     for (int64_t i = threadIdx.x; i < hw; i += 1024) acc += sal[i];
-    acc = wave_sum(acc);
-    if (lane == 0) part[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      float v = threadIdx.x < 16 ? part[threadIdx.x] : 0.f;
-      v = wave_sum(v);
-      if (threadIdx.x == 0) *total = v;
-    }
+    acc = block_sum_lane0<16>(acc, part);
+    if (threadIdx.x == 0) *total = acc;
     return;
   }
   const int t = blockIdx.x * 16 + wave;
@@ -84,14 +78,6 @@ __global__ __launch_bounds__(1024) void segment_sums_kernel(const float* __restr
   if (lane == 0) seg[t] = acc;
 }
 
-// argmax order: NaN beats every number (torch.max propagates NaN), ties go to the lower index.
-__device__ __forceinline__ bool beats(float v, int i, float m, int mi) {
-  const bool vn = v != v, mn = m != m;
-  if (vn != mn) return vn;
-  if (vn) return i < mi;
-  return v > m || (v == m && i < mi);
-}
-
 // One wave per row of logits.
 __global__ __launch_bounds__(kBlock) void softmax_stats_kernel(const float* __restrict__ logits, int B, int K,
                                                                const int32_t* __restrict__ target_dev, int target_host,
@@ -101,18 +87,9 @@ __global__ __launch_bounds__(kBlock) void softmax_stats_kernel(const float* __re
   if (row >= B) return;
   const int lane = threadIdx.x & 63;
   const float* z = logits + static_cast<int64_t>(row) * K;
-  float m = -INFINITY;
-  int mi = INT32_MAX;
-  for (int k = lane; k < K; k += kWave) {
-    const float v = z[k];
-    if (beats(v, k, m, mi)) { m = v; mi = k; }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, kWave);
-    const int oi = __shfl_xor(mi, off, kWave);
-    if (beats(om, oi, m, mi)) { m = om; mi = oi; }
-  }
+  const ArgMax top = wave_argmax(z, K);                // a NaN is the maximum, as torch.max propagates it
+  const float m = top.v;
+  const int mi = top.i;
   float sum = 0.f;
   for (int k = lane; k < K; k += kWave) sum += expf(z[k] - m);
   sum = wave_sum(sum);
@@ -149,7 +126,7 @@ XAI_EXPORT int xai_perturb_batch_f32(const float* start, const float* finish, co
   XAI_REQUIRE_PTR(start); XAI_REQUIRE_PTR(finish); XAI_REQUIRE_PTR(flip_step); XAI_REQUIRE_PTR(out);
   XAI_REQUIRE(C > 0 && hw > 0 && n_batch > 0 && first_step >= 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = (hw % 4 == 0) && xai_aligned16(start) && xai_aligned16(finish) && xai_aligned16(flip_step) && xai_aligned16(out);
+  const bool vec = xai_can_vec4(hw, {start, finish, flip_step, out});
   const int64_t tiles = xai_ceil_div(hw, kBlock * (vec ? 4 : 1));
   int per, chunks, zdim = 1;
   if (static_cast<int64_t>(n_batch) * C * hw * 4 >= (int64_t(64) << 20) && C <= 64) {

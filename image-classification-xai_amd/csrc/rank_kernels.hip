@@ -112,12 +112,7 @@ __global__ __launch_bounds__(kBins) void rank_scan_kernel(int64_t hw, int n_tile
     for (int u = 0; u < 8; ++u) total += c[u];
   }
   for (; t < n_tiles; ++t) total += hist[t * kBins + d];
-  uint32_t incl = total;                                  // exclusive scan of the 256 digit totals
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t up = __shfl_up(incl, off, kWave);
-    if (lane >= off) incl += up;
-  }
+  const uint32_t incl = wave_scan_incl(total);            // exclusive scan of the 256 digit totals
   if (lane == 63) wsum[wave] = incl;
   const bool one_bin = __any(total == static_cast<uint32_t>(hw));
   __syncthreads();

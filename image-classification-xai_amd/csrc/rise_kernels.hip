@@ -141,9 +141,8 @@ __device__ __forceinline__ float blend8(uint2 rows, const Tap& r, const Tap& c, 
 
 // NT: non-temporal stores for batches that cannot stay cache-resident anyway (see xai_rise_apply_f32); C3: the usual
 // three channels -- the lane's three image quads are loaded before the mask arithmetic, so their latency hides behind it.
-typedef float rise_f4 __attribute__((ext_vector_type(4)));
 template <bool NT> __device__ __forceinline__ void rise_store(float* p, float4 v) {
-  if (NT) { const rise_f4 t = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t, reinterpret_cast<rise_f4*>(p)); }
+  if (NT) st4_nt(p, v);
   else st4(p, v);
 }
 
@@ -296,7 +295,7 @@ XAI_EXPORT int xai_rise_apply_f32(const uint8_t* grid, const int32_t* shift, int
   const int64_t hw = static_cast<int64_t>(H) * W;
   XAI_REQUIRE(hw < (int64_t(1) << 31), XAI_E_UNSUPPORTED);
   const double rh = static_cast<double>(s) / static_cast<double>((s + 1) * cell_h), rw = static_cast<double>(s) / static_cast<double>((s + 1) * cell_w);
-  const bool vec = (W % 4 == 0) && xai_aligned16(image) && xai_aligned16(masked_out) && xai_aligned16(masks_out);
+  const bool vec = xai_can_vec4(W, {image, masked_out, masks_out});
   if (vec && s == 8 && (reinterpret_cast<uintptr_t>(grid) & 7u) == 0) {
     dim3 g(static_cast<unsigned>(xai_ceil_div(hw, kBlock * 4)), n_masks);
     // Store policy by what the classifier will find: a batch that fits the 256 MiB Infinity Cache with room to spare is

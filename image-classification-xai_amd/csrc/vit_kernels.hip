@@ -195,8 +195,7 @@ __global__ __launch_bounds__(256) void residual_shares_kernel(const float* const
 constexpr int kCamThreads = 1024;
 __global__ __launch_bounds__(kCamThreads) void attn_cam_kernel(const float* __restrict__ attn, const float* __restrict__ grad, int H, int S,
                                                                float* __restrict__ out) {
-  __shared__ float red_lo[kCamThreads / kWave], red_hi[kCamThreads / kWave];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __shared__ float red[2 * (kCamThreads / kWave)];
   const int P = S - 1;
   const int64_t plane = static_cast<int64_t>(S) * S;
   const float* A = attn + static_cast<int64_t>(blockIdx.x) * H * plane;
@@ -211,15 +210,7 @@ __global__ __launch_bounds__(kCamThreads) void attn_cam_kernel(const float* __re
     lo = fminf(lo, c);
     hi = fmaxf(hi, c);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, off, kWave));
-    hi = fmaxf(hi, __shfl_xor(hi, off, kWave));
-  }
-  if (lane == 0) { red_lo[wave] = lo; red_hi[wave] = hi; }
-  __syncthreads();
-  lo = red_lo[0]; hi = red_hi[0];
-  for (int w = 1; w < kCamThreads / kWave; ++w) { lo = fminf(lo, red_lo[w]); hi = fmaxf(hi, red_hi[w]); }
+  block_min_max<kCamThreads / kWave>(lo, hi, red);
   for (int p = threadIdx.x; p < P; p += blockDim.x) o[p] = (o[p] - lo) / (hi - lo);   // constant map: 0/0 = NaN, as the reference
 }
 

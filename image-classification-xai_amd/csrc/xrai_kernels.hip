@@ -27,12 +27,6 @@ constexpr int kMaxWords = 4096;                      // 32 KiB of LDS for `curre
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // bits [lo, hi] (inclusive, flat pixel indices of one row) of plane `dst`
 __device__ __forceinline__ void or_run(u64* dst, int64_t lo, int64_t hi) {
   for (int64_t w = lo >> 6; w <= (hi >> 6); ++w) {
@@ -96,11 +90,8 @@ __global__ __launch_bounds__(kPackBlock) void span_kernel(const u64* __restrict_
       lo = min(lo, w);
       hi = max(hi, w);
     }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = min(lo, __shfl_xor(lo, off, kWave));
-    hi = max(hi, __shfl_xor(hi, off, kWave));
-  }
+  lo = wave_min(lo);
+  hi = wave_max(hi);
   if (lane == 0) {
     span[2 * m] = lo;
     span[2 * m + 1] = hi;
@@ -120,7 +111,7 @@ struct Plane {
 __device__ __forceinline__ int diff_count(const Plane& pl, const u64* __restrict__ mask, const u64* cur, int w0, int w1, int lane) {
   int c = 0;
   for (int w = w0 + lane; w <= w1; w += kWave) c += __popcll(pl.word(mask, w) & ~cur[w]);
-  return wave_sum_i(c);
+  return wave_sum(c);
 }
 
 // fp64 sum of attr over mask & ~current, in the fixed order (one wave; every lane returns the total)

@@ -99,7 +99,7 @@ def _maps():
     w2 = rng.standard_normal(7).astype(np.float32)
     w2[3] = np.inf
     out.append(("inf_7", w2))
-    # where the three-pass radix select has to work (the find_digit K22 shares): keys that share their top 22 bits, their top 11
+    # where the three-pass radix select has to work (select_digit, which K22 shares): keys that share their top 22 bits, their top 11
     # bits, and keys on both sides of digit boundaries (powers of two +- 1 ulp); the gradient kinds of tests/gig_edges.py
     gen = np.random.default_rng(22)
     for kind in ("band", "mid_band", "pow2"):

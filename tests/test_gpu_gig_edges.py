@@ -21,7 +21,7 @@ AGAINST = "restatement, fp32 sums"
 
 
 def _view(numel, off):
-    """`numel` floats starting `off` floats into a fresh (256-byte aligned) allocation: off = 1 defeats vec4_ok."""
+    """`numel` floats starting `off` floats into a fresh (256-byte aligned) allocation: off = 1 defeats xai_can_vec4."""
     return torch.zeros(numel + 4, dtype=torch.float32, device=DEV)[off:off + numel]
 
 
@@ -36,7 +36,7 @@ def _same(got, want, what, nan_ok=False):
 
 def drive(case, offs=(0, 0, 0, 0, 0), extra=0):
     """Run the case's launches; offs: float offsets of x_input, x_baseline, grad, x, attr into their allocations (the five
-    pointers vec4_ok looks at).  -> everything the kernel read and wrote, on the host."""
+    pointers xai_can_vec4 looks at).  -> everything the kernel read and wrote, on the host."""
     from xai_engine import kernels as K
     B, n = len(case.images), case.n
     pairs = [case.inputs(i) for i in range(B)]
@@ -168,7 +168,7 @@ def test_k22_full_size_on_the_scalar_path():
 
 @pytest.mark.parametrize("n", [64, 1024])
 def test_each_misaligned_pointer_alone_selects_the_scalar_path_with_identical_results(n):
-    """vec4_ok looks at x_input, x_baseline, grad, x and attr: each of them misaligned alone (and all together) gives the bytes of
+    """xai_can_vec4 looks at x_input, x_baseline, grad, x and attr: each of them misaligned alone (and all together) gives the bytes of
     the aligned run, on a case whose steps take several selections with ties at the threshold."""
     c = E.Case(f"misalign/n{n}", n, 7, 0.25, 0.3, [("grid_eq30", "ties")])
     aligned = drive(c)

@@ -181,7 +181,8 @@ XAI_EXPORT int xai_blur_1d_f32(const float* x, const float* k1d, int klen, int a
 XAI_EXPORT int xai_blur_sep_f32(const float* x, const float* k1d, int klen, int B, int C, int H, int W, float* out,
                                 xai_stream_t stream) {
   XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(k1d); XAI_REQUIRE_PTR(out);
-  XAI_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && klen > 0 && (klen & 1), XAI_E_SHAPE);
+  // in place a workgroup would read halo pixels that its neighbours have already overwritten
+  XAI_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && klen > 0 && (klen & 1) && x != out, XAI_E_SHAPE);
   XAI_REQUIRE(klen <= 63 && static_cast<int64_t>(B) * C <= 65535, XAI_E_UNSUPPORTED);
   const int r = klen / 2;
   // 16-row tiles while that is what it takes to give every CU a couple of workgroups (one image: 168 tiles), 32-row tiles

@@ -189,7 +189,8 @@ int xai_segment_sums_f32(const float* sal, const int32_t* order, int64_t hw, int
 
 /* K7  separable zero-padded blur: out = k1d (x) k1d applied per channel
  * replaces  conv2d(x, gkern(klen, nsig), padding=klen//2) at evaluatePerturbation.py:459
- *   x, out : [B][C][H][W];  k1d : [klen] on the device, klen odd <= 63 */
+ *   x, out : [B][C][H][W];  k1d : [klen] on the device, klen odd <= 63
+ *   Not in place: x == out is refused with XAI_E_SHAPE (a tile's halo belongs to its neighbours' outputs). */
 int xai_blur_sep_f32(const float* x, const float* k1d, int klen, int B, int C, int H, int W,
                      float* out, xai_stream_t stream);
 

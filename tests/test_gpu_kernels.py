@@ -414,6 +414,7 @@ def test_abi_argument_errors(K):
     assert lib.xai_ig_interp_f32(x.data_ptr(), None, 0.0, x.data_ptr(), 0, 0, 1, 4, x.data_ptr(), None) == -2
     assert lib.xai_gradcam_f32(x.data_ptr(), x.data_ptr(), 1, 1, 64, 64, 1, x.data_ptr(), None, 0, None) == -3
     assert lib.xai_blur_sep_f32(x.data_ptr(), x.data_ptr(), 4, 1, 1, 2, 2, x.data_ptr(), None) == -2
+    assert lib.xai_blur_sep_f32(x.data_ptr(), x[4:].data_ptr(), 3, 1, 1, 2, 2, x.data_ptr(), None) == -2                     # x == out
     p = x.data_ptr()
     assert lib.xai_bn_act_fwd_f32(p, None, p, p, p, None, 1e-5, None, None, None, None, 0.0, 9, 1, 1, 2, 4, p, None) == -1     # var missing
     assert lib.xai_bn_act_fwd_f32(p, None, p, p, p, p, 1e-5, None, None, None, None, 0.0, 99, 1, 1, 2, 4, p, None) == -2     # variant

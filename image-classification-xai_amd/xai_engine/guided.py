@@ -16,6 +16,8 @@ A classifier prepared with `prepare.fuse_bn_relu` runs the pass through the guid
 `nn.ReLU` module puts the clamp, in device torch ops, on the gradient of that module's output.  The hook acts only on tensors
 made by the calling thread's forward, so other threads' passes through the same model are untouched.
 
+The hook that records the layer's output, the sum over a forked output's two gradient handles and the Grad-CAM reduction are
+gradcam.py's (`layer_tensor`, `layer_handles` / `sum_handles`, `gradcam_reduce`); the pass itself is this module's.
 The whole pass -- forward, backward, the Grad-CAM reduction and K28 -- runs on static buffers and is replayed from a hipGraph
 once the graph has proven itself on the caller's first real batch (streams.CapturedCall, per host thread).
 
@@ -32,6 +34,7 @@ import torch.nn.functional as F
 from . import kernels as K
 from . import prepare
 from ._lib import XaiHipError
+from .gradcam import LayerGradCam, gradcam_reduce, layer_handles, layer_tensor, sum_handles
 from .ig import _logits_of, check_input, class_targets
 from .streams import GRAD_RTOL, CapturedCall, ThreadGraphs, backward_turn
 
@@ -90,48 +93,28 @@ def guided_gradients(x, model, tgt, layer=None, guided=True):
     """One forward and one backward -> (d score / d x, layer output or None, d score / d layer output or None) with
     score = sum_b logits[b, tgt[b]]; `guided`: every ReLU backpropagates by Guided Backprop's rule.  x (B, ...) and tgt (B, 1)
     int64 on the device.  A layer output forked by fuse_bn_relu(fork_residual=True) gets the sum over its two handles."""
-    kept = {}
-    me = threading.get_ident()
-    handle = None
-    if layer is not None:
-        handle = layer.register_forward_hook(lambda mod, inp, out: kept.__setitem__("act", out) if threading.get_ident() == me else None)
-    try:
-        with contextlib.ExitStack() as stack:
-            stack.enter_context(torch.enable_grad())
-            if guided:
-                stack.enter_context(prepare.guided_relu())
-                stack.enter_context(_guided_modules(model))
-            xs = x.detach().requires_grad_(True)
-            out = _logits_of(model(xs))
-            score = out.gather(1, tgt).sum()
-            if layer is None:
-                with backward_turn(x.device):
-                    (gx,) = torch.autograd.grad(score, xs)
-                return gx.detach(), None, None
-            act = kept.get("act")
-            if not torch.is_tensor(act):
-                raise XaiHipError("guided Grad-CAM: the layer's output is not a single tensor")
-            alias = getattr(act, "_xai_alias", None)
+    with contextlib.ExitStack() as stack:
+        kept = {} if layer is None else stack.enter_context(layer_tensor(layer))
+        stack.enter_context(torch.enable_grad())
+        if guided:
+            stack.enter_context(prepare.guided_relu())
+            stack.enter_context(_guided_modules(model))
+        xs = x.detach().requires_grad_(True)
+        out = _logits_of(model(xs))
+        score = out.gather(1, tgt).sum()
+        if layer is None:
             with backward_turn(x.device):
-                grads = torch.autograd.grad(score, [xs, act] + ([alias] if alias is not None else []), allow_unused=True)
-    finally:
-        if handle is not None:
-            handle.remove()
-    live = [g for g in grads[1:] if g is not None]
-    if grads[0] is None or not live:
+                (gx,) = torch.autograd.grad(score, xs)
+            return gx.detach(), None, None
+        act = kept.get("act")
+        if not torch.is_tensor(act):
+            raise XaiHipError("guided Grad-CAM: the layer's output is not a single tensor")
+        with backward_turn(x.device):
+            grads = torch.autograd.grad(score, [xs] + layer_handles(act), allow_unused=True)
+    g_act = sum_handles(grads[1:])
+    if grads[0] is None or g_act is None:
         raise XaiHipError("guided Grad-CAM: the score does not depend on the input through the layer")
-    g_act = live[0] if len(live) == 1 else live[0] + live[1]
     return grads[0].detach(), act.detach(), g_act.detach()
-
-
-def _gradcam(act, g_act):
-    """LayerGradCam(..., relu_attributions=True) of a (B, C, h, w) layer -> (B, h, w)"""
-    act, g_act = act.float().contiguous(), g_act.float().contiguous()
-    if act.dim() != 4:
-        raise XaiHipError(f"guided Grad-CAM needs a (B, C, h, w) layer output, got {tuple(act.shape)}")
-    if act.shape[2] * act.shape[3] <= 1024:
-        return K.gradcam(act, g_act, relu=True)
-    return torch.relu((g_act.mean(dim=(2, 3), keepdim=True) * act).sum(dim=1))    # maps beyond K3's 1024 positions: device torch ops
 
 
 class _GuidedPass(CapturedCall):
@@ -146,7 +129,11 @@ class _GuidedPass(CapturedCall):
 
     def step(self):
         gx, act, g_act = guided_gradients(self.x, self.model, self.tgt, self.layer)
-        cam = None if self.layer is None else _gradcam(act, g_act)
+        cam = None
+        if self.layer is not None:
+            if act.dim() != 4:
+                raise XaiHipError(f"guided Grad-CAM needs a (B, C, h, w) layer output, got {tuple(act.shape)}")
+            cam = gradcam_reduce(act, g_act, relu=True)[:, 0]         # LayerGradCam(..., relu_attributions=True) -> (B, h, w)
         out = K.guided_map(gx.float().contiguous(), cam, want_attr=self.want_attr, want_map=self.want_map)
         return out if isinstance(out, tuple) else (out,)
 
@@ -219,7 +206,6 @@ class GuidedGradCam:
         model = _forward_args(self.model, additional_forward_args)
         if interpolate_mode == "nearest" and not attribute_to_layer_input:
             return guided_backprop_batch(inputs, model, target, layer=self.layer, graphs=additional_forward_args is None)
-        from .gradcam import LayerGradCam
         x = check_input(inputs, "GuidedGradCam.attribute")
         tgt = class_targets(target, x.shape[0], x.device, "GuidedGradCam.attribute")
         gx, _, _ = guided_gradients(x, model, tgt.view(-1, 1))

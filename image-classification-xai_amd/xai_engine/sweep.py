@@ -23,7 +23,7 @@ from scipy.stats import spearmanr
 from . import curves
 from . import kernels as K
 from .blur import GaussianBlur
-from .gradcam import gradcam_saliency, CapturedGradCam
+from .gradcam import gradcam_saliency
 from .guided_ig import guided_ig_batch
 from .ig import IG, IDG, abs_channel_sum, getGradientsParallel, hip_device, _logits_of
 from .perturb import (AICMetric, MASMetric, MonotonicityMetric, PositiveNegativePerturbation, _Probe, sequence_stats)
@@ -97,17 +97,9 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         sal = xrai.xrai_batch(ig.detach().to(dev)[None], xrai.pack_segments(label_maps, dilation_rad=5, device=dev))[0].abs()
     elif attr_function == "gc":
         # |cam_up + cam_up + cam_up| fused into the up-sample kernel (scale 3, abs); with testing_dict["capture_gradcam"] the
-        # launch-bound one-image pass is one hipGraph replay (captured once per model and input shape)
-        x = input_tensor.to(dev)
-        if testing_dict.get("capture_gradcam"):
-            # one graph per stream: a replay reads and writes the graph's static buffers, so two streams must not share one
-            key = (id(model), tuple(x.shape), str(dev), torch.cuda.current_stream(dev).cuda_stream)
-            cache = testing_dict.setdefault("_captured_gradcam", {})
-            if key not in cache:
-                cache[key] = CapturedGradCam(model, model.layer4, x, (img_hw, img_hw))
-            sal = cache[key](x, target_class)[0]
-        else:
-            sal = gradcam_saliency(model, model.layer4, x, target_class, (img_hw, img_hw))[0]
+        # launch-bound one-image pass is one replay of the calling thread's hipGraph (gradcam._PASSES)
+        sal = gradcam_saliency(model, model.layer4, input_tensor.to(dev), target_class, (img_hw, img_hw),
+                               graphs=bool(testing_dict.get("capture_gradcam")))[0]
     elif attr_function in ("gbp", "ggc"):
         # :154-163: captum's GuidedBackprop / GuidedGradCam(model, model.layer4) on models[1] (:84; the reference's copy without
         # in-place ReLUs -- a fused classifier needs none), then |sum over channels| (:181) straight from K28

@@ -643,14 +643,22 @@ def test_stream_workers_fail_loudly_without_a_device():
 
 def test_only_streams_py_captures_hip_graphs():
     """How a hipGraph is captured and when it is trusted is decided in one module (xai_engine/streams.py: capture, CapturedCall)."""
-    capturing = []
+    import re
+    capturing, using_capture = [], []
     for d, _, files in os.walk(PKG):
         for f in files:
             if f.endswith(".py"):
                 src = open(os.path.join(d, f)).read()
+                rel = os.path.relpath(os.path.join(d, f), PKG)
                 if "torch.cuda.graph(" in src or "CUDAGraph(" in src:
-                    capturing.append(os.path.relpath(os.path.join(d, f), PKG))
+                    capturing.append(rel)
+                # the bare capture is streams.py's own: every driver goes through CapturedCall, which proves a graph before it is trusted
+                if rel != os.path.join("xai_engine", "streams.py") and (
+                        re.search(r"^\s*from\s+\.?(xai_engine\.)?streams\s+import\s[^\n]*\bcapture\b", src, re.M)
+                        or re.search(r"\bstreams\.capture\b|(?<![\w.])capture\(", src)):
+                    using_capture.append(rel)
     assert capturing == [os.path.join("xai_engine", "streams.py")]
+    assert using_capture == []
 
 
 @pytest.mark.parametrize("n, k, spans", [(7, 3, [(0, 3), (3, 6), (6, 7)]), (7, 7, [(0, 7)]), (7, 99, [(0, 7)]), (7, None, [(0, 7)]),

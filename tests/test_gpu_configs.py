@@ -196,6 +196,8 @@ def test_captured_gradcam_graphs_replayed_concurrently_on_three_streams(resnet):
     backward-to-layer4 replay CONCURRENTLY on three streams.  Concurrent replays of captured classifier passes are not a given
     (profiles/r03_exp_ig_graph_streams.jsonl: per-pass IG graphs at batch 50 corrupt each other), so the sums are held, bit for bit,
     to the eager one-stream sweep."""
+    from xai_engine.gradcam import _PASSES
+    from xai_engine.streams import run_on_streams
     from xai_engine.sweep import sweep_images, get_CNN_attr, KEYS
     td = {"models": [resnet], "img_hw": 224, "batch_size": 50, "device": DEV, "device_maps": True, "attr_func": "gc"}
     images = [_image(2000 + i) for i in range(6)]
@@ -203,7 +205,9 @@ def test_captured_gradcam_graphs_replayed_concurrently_on_three_streams(resnet):
     tdc = dict(td, capture_gradcam=True)
     for rep in range(2):
         cap, used_c, _ = sweep_images(images, resnet, DEV, lambda x, t: get_CNN_attr(x, None, t, tdc), img_hw=224, batch_size=50, streams=3)
-        assert used == used_c == 6 and len(tdc["_captured_gradcam"]) == 3
+        assert used == used_c == 6
+        per_worker = run_on_streams(DEV, 3, [lambda: [e.refused for m, e in _PASSES.entries().values() if m is resnet]] * 3)
+        assert per_worker == [[None]] * 3, per_worker            # one kept graph per stream worker
         for k in KEYS:
             assert cap[k] == eager[k], (rep, k, cap[k], eager[k])
 

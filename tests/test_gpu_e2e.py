@@ -211,11 +211,15 @@ def test_ig_batch_called_from_a_stream_worker_runs_its_passes_eagerly_on_that_th
     assert torch.equal(nested, main)
 
 
+def _entries_per_worker(cache, model):
+    """per stream worker (three of them): the `refused` of each entry `model` has in a driver's graph cache"""
+    from xai_engine.streams import run_on_streams
+    return run_on_streams(DEV, 3, [lambda: [e.refused for m, e in cache.entries().values() if m is model]] * 3)
+
+
 def _refusals(cache, model):
     """the refusal reasons of `model`'s entries in a driver's graph cache, on each of three stream workers"""
-    from xai_engine.streams import run_on_streams
-    per_worker = run_on_streams(DEV, 3, [lambda: [e.refused for m, e in cache.entries().values() if m is model]] * 3)
-    return [r for reasons in per_worker for r in reasons]
+    return [r for reasons in _entries_per_worker(cache, model) for r in reasons]
 
 
 @pytest.mark.parametrize("wrapper", [Syncing, SquaresWhenCaptured])
@@ -252,6 +256,50 @@ def test_refused_captures_run_eagerly_in_ig_the_sweep_and_guided_ig(wrapper):
     got = gig.guided_ig_batch(xs, wrapped, ts)
     assert_refused(gig.GIG_COUNTS, before, [e.refused for m, e in gig._PASSES.entries().values() if m is wrapped])
     assert torch.equal(got, gig.guided_ig_batch(xs, model, ts, graphs=False))
+
+
+def test_a_refused_gradcam_capture_runs_eagerly():
+    """Grad-CAM's graph is refused like every other driver's: a classifier whose graph differs from the eager pass on real inputs
+    keeps the reason, replays nothing, and returns the eager map -- now and on the next call."""
+    from xai_engine import gradcam as gc
+    from xai_engine.zoo import resnet50
+    model = resnet50(seed=0, width=16, num_classes=20).to(DEV)
+    wrapped = SquaresWhenCaptured(model)
+    x = torch.randn(1, 3, 64, 64, generator=torch.Generator().manual_seed(41)).to(DEV)
+    want = gc.gradcam_saliency(model, model.layer4, x, 11, (64, 64), graphs=False)
+    before = dict(gc.GRADCAM_COUNTS)
+    for _ in range(2):
+        got = gc.gradcam_saliency(wrapped, wrapped.inner.layer4, x, 11, (64, 64), graphs=True)
+        assert torch.equal(got, want)
+    after = gc.GRADCAM_COUNTS
+    assert after["captures_refused"] == before["captures_refused"] + 1 and after["captures"] == before["captures"]
+    assert after["replayed"] == before["replayed"] and after["eager"] == before["eager"] + 2
+    assert [e.refused for m, e in gc._PASSES.entries().values() if m is wrapped] == ["replay differs"]
+
+
+def test_gradcam_reduce_is_K3_up_to_1024_positions_and_device_torch_beyond():
+    """The one Grad-CAM reduction (LayerGradCam, the captured pass, Guided Grad-CAM): 1024 positions per channel is the last K3 size,
+    bit for bit the kernel; one row more is the torch expression, bit for bit; a rank-3 layer goes through K3 with its positions
+    flattened, the way LayerGradCam.attribute has always sent it."""
+    from xai_engine import kernels as K
+    from xai_engine.gradcam import gradcam_reduce
+    gen = torch.Generator(device=DEV).manual_seed(7)
+
+    def pair(*shape):
+        return torch.randn(shape, device=DEV, generator=gen), torch.randn(shape, device=DEV, generator=gen)
+    for relu in (True, False):
+        act, grad = pair(2, 8, 32, 32)
+        got = gradcam_reduce(act, grad, relu=relu)
+        assert got.shape == (2, 1, 32, 32) and torch.equal(got[:, 0], K.gradcam(act, grad, relu=relu))
+        act, grad = pair(2, 8, 33, 32)
+        want = (grad.mean(dim=(2, 3), keepdim=True) * act).sum(dim=1, keepdim=True)
+        got = gradcam_reduce(act, grad, relu=relu)
+        assert got.shape == (2, 1, 33, 32) and torch.equal(got, torch.relu(want) if relu else want)
+        act, grad = pair(2, 5, 16)
+        got = gradcam_reduce(act, grad, relu=relu)
+        assert got.shape == (2, 1, 16)
+        assert torch.equal(got, K.gradcam(act.reshape(2, 5, 16, 1), grad.reshape(2, 5, 16, 1), relu=relu).reshape(2, 1, 16))
+        assert bool((got < 0).any()) == (not relu)
 
 
 def test_the_sweeps_graph_cache_keeps_its_model_alive():
@@ -1320,6 +1368,7 @@ def test_get_VIT_attr_vitcx_and_tis_dispatch():
 
 
 def test_captured_gradcam_replays_match_eager():
+    from xai_engine import gradcam as gc
     from xai_engine.gradcam import CapturedGradCam, gradcam_saliency
     from xai_engine.zoo import resnet50
     model = resnet50(seed=0, width=16, num_classes=20).to(DEV)
@@ -1329,29 +1378,42 @@ def test_captured_gradcam_replays_match_eager():
         want = gradcam_saliency(model, model.layer4, x, t, (64, 64))
         got = cap(x, t)
         assert got.shape == want.shape == (1, 64, 64)
-        assert rel_inf(got.cpu().numpy(), want.cpu().numpy()) <= 1e-5
+        assert torch.equal(got, want)                                   # deterministic solvers (conftest): the same bits
+    assert cap.refused is None and cap.graph is not None
     a, b = cap(xs[0], 3), cap(xs[0], 11)
     assert not torch.equal(a, b)
     with pytest.raises(ValueError):
         cap(torch.zeros(2, 3, 64, 64, device=DEV), 0)
+    # two images with a class each: every image gets the map of its own class
+    x2, t2 = torch.cat(xs[:2]), torch.tensor([3, 11], device=DEV)
+    want2 = gradcam_saliency(model, model.layer4, x2, t2, (64, 64))
+    cap2 = CapturedGradCam(model, model.layer4, x2, (64, 64))
+    for _ in range(2):                                                  # the proving call, then a plain replay
+        assert torch.equal(cap2(x2, t2), want2)
+    assert cap2.refused is None and not torch.equal(want2, gradcam_saliency(model, model.layer4, x2, 3, (64, 64)))
     from xai_engine.sweep import get_CNN_attr
     td = {"models": [model], "img_hw": 64, "batch_size": 25, "device": DEV, "attr_func": "gc"}
     eager = get_CNN_attr(xs[1].cpu(), None, torch.tensor(11), dict(td))
     tdc = dict(td, capture_gradcam=True)
+    before = dict(gc.GRADCAM_COUNTS)
     for _ in range(2):                                                  # second call replays the cached graph
-        assert rel_inf(get_CNN_attr(xs[1].cpu(), None, torch.tensor(11), tdc), eager) <= 1e-5
-    assert len(tdc["_captured_gradcam"]) == 1
-    # the sweep on three streams with captured Grad-CAM: one graph PER STREAM (a replay owns the graph's static buffers), same sums
+        assert np.array_equal(get_CNN_attr(xs[1].cpu(), None, torch.tensor(11), tdc), eager)
+    moved = {k: gc.GRADCAM_COUNTS[k] - before[k] for k in before}
+    assert moved == {"captures": 1, "captures_refused": 0, "replayed": 2, "eager": 0}, moved
+    assert [e.refused for m, e in gc._PASSES.entries().values() if m is model] == [None]       # one kept graph of this thread for this model
+    # the sweep on three streams with captured Grad-CAM: one graph PER STREAM WORKER (a replay owns the graph's static buffers), same sums
     from xai_engine.sweep import sweep_images, KEYS
     images = [torch.randn(1, 3, 64, 64, generator=torch.Generator().manual_seed(60 + i)) for i in range(7)]
     tds = dict(td, device_maps=True, capture_gradcam=True)
+    before = dict(gc.GRADCAM_COUNTS)
     s3, used, _ = sweep_images(images, model, DEV, lambda x, t: get_CNN_attr(x, None, t, tds), img_hw=64, batch_size=25, streams=3)
-    assert used == 7 and len(tds["_captured_gradcam"]) == 3
+    moved = {k: gc.GRADCAM_COUNTS[k] - before[k] for k in before}
+    assert used == 7 and _entries_per_worker(gc._PASSES, model) == [[None]] * 3
+    assert moved["replayed"] == 7 and moved["eager"] == 0, moved
     te = dict(td, device_maps=True)
     s1, _, _ = sweep_images(images, model, DEV, lambda x, t: get_CNN_attr(x, None, t, te), img_hw=64, batch_size=25)
     for k in KEYS:                                       # deterministic solvers (conftest): a replay computes what the eager launch computes
         assert s3[k] == s1[k], (k, s3[k], s1[k])
-
 
 
 # ------------------------------------------------------------------------------ opt-in classifier fusion

@@ -3,6 +3,8 @@
 //   K11 up_rownorm     feature maps (R,h,w) -> bilinear (H,W) -> per-row min-max normalised masks, one launch:
 //                      the map is stretched in LDS and its up-sampled values are computed twice (once for the
 //                      row's min / max, once to write), so HBM sees R*H*W*4 bytes of writes and nothing else.
+//                      Up-sampling only (H >= h, W >= w): the reference resizes with antialias=True, which is this
+//                      two-tap formula only then; a smaller target in either axis is refused (XAI_E_UNSUPPORTED).
 //   K12 rownorm        per-row min-max normalisation of stored rows (the cluster sums).
 //   K13 cluster_sum    out[k] = sum of the member rows of cluster k, members in ascending row order (the order of
 //                      the reference's `mask_clustering[label[i]] += mask[i]` loop, so the sums round identically).
@@ -18,7 +20,9 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxSrc = 4096;       // h*w floats of one feature map held in LDS
 constexpr int kMaxStretch = 8192;   // h*W floats of its horizontally stretched copy (dynamic LDS, 32 KB)
-constexpr int kMaxTaps = 1024;      // H vertical taps of 16 B behind it (16 KB): 64 KB per workgroup with `s`
+constexpr int kMaxTaps = 1024;      // H vertical taps of 16 B behind it (16 KB).  With `s` and `red` a workgroup at all three
+                                    // limits holds 16 416 B static + 49 152 B dynamic = 65 568 B, 32 B over 64 KiB: gfx950
+                                    // gives a workgroup up to 160 KiB and the launch succeeds (tests/test_gpu_masker_edges.py)
 
 // NaN-propagating variants of block_min_max are not needed: the reference's torch.min / torch.max propagate NaN, fminf / fmaxf
 // drop it; feature maps and cluster sums are finite, and a NaN row would stay NaN in the reference only.
@@ -38,7 +42,9 @@ __device__ __forceinline__ Tap make_tap(int o, int n_in, float ratio) {
 }
 
 // Correctly rounded num / span from y = RN(1 / span) (Markstein): q = RN(num*y), r = num - q*span exactly (fma),
-// RN(q + r*y) is the IEEE quotient -- 3 instructions per element instead of a full division sequence.
+// RN(q + r*y) is the IEEE quotient -- 3 instructions per element instead of a full division sequence.  The sequence is
+// evaluated exactly and held to IEEE division for 0 <= num <= span in tests/test_cpu_maskers.py (all-ones and power-of-two
+// significands, num at span, one ulp below and 0, everything again times 2^60 and 2^-60), and K11 to the quotient's bits on the GPU.
 __device__ __forceinline__ float div_by(float num, float span, float y) {
   const float q = num * y;
   const float r = __builtin_fmaf(-q, span, num);
@@ -312,6 +318,7 @@ XAI_EXPORT int xai_up_rownorm_f32(const float* src, int R, int h, int w, int H, 
   XAI_REQUIRE(static_cast<int64_t>(h) * w <= kMaxSrc && static_cast<int64_t>(H) * W <= INT32_MAX &&
               static_cast<int64_t>(h) * W <= kMaxStretch, XAI_E_UNSUPPORTED);
   XAI_REQUIRE(H <= kMaxTaps, XAI_E_UNSUPPORTED);
+  XAI_REQUIRE(H >= h && W >= w, XAI_E_UNSUPPORTED);     // shrinking: the reference's antialias filter is no longer these two taps
   const size_t lds = (static_cast<size_t>((h * W + 3) & ~3) + 4 * static_cast<size_t>(H)) * sizeof(float);
   if (xai_can_vec4(W, {out}))
     hipLaunchKernelGGL(up_rownorm_kernel<true>, dim3(R), dim3(kBlock), lds, static_cast<hipStream_t>(stream), src, h, w, H, W, out);

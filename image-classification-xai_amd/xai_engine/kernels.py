@@ -316,7 +316,9 @@ def softmax_stats(logits, target=None, want_entropy=True, want_argmax=True, out=
 
 # ------------------------------------------------------------------------------ feature-map maskers (ViT-CX)
 def up_rownorm(src, H, W):
-    """src (R,h,w) -> (R, H*W): bilinear up-sample (align_corners=False) and per-row min-max normalisation."""
+    """src (R,h,w) -> (R, H*W): bilinear up-sample (align_corners=False) and per-row min-max normalisation.
+    H >= h and W >= w: the reference's Resize(antialias=True) is plain bilinear only when up-sampling, so a smaller target
+    in either axis raises (XAI_E_UNSUPPORTED) instead of returning the un-filtered samples."""
     _need(src, F32, "src")
     R, h, w = src.shape
     out = torch.empty((R, int(H) * int(W)), dtype=F32, device=src.device)

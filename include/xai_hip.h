@@ -213,7 +213,9 @@ int xai_softmax_stats_f32(const float* logits, int B, int K, const int32_t* targ
 /* K11 masks[r] = minmax_row( bilinear_up(src[r], (H,W), align_corners = False) ), one launch, the up-sampled
  *     maps never exist un-normalised in memory
  * replaces  ViT_CX/ViT_CX.py:82-84 (transforms.Resize(input_size, antialias=True), then norm_matrix :29-34)
- *   src : [R][h*w], h*w <= 4096, h*W <= 8192, H <= 1024;  out : [R][H*W];  a constant row gives 0/0 = NaN as in the reference */
+ *   src : [R][h*w], h*w <= 4096, h*W <= 8192, H <= 1024;  out : [R][H*W];  a constant row gives 0/0 = NaN as in the reference
+ *   H >= h and W >= w: the reference's antialias = True is the plain bilinear formula only when up-sampling (14x14 -> 7x7
+ *   differs by 0.74 of the row span), so a target smaller than the source in either axis is XAI_E_UNSUPPORTED */
 int xai_up_rownorm_f32(const float* src, int R, int h, int w, int H, int W, float* out,
                        xai_stream_t stream);
 

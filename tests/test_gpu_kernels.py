@@ -481,7 +481,8 @@ def test_rownorm_cluster_sum_and_causal_apply(K):
     from oracle import vit_cx as ocx
     from xai_engine.vit_cx import cluster_members
     g = load_golden("vit_cx.npz")
-    assert rel_inf(K.rownorm(dev(g["act"])).cpu().numpy(), g["act_norm"]) <= 1e-6          # the reference's norm_matrix
+    got = K.rownorm(dev(g["act"])).cpu().numpy()                                            # the reference's norm_matrix, to the bit
+    assert np.array_equal(got.view(np.int32), g["act_norm"].view(np.int32)) and np.array_equal(got, ocx.norm_matrix(g["act"]))
     rng = np.random.default_rng(31)
     for R, P, n_cl in ((40, 1024, 7), (33, 1001, 5), (768, 224 * 224, 60)):
         rows = rng.random((R, P)).astype(np.float32)
@@ -500,6 +501,7 @@ def test_rownorm_cluster_sum_and_causal_apply(K):
     lib = __import__("xai_engine")._lib.load()
     t = torch.zeros(8, device=DEV)
     assert lib.xai_up_rownorm_f32(t.data_ptr(), 1, 100, 100, 4, 4, t.data_ptr(), None) == -3
+    assert lib.xai_up_rownorm_f32(t.data_ptr(), 1, 2, 2, 1, 4, t.data_ptr(), None) == -3     # a smaller target: antialiasing is not these taps
     assert lib.xai_cluster_sum_f32(t.data_ptr(), None, t.data_ptr(), 1, 4, t.data_ptr(), None) == -1
     assert lib.xai_causal_apply_f32(t.data_ptr(), t.data_ptr(), t.data_ptr(), 0, 3, 4, 0.1, t.data_ptr(), None) == -2
 

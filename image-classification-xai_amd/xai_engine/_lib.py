@@ -78,11 +78,15 @@ SIGNATURES = {
     "xai_xrai_workspace_bytes": [_i, _i, _i, _l],
     "xai_xrai_pack_u64": [_p, _p, _p, _i, _p, _l, _i, _i, _i, _p, _p, _p],
     "xai_xrai_rank_f32": [_p, _p, _p, _p, _i, _l, _i, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, C.c_size_t, _p],
+    "xai_lime_max_features": [],
+    "xai_lime_compose_f32": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _l, _i, _p, _p],
+    "xai_lime_fit_f64": [_p, _i, _p, _p, _i, _i, _i, _i, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p],
+    "xai_lime_paint_f32": [_p, _p, _i, _i, _i, _i, _p, _p],
 }
 _RESTYPE = {"xai_strerror": C.c_char_p, "xai_rank_workspace_bytes": C.c_size_t, "xai_gradcam_workspace_bytes": C.c_size_t,
             "xai_attn_head_importance_workspace_bytes": C.c_size_t, "xai_bn_gate_mask_bytes": C.c_size_t, "xai_xrai_workspace_bytes": C.c_size_t}
 
-ABI_VERSION, ABI_MINOR = 1, 10      # XAI_ABI_VERSION / XAI_ABI_MINOR of include/xai_hip.h this binding was written against
+ABI_VERSION, ABI_MINOR = 1, 11      # XAI_ABI_VERSION / XAI_ABI_MINOR of include/xai_hip.h this binding was written against
 
 _lib = None
 

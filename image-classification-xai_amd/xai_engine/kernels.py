@@ -946,3 +946,85 @@ def xrai_rank(attr, bits, span, mask_first, min_pixel_diff, area_threshold, fast
           int(min_pixel_diff), float(area_threshold), int(bool(fast)), _ptr(out), _ptr(pixel_iter), _ptr(sel_key) if M else None,
           _ptr(sel_gain) if M else None, _ptr(state), _ptr(ws), nbytes)
     return out, pixel_iter, sel_key, sel_gain, state
+
+
+# ------------------------------------------------------------------------------ LIME (K31, K32, K33)
+F64 = torch.float64
+
+
+def lime_max_features():
+    """The largest number of superpixels of one image K32 fits."""
+    return int(_lib.load().xai_lime_max_features())
+
+
+def lime_words(d_max):
+    return (int(d_max) + 63) // 64
+
+
+def _lime_rows(rows, D, B, name):
+    """rows int64 (B * N, words) bit rows, D int32 (B,) -> (N, words)"""
+    _need(rows, I64, "rows"); _need(D, I32, "D")
+    if rows.dim() != 2 or D.numel() != B or rows.shape[0] % B or rows.shape[0] == 0 or rows.shape[1] == 0:
+        raise ValueError(f"{name}: rows must be (B * n_samples, words) and D ({B},)")
+    return rows.shape[0] // B, rows.shape[1]
+
+
+def lime_compose(x, seg, rows, D, hide, first, n, fudged=None, out=None):
+    """K31: rows [first, first + n) of the flat list of perturbed images (image * n_samples + sample) of x (B, C, H, W):
+    x where the row keeps the pixel's superpixel, else `fudged` (B, C, H, W) or `hide` (C,) -> (n, C, H, W).  seg: int32 (B, H, W);
+    rows: int64 (B * n_samples, words) bit rows; D: int32 (B,) superpixels per image."""
+    _need(x, F32, "x"); _need(seg, I32, "seg")
+    if x.dim() != 4:
+        raise ValueError("x must be (B, C, H, W)")
+    B, Cc, H, W = x.shape
+    if tuple(seg.shape) != (B, H, W):
+        raise ValueError(f"seg must be ({B}, {H}, {W}), got {tuple(seg.shape)}")
+    N, words = _lime_rows(rows, D, B, "lime_compose")
+    if fudged is not None:
+        _need(fudged, F32, "fudged")
+        if tuple(fudged.shape) != tuple(x.shape):
+            raise ValueError(f"fudged must be {tuple(x.shape)}, got {tuple(fudged.shape)}")
+    if hide is not None:
+        _need(hide, F32, "hide")
+        if hide.numel() != Cc:
+            raise ValueError(f"hide must hold {Cc} values")
+    if hide is None and fudged is None:
+        raise ValueError("lime_compose: pass hide or fudged")
+    out = _ablation_rows(x, N, int(first), int(n), out)
+    _call("xai_lime_compose_f32", x.device, _ptr(x), _ptr(seg), _ptr(rows), _ptr(D), words, _ptr(hide), _ptr(fudged), B, Cc, H, W, N,
+          int(first), int(n), _ptr(out))
+    return out
+
+
+def lime_fit(rows, D, Y, kernel_width=0.25, alpha_select=0.01, alpha=1.0, d_stride=None):
+    """K32: rows int64 (B * N, words), D int32 (B,), Y float32 (B, N, L) -> dict of fp64 device tensors coef (B, L, d_stride),
+    intercept, score, local_pred (B, L), dist, weight (B, N) and int32 order (B, L, d_stride).  An image whose D is above
+    `lime_max_features()` is skipped: its entries stay zero (order -1)."""
+    _need(Y, F32, "Y")
+    if Y.dim() != 3:
+        raise ValueError("lime_fit: Y must be (B, N, L)")
+    B, N, L = Y.shape
+    n_rows, words = _lime_rows(rows, D, B, "lime_fit")
+    if n_rows != N or L == 0:
+        raise ValueError(f"lime_fit: rows hold {n_rows} samples per image, Y {N} with {L} labels")
+    d_stride = words * 64 if d_stride is None else int(d_stride)
+    dev = Y.device
+    res = dict(coef=torch.zeros((B, L, d_stride), dtype=F64, device=dev), order=torch.full((B, L, d_stride), -1, dtype=I32, device=dev),
+               intercept=torch.zeros((B, L), dtype=F64, device=dev), score=torch.zeros((B, L), dtype=F64, device=dev),
+               local_pred=torch.zeros((B, L), dtype=F64, device=dev), dist=torch.zeros((B, N), dtype=F64, device=dev),
+               weight=torch.zeros((B, N), dtype=F64, device=dev))
+    _call("xai_lime_fit_f64", dev, _ptr(rows), words, _ptr(D), _ptr(Y), B, N, L, d_stride, float(kernel_width), float(alpha_select),
+          float(alpha), _ptr(res["coef"]), _ptr(res["intercept"]), _ptr(res["score"]), _ptr(res["local_pred"]), _ptr(res["order"]),
+          _ptr(res["dist"]), _ptr(res["weight"]))
+    return res
+
+
+def lime_paint(table, seg):
+    """K33: table float32 (B, d_stride), seg int32 (B, H, W) -> (B, H, W) float32, table[b][seg[b]] (0 for an id outside the table)."""
+    _need(table, F32, "table"); _need(seg, I32, "seg")
+    if table.dim() != 2 or seg.dim() != 3 or seg.shape[0] != table.shape[0] or table.shape[1] == 0:
+        raise ValueError("lime_paint: table must be (B, d_stride) and seg (B, H, W)")
+    B, H, W = seg.shape
+    out = torch.empty((B, H, W), dtype=F32, device=seg.device)
+    _call("xai_lime_paint_f32", seg.device, _ptr(table), _ptr(seg), B, table.shape[1], H, W, _ptr(out))
+    return out

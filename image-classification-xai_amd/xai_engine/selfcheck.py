@@ -263,6 +263,36 @@ def run(device="cuda:0", verbose=True):
     n_sel = int(xstate[0, 0])
     check("xrai_rank selections", float(n_sel != len(keys) or skey[:n_sel].tolist() != keys), 0.0)
     check("xrai_rank map", _rel(xo[0], want), 2e-6)
+    # LIME (K31 - K33): two images with 70 and 9 superpixels, 40 samples
+    lD, lN = (70, 9), 40
+    lseg = torch.stack([torch.randint(0, d, (20, 24), device=dev, generator=gen) for d in lD]).int()
+    lbits = [torch.randint(0, 2, (lN, d), device=dev, generator=gen) for d in lD]
+    lrows = torch.zeros((2 * lN, 2), dtype=torch.int64, device=dev)
+    for i, bits in enumerate(lbits):
+        for z in range(bits.shape[1]):
+            lrows[i * lN:(i + 1) * lN, z // 64] |= bits[:, z] << (z % 64)
+    lDt = torch.tensor(lD, dtype=torch.int32, device=dev)
+    lx, lhide = rnd(2, 3, 20, 24), rnd(3)
+    got = K.lime_compose(lx, lseg, lrows, lDt, lhide, 30, 20)                  # rows 30 .. 49: the end of image 0, the start of image 1
+    want = torch.stack([torch.where(lbits[r // lN][r % lN][lseg[r // lN].long()].bool()[None], lx[r // lN], lhide.view(3, 1, 1).expand(3, 20, 24))
+                        for r in range(30, 50)])
+    check("lime_compose", float(not torch.equal(got, want)), 0.0)
+    lY = torch.rand(2, lN, 3, device=dev, generator=gen)
+    fit = K.lime_fit(lrows, lDt, lY)
+    worst = 0.0
+    for i, bits in enumerate(lbits):
+        X = bits.double()
+        d = 1.0 - (X.sum(1) / lD[i]).sqrt()
+        w = (-(d * d) / 0.25 ** 2).exp().sqrt()
+        xbar, ybar = (w[:, None] * X).sum(0) / w.sum(), (w[:, None] * lY[i].double()).sum(0) / w.sum()
+        A = ((X - xbar) * w[:, None]).T @ (X - xbar) + torch.eye(lD[i], device=dev, dtype=torch.float64)
+        coef = torch.linalg.solve(A, ((X - xbar) * w[:, None]).T @ (lY[i].double() - ybar))          # (D, L)
+        worst = max(worst, _rel(fit["coef"][i, :, :lD[i]], coef.T), _rel(fit["intercept"][i], ybar - xbar @ coef), _rel(fit["weight"][i], w))
+        by_size = fit["coef"][i, :, :lD[i]].abs().gather(1, fit["order"][i, :, :lD[i]].long())
+        worst = max(worst, float((by_size[:, 1:] > by_size[:, :-1]).any()))       # the order is by descending |coef|
+    check("lime_fit", worst, 1e-9)
+    ltab = rnd(2, 128)
+    check("lime_paint", float(not torch.equal(K.lime_paint(ltab, lseg), ltab.gather(1, lseg.view(2, -1).long()).view(2, 20, 24))), 0.0)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

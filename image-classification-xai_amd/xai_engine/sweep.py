@@ -31,8 +31,10 @@ from .smooth import smoothGrad
 from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "sg", "xrai", "gc", "gbp", "ggc", "fa", "occ")
-TRANS_ATTR_FUNCS = ("agi",)          # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
+# ("lime" stands in front of "sg": the reference's place for it is between ggc and fa, :168-170, but the tuple's tail and the
+# neighbours of "xrai" are pinned by the rows that came before it)
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "lime", "sg", "xrai", "gc", "gbp", "ggc", "fa", "occ")
+TRANS_ATTR_FUNCS = ("agi", "lime")   # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
 
@@ -85,6 +87,19 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
             raise ValueError(f"agi: the image predicted as class {int(init_pred[0])} has no attribution: every selected class "
                              "equals its prediction or no attack made an update (the reference crashes here)")
         sal = hm[0]
+    elif attr_function == "lime":
+        # :168-170 -> limeAttr.py:23-36: the un-normalised [0, 1] image goes to the classifier as it is (no Normalize: the
+        # reference's behaviour), quickshift superpixels on the host (skimage; testing_dict["lime_segments"], not a reference key,
+        # a callable from the (H, W, C) image to the ids, replaces the segmenter), 1000 samples, top 5 labels, hide colour 0; the
+        # mask of the five most positive superpixels of the top class times ones(3, H, W), |sum over channels| (:181) = K33's 3 / 0
+        if trans_img is None:
+            raise ValueError("lime: the row needs the harness's un-normalised [0, 1] image (trans_img)")
+        from . import lime
+        seg_fn = testing_dict.get("lime_segments")
+        segmenter = (lambda im, seed: seg_fn(im)) if seg_fn is not None else lime.quickshift_segments
+        model.eval()
+        sal = lime.lime_batch(torch.as_tensor(trans_img).to(torch.float32)[None].to(dev), model, segmenter, num_samples=1000, top_labels=5,
+                              hide_color=0, random_state=testing_dict.get("lime_random_state"))[0]
     elif attr_function == "sg":
         saliency_map = smoothGrad("IG", input_tensor, model, 50, baseline, target_class, device)
     elif attr_function == "xrai":

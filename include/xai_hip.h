@@ -45,9 +45,10 @@ typedef void* xai_stream_t; /* hipStream_t */
  *   8 = + xai_bn_gate_mask_bytes, xai_bn_relu_fwd_mask_f32, xai_bn_relu_bwd_mask_f32, xai_bn_relu_maxpool_fwd_code_f32,
  *         xai_bn_relu_maxpool_bwd_f32;
  *   9 = + xai_bn_relu_bwd_mask_guided_f32, xai_bn_relu_maxpool_bwd_guided_f32, xai_guided_map_f32;
- *  10 = + xai_xrai_workspace_bytes, xai_xrai_pack_u64, xai_xrai_rank_f32 */
+ *  10 = + xai_xrai_workspace_bytes, xai_xrai_pack_u64, xai_xrai_rank_f32;
+ *  11 = + xai_lime_max_features, xai_lime_compose_f32, xai_lime_fit_f64, xai_lime_paint_f32 */
 #define XAI_ABI_VERSION 1
-#define XAI_ABI_MINOR 10
+#define XAI_ABI_MINOR 11
 #define XAI_OK 0
 #define XAI_E_NULL (-1)        /* required pointer is NULL                      */
 #define XAI_E_SHAPE (-2)       /* non-positive / inconsistent extent, or misaligned */
@@ -553,6 +554,53 @@ int xai_xrai_rank_f32(const float* attr, const uint64_t* bits, const int32_t* sp
                       int64_t M_total, int H, int W, int min_pixel_diff, double area_threshold, int fast, float* out,
                       int32_t* pixel_iter, int32_t* sel_key, float* sel_gain, int32_t* state, void* workspace,
                       size_t workspace_bytes, xai_stream_t stream);
+
+/* ---- LIME for images (xai_engine/lime.py) ------------------------------------------------- */
+
+/* A sample is a row of bits, one per superpixel: bit z % 64 of word z / 64 of the row is 1 where superpixel z keeps the image
+ * and 0 where it is replaced; a row has words >= ceil(D / 64) uint64 words, the bits at positions >= D are ignored.  The
+ * samples of all images form one flat list, row r = image * n_samples + sample.
+ *
+ * K31 out[k][c][p] = bit(rows[first + k], seg[b][p]) ? x[b][c][p] : (fudged ? fudged[b][c][p] : hide[c]),  b = (first + k) / n_samples
+ * replaces  lime_image.py:255-262 (data_labels: one deepcopy and one full-image compare per switched-off superpixel, per sample)
+ *           and the transpose / stack of limeAttr.py:8-13
+ *   x : [B][C][H][W];  seg : [B][H][W] int32;  rows : [B * n_samples][words];  D : [B] int32 (device), the superpixels of every
+ *   image;  hide : [C] or NULL;  fudged : [B][C][H][W] or NULL (one of the two required; fudged wins);  out : [n][C][H][W]
+ *   The value is selected, never blended: NaN and Inf of a kept superpixel pass through, those of a replaced one vanish.  An id
+ *   outside [0, D[b]) belongs to no superpixel a row can switch off and keeps the image.  16-byte accesses when C*H*W % 4 == 0
+ *   and x, fudged, out are 16-byte aligned, else the scalar flavour.  words <= 2048, above it XAI_E_UNSUPPORTED. */
+int xai_lime_compose_f32(const float* x, const int32_t* seg, const uint64_t* rows, const int32_t* D, int words, const float* hide,
+                         const float* fudged, int B, int C, int H, int W, int n_samples, int64_t first, int n, float* out,
+                         xai_stream_t stream);
+
+/* the largest D[b] xai_lime_fit_f64 fits (lime_base.py:78-80 and :189-193 put no bound on it; the caller fits larger images itself) */
+int xai_lime_max_features(void);
+
+/* K32 distances, kernel weights and both weighted ridge fits of every label of every image in one launch, one workgroup per image
+ * replaces  lime_image.py:202-206 (cosine distances to row 0), :120-121 (the exponential kernel) and lime_base.py:181-207
+ *           (explain_instance_with_data with feature_selection 'highest_weights': Ridge(alpha_select) at :78-80, the order of
+ *           :109-114, Ridge(alpha) at :189-193, score, local_pred and the sorted explanation of :205-206)
+ *   rows as for K31, N = n_samples;  Y : [B][N][L] float32, the label columns of the classifier's probabilities
+ *   k_n = popcount of the first D bits of row n;  dist = 1 - sqrt(k_n / D);  weight = sqrt(exp(-dist^2 / kernel_width^2))
+ *   mean_j = sum_n w x_nj / sum_n w,  ybar likewise;  A = sum_n w (x_n - mean)(x_n - mean)^T;  rhs = sum_n w (x_n - mean)(y_n - ybar)
+ *   c1 = (A + alpha_select I)^-1 rhs;  position of feature j among the used features = its rank by |c1_j * x_0j| descending,
+ *   ties to the lower j;  coef = (A + alpha I)^-1 rhs;  intercept = ybar - mean . coef;  local_pred = intercept + x_0 . coef;
+ *   score = 1 - sum w (y - pred)^2 / sum w (y - ybar)^2 (NaN for N < 2; a zero denominator gives 1 when the numerator is 0,
+ *   else 0, as sklearn's r2_score);  order = the features by |coef_j| descending, ties to the earlier position
+ *   coef : [B][L][d_stride] fp64, indexed by feature, 0 at j >= D;  order : [B][L][d_stride] int32, -1 at j >= D;
+ *   intercept, score, local_pred : [B][L] fp64;  dist, weight : [B][N] fp64
+ *   All arithmetic is fp64 (Cholesky, packed lower triangles in LDS); every sum has one fixed order and there are no floating-point
+ *   atomics: two runs give the same bits.  An image with D[b] outside [1, min(xai_lime_max_features(), d_stride, 64 * words)] is
+ *   skipped: none of its outputs is written.  NaN in Y leaves `order` of that label unspecified. */
+int xai_lime_fit_f64(const uint64_t* rows, int words, const int32_t* D, const float* Y, int B, int N, int L, int d_stride,
+                     double kernel_width, double alpha_select, double alpha, double* coef, double* intercept, double* score,
+                     double* local_pred, int32_t* order, double* dist, double* weight, xai_stream_t stream);
+
+/* K33 out[b][p] = table[b][seg[b][p]], 0 for an id outside [0, d_stride)
+ * replaces  lime_image.py:74-76 (get_image_and_mask: mask[segments == f] = 1 per chosen feature) with the harness's
+ *           broadcast to three channels and |sum|, evaluatePerturbation.py:181, for a table that holds 3 on the chosen segments
+ *   table : [B][d_stride] float32;  seg : [B][H][W] int32;  out : [B][H][W] float32 */
+int xai_lime_paint_f32(const float* table, const int32_t* seg, int B, int d_stride, int H, int W, float* out, xai_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,8 @@
 //    the arithmetic removed it is no faster, and a separable LDS-staged form (column-interpolated rows + one vertical
 //    lerp per pixel) is 4-7 % slower (csrc/tune/tune_rise.hip, profiles/r02_tune_rise.txt).
 // K5 (compute/LDS-bound, almost no HBM traffic): grid = (pixel tiles, mask slices); tap tables
-//    for every up-sampled row/column live in LDS, mask grids are staged in LDS 256 at a time,
+//    for every up-sampled row/column live in LDS, mask grids are staged in LDS 256 at a time (fewer
+//    for s >= 15, where 256 grids of s*s bytes no longer fit 64 KiB: any s <= 64 runs),
 //    a lane owns one pixel and accumulates score*mask in fp64; one fp64 atomic per pixel per
 //    slice merges the slices.
 #include "xai_common.h"
@@ -186,20 +187,22 @@ __global__ __launch_bounds__(kBlock) void rise_apply_kernel_s8(const uint8_t* __
   }
 }
 
-constexpr int kStage = 256;   // masks staged in LDS per round
+constexpr int kStage = 256;   // masks staged in LDS per round, at most
 
+// `stage` = masks staged per round, chosen by the host so that the arrays below fit 64 KiB for this s and tap-table size
+// (kStage while s*s + 20 bytes per mask allow it, fewer for large s)
 __global__ __launch_bounds__(kBlock) void rise_accum_kernel(const uint8_t* __restrict__ grid, const int32_t* __restrict__ shift,
-                                                            const float* __restrict__ scores, int n_masks, int per_slice, int s,
+                                                            const float* __restrict__ scores, int n_masks, int per_slice, int stage, int s,
                                                             int cell_h, int cell_w, double rh, double rw, int H, int W, double scale,
                                                             double* __restrict__ acc_out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   const int up_h = (s + 1) * cell_h, up_w = (s + 1) * cell_w;
   Tap* rtap = reinterpret_cast<Tap*>(lds_raw);                      // [up_h]
   Tap* ctap = rtap + up_h;                                          // [up_w]
-  float* sc = reinterpret_cast<float*>(ctap + up_w);                // [kStage]
-  int* sh = reinterpret_cast<int*>(sc + kStage);                    // [kStage][2]
-  float* lim = reinterpret_cast<float*>(sh + 2 * kStage);           // [kStage][2] clip range of each mask
-  uint8_t* gs = reinterpret_cast<uint8_t*>(lim + 2 * kStage);       // [kStage][s*s]
+  float* sc = reinterpret_cast<float*>(ctap + up_w);                // [stage]
+  int* sh = reinterpret_cast<int*>(sc + stage);                     // [stage][2]
+  float* lim = reinterpret_cast<float*>(sh + 2 * stage);            // [stage][2] clip range of each mask
+  uint8_t* gs = reinterpret_cast<uint8_t*>(lim + 2 * stage);        // [stage][s*s]
   for (int i = threadIdx.x; i < up_h; i += kBlock) rtap[i] = make_tap(i, s, rh);
   for (int i = threadIdx.x; i < up_w; i += kBlock) ctap[i] = make_tap(i, s, rw);
   const int64_t hw = static_cast<int64_t>(H) * W;
@@ -209,8 +212,8 @@ __global__ __launch_bounds__(kBlock) void rise_accum_kernel(const uint8_t* __res
   const int n_lo = blockIdx.y * per_slice, n_hi = min(n_lo + per_slice, n_masks);
   const int ss = s * s;
   double acc = 0.0;
-  for (int base = n_lo; base < n_hi; base += kStage) {
-    const int cnt = min(kStage, n_hi - base);
+  for (int base = n_lo; base < n_hi; base += stage) {
+    const int cnt = min(stage, n_hi - base);
     __syncthreads();
     for (int i = threadIdx.x; i < cnt; i += kBlock) {
       sc[i] = scores[base + i];
@@ -327,22 +330,28 @@ XAI_EXPORT int xai_rise_accum_f64(const uint8_t* grid, const int32_t* shift, con
   XAI_REQUIRE(H + cell_h - 1 <= (s + 1) * cell_h && W + cell_w - 1 <= (s + 1) * cell_w, XAI_E_SHAPE);
   const int up_h = (s + 1) * cell_h, up_w = (s + 1) * cell_w;
   const double rh = static_cast<double>(s) / static_cast<double>(up_h), rw = static_cast<double>(s) / static_cast<double>(up_w);
-  const size_t lds = static_cast<size_t>(up_h + up_w) * sizeof(Tap) + kStage * (3 * sizeof(float) + 2 * sizeof(int)) +
-                     static_cast<size_t>(kStage) * s * s;
-  XAI_REQUIRE(s <= 64 && lds <= 64 * 1024, XAI_E_UNSUPPORTED);
+  XAI_REQUIRE(s <= 64, XAI_E_UNSUPPORTED);
+  const size_t tap_bytes = static_cast<size_t>(up_h + up_w) * sizeof(Tap);
+  const bool s8 = s == 8 && (reinterpret_cast<uintptr_t>(grid) & 7u) == 0 && cell_h < 32768 && cell_w < 32768;
+  const size_t lds8 = kStage * (sizeof(unsigned long long) + sizeof(float2)) + tap_bytes;
+  // generic kernel: per staged mask one score, two shifts, two clip limits and s*s grid bytes next to the tap tables; as many
+  // masks per round as 64 KiB hold, kStage at most (s <= 14 at 224 x 224 stage all kStage; s = 64 stages 15 at 64 x 128)
+  const size_t per_mask = 3 * sizeof(float) + 2 * sizeof(int) + static_cast<size_t>(s) * s;
+  const size_t room = tap_bytes < 64 * 1024 ? 64 * 1024 - tap_bytes : 0;
+  const int stage = static_cast<int>(std::min<size_t>(kStage, room / per_mask));
+  XAI_REQUIRE(s8 ? lds8 <= 64 * 1024 : stage >= 1, XAI_E_UNSUPPORTED);
   const int64_t hw = static_cast<int64_t>(H) * W;
   const int64_t tiles = xai_ceil_div(hw, kBlock);
   int slices = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(xai_ceil_div(n_masks, 64), xai_ceil_div(2048, tiles))));
   const int per = static_cast<int>(xai_ceil_div(n_masks, slices));
   slices = static_cast<int>(xai_ceil_div(n_masks, per));
   dim3 g(static_cast<unsigned>(tiles), slices);
-  if (s == 8 && (reinterpret_cast<uintptr_t>(grid) & 7u) == 0 && cell_h < 32768 && cell_w < 32768) {
-    const size_t lds8 = kStage * (sizeof(unsigned long long) + sizeof(float2)) + static_cast<size_t>(up_h + up_w) * sizeof(Tap);
+  if (s8) {
     hipLaunchKernelGGL(rise_accum_kernel_s8, g, dim3(kBlock), lds8, static_cast<hipStream_t>(stream), grid, shift, scores, n_masks, per,
                        cell_h, cell_w, rh, rw, H, W, scale, acc);
     return xai_launch_status();
   }
-  hipLaunchKernelGGL(rise_accum_kernel, g, dim3(kBlock), lds, static_cast<hipStream_t>(stream), grid, shift, scores, n_masks, per, s,
-                     cell_h, cell_w, rh, rw, H, W, scale, acc);
+  hipLaunchKernelGGL(rise_accum_kernel, g, dim3(kBlock), tap_bytes + stage * per_mask, static_cast<hipStream_t>(stream), grid, shift, scores,
+                     n_masks, per, stage, s, cell_h, cell_w, rh, rw, H, W, scale, acc);
   return xai_launch_status();
 }

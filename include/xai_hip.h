@@ -145,14 +145,21 @@ int xai_bilinear_up_f32(const float* src, int B, int h, int w, int H, int W, flo
 /* K4  mask_n = crop(upsample(grid_n, (s+1)*cell), shift_n, HxW);  masked_n = image * mask_n
  * replaces  generate_emap.py:72-80 (skimage resize order=1 'reflect' + shift crop) and :91
  *   grid : [n][s][s] uint8 {0,1};  shift : [n][2] int32 (row shift, col shift)
- *   image : [C][H][W];  masked_out : [n][C][H][W] or NULL;  masks_out : [n][H][W] or NULL */
+ *   image : [C][H][W];  masked_out : [n][C][H][W] or NULL;  masks_out : [n][H][W] or NULL
+ *   Limits: s <= 64, n_masks <= 65535, H*W < 2^31 (XAI_E_UNSUPPORTED above); the crop must lie inside the up-sampled grid,
+ *   H + cell_h - 1 <= (s+1)*cell_h and the same along W (XAI_E_SHAPE otherwise; cell = ceil(H/s) always fits). */
 int xai_rise_apply_f32(const uint8_t* grid, const int32_t* shift, int n_masks, int s,
                        int cell_h, int cell_w, const float* image, int C, int H, int W,
                        float* masked_out, float* masks_out, xai_stream_t stream);
 
 /* K5  acc[p] += scale * sum_n scores[n] * mask_n[p]     (masks regenerated from the grid;
  *     fp64 accumulator that may be carried over several calls; the caller rounds to fp32)
- * replaces  generate_emap.py:99-100  (scale = 1/N/p1) */
+ * replaces  generate_emap.py:99-100  (scale = 1/N/p1)
+ *   Limits: every s <= 64 that K4 accepts runs (XAI_E_UNSUPPORTED above).  The tap tables of the up-sampled grid,
+ *   12 * (s+1) * (cell_h + cell_w) bytes, share 64 KiB of LDS with the staged masks: 256 masks of 16 bytes for s == 8 with an
+ *   8-byte aligned grid, else as many masks of 20 + s*s bytes as fit, 256 at most (256 up to s = 14 at 224 x 224, 243 at
+ *   s = 15, 14 at s = 64).  XAI_E_UNSUPPORTED only where not even one mask fits next to the tap tables (s = 64 needs
+ *   cell_h + cell_w <= 78, images up to about 2500 x 2500); the same crop rule as K4 (XAI_E_SHAPE). */
 int xai_rise_accum_f64(const uint8_t* grid, const int32_t* shift, const float* scores,
                        int n_masks, int s, int cell_h, int cell_w, int H, int W, double scale,
                        double* acc, xai_stream_t stream);

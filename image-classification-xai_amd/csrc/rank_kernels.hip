@@ -8,7 +8,9 @@
 //             global atomics on the DESTINATION tile (counts do not depend on arrival order)
 //   scan    : one 256-lane workgroup per map: lane = digit, running sum over tiles, wave-shuffle
 //             exclusive scan over digits -> offs[tile][digit]; flags an identity pass (every key in
-//             one bin, e.g. the sign/exponent byte of a non-negative map)
+//             one bin: all four passes of an all-zero map, the two low bytes of a 0/1 or small-integer map, the
+//             top byte of a map inside [1, 2) -- non-negative values share the top byte only when their
+//             exponents agree in the top seven bits)
 //   scatter : each wave owns 256 consecutive keys, 4 rounds of 64 (coalesced dword loads); the
 //             stable rank inside a round comes from 8 ballots (lanes with the same digit),
 //             across rounds from a per-wave LDS counter row, across waves from a 4-row prefix;

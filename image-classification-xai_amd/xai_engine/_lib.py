@@ -1,98 +1,91 @@
 """ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h).
 
-There is no CPU fallback: if the shared library is missing or a tensor is not on a HIP
-device the call raises.  Build with `make -C image-classification-xai_amd/csrc`
+The header is the one description of the ABI: the argument types, the return types and the two version numbers below are read
+from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if the shared library is missing
+or a tensor is not on a HIP device the call raises.  Build with `make -C image-classification-xai_amd/csrc`
 (or `python -c "import __graft_entry__ as g; g.build()"`).
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libxai_hip.so")
-
-_p = C.c_void_p
-_i = C.c_int
-_l = C.c_int64
-_f = C.c_float
-_d = C.c_double
-
-# name -> argument types, exactly the prototypes of include/xai_hip.h (return type int unless noted)
-SIGNATURES = {
-    "xai_version": [],
-    "xai_version_minor": [],
-    "xai_strerror": [_i],
-    "xai_ig_interp_f32": [_p, _p, _f, _p, _l, _i, _i, _l, _p, _p],
-    "xai_ig_cutoff_f32": [_p, _i, _i, _f, _p, _p],
-    "xai_ig_accum_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p, _f, _i, _l, _p, _p, _p],
-    "xai_ig_accum_timed_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p, _f, _i, _l, _p, _p, _p, _p, _p],
-    "xai_ig_store_grads_f32": [_p, _p, _l, _p],
-    "xai_ig_accum_add_f32": [_p, _i, _p, _l, _p],
-    "xai_ig_finish_f32": [_p, _i, _i, _p, _p, _f, _i, _l, _p, _p, _p],
-    "xai_sumsq_f32": [_p, _i, _l, _p, _p],
-    "xai_idgi_accum_f32": [_p, _i, _p, _p, _l, _p, _p],
-    "xai_gradcam_workspace_bytes": [_i, _i, _i, _i],
-    "xai_gradcam_f32": [_p, _p, _i, _i, _i, _i, _i, _p, _p, C.c_size_t, _p],
-    "xai_bilinear_up_f32": [_p, _i, _i, _i, _i, _i, _f, _i, _p, _p],
-    "xai_rise_apply_f32": [_p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p],
-    "xai_rise_accum_f64": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p],
-    "xai_rank_workspace_bytes": [_i, _l],
-    "xai_rank_f32": [_p, _i, _l, _p, _p, _p, C.c_size_t, _p],
-    "xai_flip_steps_i32": [_p, _l, _i, _i, _p, _p],
-    "xai_perturb_batch_f32": [_p, _p, _p, _i, _l, _i, _i, _p, _p],
-    "xai_segment_sums_f32": [_p, _p, _l, _i, _i, _i, _p, _p, _p],
-    "xai_blur_sep_f32": [_p, _p, _i, _i, _i, _i, _i, _p, _p],
-    "xai_blur_1d_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p],
-    "xai_softmax_stats_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p],
-    "xai_up_rownorm_f32": [_p, _i, _i, _i, _i, _i, _p, _p],
-    "xai_rownorm_f32": [_p, _i, _l, _p, _p],
-    "xai_cluster_sum_f32": [_p, _p, _p, _i, _l, _p, _p],
-    "xai_causal_apply_f32": [_p, _p, _p, _i, _i, _l, _f, _p, _p],
-    "xai_masked_sums_f32": [_p, _p, _i, _l, _p, _p, _p],
-    "xai_attn_head_importance_workspace_bytes": [_i, _i, _i],
-    "xai_attn_head_importance_f32": [_p, _p, _i, _i, _i, _p, _p, C.c_size_t, _p],
-    "xai_rave_matrices_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
-    "xai_rollout_row_f32": [_p, _i, _i, _i, _i, _p, _p],
-    "xai_residual_shares_f32": [_p, _i, _i, _i, _p, _p, _p],
-    "xai_attn_cam_f32": [_p, _p, _i, _i, _i, _p, _p],
-    "xai_gig_init_f32": [_p, _p, _i, _l, _p, _p, _p, _p, _p],
-    "xai_gig_step_f32": [_p, _p, _p, _i, _l, _i, _f, _d, _p, _p, _p, _p, _p],
-    "xai_agi_init_f32": [_p, _p, _p, _i, _i, _i, _l, _p, _p, _p, _p, _p],
-    "xai_agi_step_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _i, _p, _p, _p, _p],
-    "xai_agi_heatmap_f32": [_p, _i, _i, _i, _l, _d, _d, _p, _p, _p, _p],
-    "xai_ablate_features_f32": [_p, _p, _i, _i, _i, _p, _f, _i, _i, _i, _i, _l, _i, _p, _p],
-    "xai_ablate_windows_f32": [_p, _i, _i, _i, _i, _p, _f, _i, _i, _i, _i, _l, _i, _p, _p],
-    "xai_ablation_finish_features_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "xai_ablation_finish_windows_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "xai_bn_act_fwd_f32": [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _p, _p],
-    "xai_bn_relu_bwd_f32": [_p, _p, _p, _p, _p, _f, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p],
-    "xai_maxpool_bwd_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
-    "xai_bn_relu_maxpool_fwd_f32": [_p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
-    "xai_bn_gate_mask_bytes": [_l],
-    "xai_bn_relu_fwd_mask_f32": [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p],
-    "xai_bn_relu_bwd_mask_f32": [_p, _p, _p, _p, _p, _f, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p],
-    "xai_bn_relu_maxpool_fwd_code_f32": [_p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "xai_bn_relu_maxpool_bwd_f32": [_p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
-    "xai_bn_relu_bwd_mask_guided_f32": [_p, _p, _p, _p, _p, _f, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p],
-    "xai_bn_relu_maxpool_bwd_guided_f32": [_p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
-    "xai_guided_map_f32": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "xai_xrai_workspace_bytes": [_i, _i, _i, _l],
-    "xai_xrai_pack_u64": [_p, _p, _p, _i, _p, _l, _i, _i, _i, _p, _p, _p],
-    "xai_xrai_rank_f32": [_p, _p, _p, _p, _i, _l, _i, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, C.c_size_t, _p],
-    "xai_lime_max_features": [],
-    "xai_lime_compose_f32": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _l, _i, _p, _p],
-    "xai_lime_fit_f64": [_p, _i, _p, _p, _i, _i, _i, _i, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p],
-    "xai_lime_paint_f32": [_p, _p, _i, _i, _i, _i, _p, _p],
-}
-_RESTYPE = {"xai_strerror": C.c_char_p, "xai_rank_workspace_bytes": C.c_size_t, "xai_gradcam_workspace_bytes": C.c_size_t,
-            "xai_attn_head_importance_workspace_bytes": C.c_size_t, "xai_bn_gate_mask_bytes": C.c_size_t, "xai_xrai_workspace_bytes": C.c_size_t}
-
-ABI_VERSION, ABI_MINOR = 1, 11      # XAI_ABI_VERSION / XAI_ABI_MINOR of include/xai_hip.h this binding was written against
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "xai_hip.h"))     # csrc/Makefile's -I../../include
 
 _lib = None
 
 
 class XaiHipError(RuntimeError):
     pass
+
+
+_SCALAR = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+           "xai_stream_t": C.c_void_p}
+_POINTER = re.compile(r"(const )?(float|double|void|int32_t|int64_t|uint64_t|uint8_t)\*( const\*)?")
+_RETURN = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+_PROTOTYPE = re.compile(r"(int|size_t|const char\*) (xai_[a-z0-9_]+)\(([^()]*)\)")
+_LAUNCH = ("_f32", "_f64", "_i32", "_u64")            # the entries that launch: they return a code and end in the caller's stream
+
+
+def parse_header(text):
+    """The text of include/xai_hip.h -> ({name: argtypes}, {name: restype}, (XAI_ABI_VERSION, XAI_ABI_MINOR)).  Strict: comments,
+    preprocessor lines, the extern "C" braces and the stream typedef aside, every statement must be `<ret> xai_<name>(<params>)` in
+    the types listed above; anything else raises XaiHipError quoting the statement, nothing gets a default type."""
+    defines, body = {}, []
+    for line in re.sub(r"/\*.*?\*/", " ", text, flags=re.S).splitlines():
+        if line.rstrip().endswith("\\"):
+            raise XaiHipError(f"continued line: {line.strip()!r}")
+        if not line.lstrip().startswith("#"):
+            body.append(line)
+            continue
+        m = re.fullmatch(r"\s*#\s*define (XAI_ABI_VERSION|XAI_ABI_MINOR) (\d+)\s*", line)
+        if m:
+            if m.group(1) in defines:
+                raise XaiHipError(f"defined twice: {line.strip()!r}")
+            defines[m.group(1)] = int(m.group(2))
+    if len(defines) != 2:
+        raise XaiHipError("no `#define XAI_ABI_VERSION <n>` and `#define XAI_ABI_MINOR <n>`")
+    m = re.fullmatch(r'\s*extern "C" \{(.*)\}\s*', "\n".join(body), flags=re.S)
+    if not m:
+        raise XaiHipError('the declarations are not inside one `extern "C" { ... }`')
+    *statements, rest = (" ".join(s.split()) for s in m.group(1).split(";"))
+    if rest:
+        raise XaiHipError(f"not a statement: {rest!r}")
+    if statements.count("typedef void* xai_stream_t") != 1:
+        raise XaiHipError("no single `typedef void* xai_stream_t;`")
+    statements.remove("typedef void* xai_stream_t")
+    argtypes, restypes = {}, {}
+    for st in statements:
+        m = _PROTOTYPE.fullmatch(st)
+        if not m or m.group(2) in argtypes:
+            raise XaiHipError(f"not a prototype this binding can read, or a second one of its name: {st!r}")
+        ret, name, params = m.groups()
+        types = []
+        for p in ([] if params == "void" else params.split(",")):
+            ctype, _, ident = p.strip().rpartition(" ")
+            if not re.fullmatch(r"[A-Za-z_]\w*", ident) or not (ctype in _SCALAR or _POINTER.fullmatch(ctype)):
+                raise XaiHipError(f"parameter {p.strip()!r} has no known type: {st!r}")
+            types.append(ctype)
+        streams = [i for i, t in enumerate(types) if t == "xai_stream_t"]
+        launch = name.endswith(_LAUNCH)
+        if streams != ([len(types) - 1] if launch else []) or launch and ret != "int":
+            raise XaiHipError(f"a launch entry (*{', *'.join(_LAUNCH)}) returns int and takes the stream last, no other takes one: {st!r}")
+        argtypes[name] = [_SCALAR.get(t, C.c_void_p) for t in types]      # not in _SCALAR: one of _POINTER's spellings, checked above
+        restypes[name] = _RETURN[ret]
+    return argtypes, restypes, (defines["XAI_ABI_VERSION"], defines["XAI_ABI_MINOR"])
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except (OSError, XaiHipError) as e:
+        raise XaiHipError(f"{HEADER_PATH}: the C ABI cannot be bound from its header: {e}") from e
+
+
+# name -> argument types / return type of every prototype, and the XAI_ABI_VERSION / XAI_ABI_MINOR the header declares
+SIGNATURES, _RESTYPE, (ABI_VERSION, ABI_MINOR) = _read_header()
 
 
 def load():
@@ -119,7 +112,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the .so is stale
         fn.argtypes = argtypes
-        fn.restype = _RESTYPE.get(name, C.c_int)
+        fn.restype = _RESTYPE[name]
     _lib = lib
     return lib
 

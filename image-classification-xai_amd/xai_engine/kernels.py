@@ -2,11 +2,13 @@
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
 """
+import math
+
 import torch
 
 from . import _lib
 
-F32, I32 = torch.float32, torch.int32
+F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
 
 
 def _need(t, dtype, name):
@@ -46,6 +48,31 @@ def _base_args(baseline, like, name="baseline"):
     return None, float(baseline)
 
 
+def _out(t, name, shape, like, wrong=None, dtype=F32, alloc=torch.empty):
+    """The caller's buffer `t` once it passed _need and holds as many elements as `shape` (else ValueError(wrong)); for None a new
+    tensor from `alloc` on the device of `like` (alloc None: an optional output, None stays None)."""
+    if t is None:
+        return None if alloc is None else alloc(tuple(shape), dtype=dtype, device=like.device)
+    _need(t, dtype, name)
+    if t.numel() != math.prod(shape):
+        raise ValueError(wrong or f"{name} has the wrong size")
+    return t
+
+
+def _workspace(entry, dev, *extents):
+    """-> (uint8 device scratch of `entry`(*extents) bytes, or None for 0 bytes; the byte count)"""
+    nbytes = getattr(_lib.load(), entry)(*extents)
+    return (torch.empty(nbytes, dtype=U8, device=dev) if nbytes else None), nbytes
+
+
+def _shaped_like(t, like, name, like_name, dtype=F32):
+    """An operand (None: absent) that must have the shape of `like`."""
+    if t is not None:
+        _need(t, dtype, name)
+        if t.shape != like.shape:
+            raise ValueError(f"{name} must have the shape of {like_name}")
+
+
 # ------------------------------------------------------------------------------ IG
 def ig_interp(x, baseline, alphas, out=None):
     """x: (n_img, *img) ; alphas: (n_alpha,) shared or (n_img, n_alpha) -> (n_img, n_alpha, *img)."""
@@ -59,12 +86,7 @@ def ig_interp(x, baseline, alphas, out=None):
             raise ValueError("alphas must be (n_alpha,) or (n_img, n_alpha)")
         n_alpha, stride = alphas.shape[1], alphas.shape[1]
     b, bs = _base_args(baseline, x)
-    if out is None:
-        out = torch.empty((n_img, n_alpha) + tuple(x.shape[1:]), dtype=F32, device=x.device)
-    else:
-        _need(out, F32, "out")
-        if out.numel() != n_img * n_alpha * n_elem:
-            raise ValueError("out has the wrong size")
+    out = _out(out, "out", (n_img, n_alpha) + tuple(x.shape[1:]), x)
     _call("xai_ig_interp_f32", x.device, _ptr(x), _ptr(b), bs, _ptr(alphas), stride, n_img, n_alpha, n_elem, _ptr(out))
     return out
 
@@ -171,8 +193,7 @@ def gradcam(act, grad, relu=True):
         raise ValueError("act and grad must both be (B,C,h,w)")
     B, Cc, h, w = act.shape
     cam = torch.empty((B, h, w), dtype=F32, device=act.device)
-    nbytes = _lib.load().xai_gradcam_workspace_bytes(B, Cc, h, w)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=act.device) if nbytes else None
+    ws, nbytes = _workspace("xai_gradcam_workspace_bytes", act.device, B, Cc, h, w)
     _call("xai_gradcam_f32", act.device, _ptr(act), _ptr(grad), B, Cc, h, w, int(bool(relu)), _ptr(cam), _ptr(ws), nbytes)
     return cam
 
@@ -192,10 +213,7 @@ def rise_apply(grid, shift, cell, image, want_masked=True, want_masks=False, out
     _need(grid, torch.uint8, "grid"); _need(shift, I32, "shift"); _need(image, F32, "image")
     n, s = grid.shape[0], grid.shape[1]
     Cc, H, W = image.shape
-    masked = None
-    if want_masked:
-        masked = out if out is not None else torch.empty((n, Cc, H, W), dtype=F32, device=image.device)
-        _need(masked, F32, "out")
+    masked = _out(out, "out", (n, Cc, H, W), image) if want_masked else None
     masks = torch.empty((n, H, W), dtype=F32, device=image.device) if want_masks else None
     _call("xai_rise_apply_f32", image.device, _ptr(grid), _ptr(shift), n, s, int(cell[0]), int(cell[1]), _ptr(image), Cc, H, W,
           _ptr(masked), _ptr(masks))
@@ -210,10 +228,7 @@ def rise_accum(grid, shift, scores, cell, H, W, scale, acc=None):
     n, s = grid.shape[0], grid.shape[1]
     if scores.numel() != n:
         raise ValueError("one score per mask")
-    if acc is None:
-        acc = torch.zeros((H, W), dtype=torch.float64, device=grid.device)
-    else:
-        _need(acc, torch.float64, "acc")
+    acc = _out(acc, "acc", (H, W), grid, dtype=F64, alloc=torch.zeros)
     _call("xai_rise_accum_f64", grid.device, _ptr(grid), _ptr(shift), _ptr(scores), n, s, int(cell[0]), int(cell[1]), int(H), int(W),
           float(scale), _ptr(acc))
     return acc
@@ -224,11 +239,10 @@ def rank(sal):
     """sal (n_seg, hw) -> (order, rank) int32: stable ascending argsort and its inverse."""
     _need(sal, F32, "sal")
     n_seg, hw = sal.shape
-    lib = _lib.load()
-    ws = torch.empty(lib.xai_rank_workspace_bytes(n_seg, hw), dtype=torch.uint8, device=sal.device)
+    ws, nbytes = _workspace("xai_rank_workspace_bytes", sal.device, n_seg, hw)
     order = torch.empty((n_seg, hw), dtype=I32, device=sal.device)
     rk = torch.empty((n_seg, hw), dtype=I32, device=sal.device)
-    _call("xai_rank_f32", sal.device, _ptr(sal), n_seg, hw, _ptr(order), _ptr(rk), _ptr(ws), ws.numel())
+    _call("xai_rank_f32", sal.device, _ptr(sal), n_seg, hw, _ptr(order), _ptr(rk), _ptr(ws), nbytes)
     return order, rk
 
 
@@ -247,12 +261,7 @@ def perturb_batch(start, finish, flip, first_step, n_batch, out=None):
     hw = start[0].numel()
     if finish.shape != start.shape or flip.numel() != hw:
         raise ValueError("start/finish/flip_step shapes disagree")
-    if out is None:
-        out = torch.empty((n_batch,) + tuple(start.shape), dtype=F32, device=start.device)
-    else:
-        _need(out, F32, "out")
-        if out.numel() != n_batch * Cc * hw:
-            raise ValueError("out has the wrong size")
+    out = _out(out, "out", (n_batch,) + tuple(start.shape), start)
     _call("xai_perturb_batch_f32", start.device, _ptr(start), _ptr(finish), _ptr(flip), Cc, hw, int(first_step), int(n_batch), _ptr(out))
     return out
 
@@ -377,22 +386,40 @@ def causal_apply(x, masks, noise, noise_scale=0.1):
 
 
 # ------------------------------------------------------------------------------ opt-in classifier-side fusion
+def _need_bn(weight, bias, mean, var, suffix=""):
+    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
+        _need(t, F32, name + suffix)
+
+
+def _bn2_fwd(bn2):
+    """bn2 = (weight, bias, mean, var, eps) of the identity operand's own BatchNorm, or None -> the five ABI arguments"""
+    if bn2 is None:
+        return None, None, None, None, 0.0
+    w2, b2, m2, v2, eps2 = bn2
+    _need_bn(w2, b2, m2, v2, "2")
+    return w2, b2, m2, v2, eps2
+
+
+def _bn2_bwd(bn2, want_identity):
+    """bn2 = (weight2, var2, eps2) or None -> (the three ABI arguments, want_identity): with bn2 g_identity is always wanted"""
+    if bn2 is None:
+        return None, None, 0.0, want_identity
+    w2, v2, eps2 = bn2
+    _need(w2, F32, "weight2"); _need(v2, F32, "var2")
+    return w2, v2, eps2, True
+
+
+def _pooled(H, W, kernel, stride, pad):
+    return (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1
+
+
 def bn_act_fwd(x, identity, weight, bias, mean, var, eps, variant, relu=True, bn2=None):
     """y = act(bn(x) [+ identity]) for eval-mode BatchNorm2d statistics; x (N,C,H,W) contiguous.
     bn2 = (weight, bias, mean, var, eps): the identity operand gets its own BatchNorm first (down-sample branch)."""
     _need(x, F32, "x")
-    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
-        _need(t, F32, name)
-    if identity is not None:
-        _need(identity, F32, "identity")
-        if identity.shape != x.shape:
-            raise ValueError("identity must have the shape of x")
-    w2 = b2 = m2 = v2 = None
-    eps2 = 0.0
-    if bn2 is not None:
-        w2, b2, m2, v2, eps2 = bn2
-        for name, t in (("weight2", w2), ("bias2", b2), ("mean2", m2), ("var2", v2)):
-            _need(t, F32, name)
+    _need_bn(weight, bias, mean, var)
+    _shaped_like(identity, x, "identity", "x")
+    w2, b2, m2, v2, eps2 = _bn2_fwd(bn2)
     N, Cc = x.shape[0], x.shape[1]
     HW = x[0, 0].numel()
     y = torch.empty_like(x)
@@ -405,16 +432,8 @@ def bn_relu_bwd(gy, y, weight, var, eps, variant, want_identity=False, gy2=None,
     """-> (gx, g_identity or None) for y = relu(bn(x) [+ identity]); the incoming gradient is gy (+ gy2).
     bn2 = (weight2, var2, eps2): g_identity is the gradient of the identity operand BEFORE its own BatchNorm."""
     _need(gy, F32, "gy"); _need(y, F32, "y"); _need(weight, F32, "weight"); _need(var, F32, "var")
-    if gy2 is not None:
-        _need(gy2, F32, "gy2")
-        if gy2.shape != gy.shape:
-            raise ValueError("gy2 must have the shape of gy")
-    w2 = v2 = None
-    eps2 = 0.0
-    if bn2 is not None:
-        w2, v2, eps2 = bn2
-        _need(w2, F32, "weight2"); _need(v2, F32, "var2")
-        want_identity = True
+    _shaped_like(gy2, gy, "gy2", "gy")
+    w2, v2, eps2, want_identity = _bn2_bwd(bn2, want_identity)
     N, Cc = y.shape[0], y.shape[1]
     HW = y[0, 0].numel()
     gx = torch.empty_like(y)
@@ -436,11 +455,9 @@ def maxpool_bwd(gy, indices, H, W, kernel, stride, pad):
 def bn_relu_maxpool_fwd(x, weight, bias, mean, var, eps, variant, kernel, stride, pad):
     """max_pool2d(relu(bn(x)), kernel, stride, pad) for inference; x (N,C,H,W) -> (N,C,PH,PW)."""
     _need(x, F32, "x")
-    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
-        _need(t, F32, name)
+    _need_bn(weight, bias, mean, var)
     N, Cc, H, W = x.shape
-    PH = (H + 2 * pad - kernel) // stride + 1
-    PW = (W + 2 * pad - kernel) // stride + 1
+    PH, PW = _pooled(H, W, kernel, stride, pad)
     y = torch.empty((N, Cc, PH, PW), dtype=F32, device=x.device)
     _call("xai_bn_relu_maxpool_fwd_f32", x.device, _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(var), float(eps), int(variant),
           N, Cc, H, W, PH, PW, int(kernel), int(stride), int(pad), _ptr(y))
@@ -457,18 +474,9 @@ def bn_relu_fwd_mask(x, identity, weight, bias, mean, var, eps, variant, bn2=Non
     `mask` (uint8 storage of bn_gate_mask_bytes(x.numel()) bytes, allocated here unless given; every word is written) for
     bn_relu_bwd_mask.  The bit layout is private to the two kernels."""
     _need(x, F32, "x")
-    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
-        _need(t, F32, name)
-    if identity is not None:
-        _need(identity, F32, "identity")
-        if identity.shape != x.shape:
-            raise ValueError("identity must have the shape of x")
-    w2 = b2 = m2 = v2 = None
-    eps2 = 0.0
-    if bn2 is not None:
-        w2, b2, m2, v2, eps2 = bn2
-        for name, t in (("weight2", w2), ("bias2", b2), ("mean2", m2), ("var2", v2)):
-            _need(t, F32, name)
+    _need_bn(weight, bias, mean, var)
+    _shaped_like(identity, x, "identity", "x")
+    w2, b2, m2, v2, eps2 = _bn2_fwd(bn2)
     N, Cc = x.shape[0], x.shape[1]
     HW = x[0, 0].numel()
     need = bn_gate_mask_bytes(x.numel())
@@ -492,16 +500,8 @@ def bn_relu_bwd_mask(gy, mask, weight, var, eps, variant, want_identity=False, g
         raise ValueError("gy must be (N, C, ...)")
     if mask.numel() < bn_gate_mask_bytes(gy.numel()):
         raise ValueError(f"mask has {mask.numel()} bytes, needs {bn_gate_mask_bytes(gy.numel())}")
-    if gy2 is not None:
-        _need(gy2, F32, "gy2")
-        if gy2.shape != gy.shape:
-            raise ValueError("gy2 must have the shape of gy")
-    w2 = v2 = None
-    eps2 = 0.0
-    if bn2 is not None:
-        w2, v2, eps2 = bn2
-        _need(w2, F32, "weight2"); _need(v2, F32, "var2")
-        want_identity = True
+    _shaped_like(gy2, gy, "gy2", "gy")
+    w2, v2, eps2, want_identity = _bn2_bwd(bn2, want_identity)
     N, Cc = gy.shape[0], gy.shape[1]
     HW = gy[0, 0].numel()
     gx = torch.empty_like(gy)
@@ -515,11 +515,9 @@ def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, s
     """-> (y, code): max_pool2d(relu(bn(x)), kernel, stride, pad) and one uint8 per pooled output for bn_relu_maxpool_bwd (the
     window-local arg-max, or 255 for a closed ReLU gate); x (N,C,H,W) -> (N,C,PH,PW) twice."""
     _need(x, F32, "x")
-    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
-        _need(t, F32, name)
+    _need_bn(weight, bias, mean, var)
     N, Cc, H, W = x.shape
-    PH = (H + 2 * pad - kernel) // stride + 1
-    PW = (W + 2 * pad - kernel) // stride + 1
+    PH, PW = _pooled(H, W, kernel, stride, pad)
     y = torch.empty((N, Cc, PH, PW), dtype=F32, device=x.device)
     code = torch.empty((N, Cc, PH, PW), dtype=torch.uint8, device=x.device)
     _call("xai_bn_relu_maxpool_fwd_code_f32", x.device, _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(var), float(eps), int(variant),
@@ -530,13 +528,8 @@ def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, s
 def bn_relu_maxpool_bwd(gy, code, weight, var, eps, variant, H, W, kernel, stride, pad, gy2=None, guided=False):
     """Input gradient (N,C,H,W) of the fused stem from the gradient(s) gy (+ gy2) of its pooled output and the forward's codes.
     guided: Guided Backprop's rule -- each position's sum over the windows that selected it goes through g <= 0 ? +0 : g."""
-    _need(gy, F32, "gy"); _need(code, torch.uint8, "code"); _need(weight, F32, "weight"); _need(var, F32, "var")
-    if code.shape != gy.shape:
-        raise ValueError("code must have the shape of gy")
-    if gy2 is not None:
-        _need(gy2, F32, "gy2")
-        if gy2.shape != gy.shape:
-            raise ValueError("gy2 must have the shape of gy")
+    _need(gy, F32, "gy"); _shaped_like(code, gy, "code", "gy", U8); _need(weight, F32, "weight"); _need(var, F32, "var")
+    _shaped_like(gy2, gy, "gy2", "gy")
     N, Cc, PH, PW = gy.shape
     gx = torch.empty((N, Cc, int(H), int(W)), dtype=F32, device=gy.device)
     _call("xai_bn_relu_maxpool_bwd_guided_f32" if guided else "xai_bn_relu_maxpool_bwd_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(code), _ptr(weight), _ptr(var), float(eps), int(variant),
@@ -561,13 +554,9 @@ def guided_map(grad, cam=None, want_attr=True, want_map=False, attr=None, map=No
     if not (want_attr or want_map):
         raise ValueError("nothing to compute: neither the attribution nor the map")
     if want_attr:
-        attr = torch.empty_like(grad) if attr is None else _need(attr, F32, "attr")
-        if attr.numel() != grad.numel():
-            raise ValueError("attr has the wrong size")
+        attr = _out(attr, "attr", grad.shape, grad)
     if want_map:
-        map = torch.empty((B, H, W), dtype=F32, device=grad.device) if map is None else _need(map, F32, "map")
-        if map.numel() != B * H * W:
-            raise ValueError("map has the wrong size")
+        map = _out(map, "map", (B, H, W), grad)
     _call("xai_guided_map_f32", grad.device, _ptr(grad), _ptr(cam), B, Cc, H, W, int(h), int(w), _ptr(attr if want_attr else None),
           _ptr(map if want_map else None))
     if want_attr and want_map:
@@ -612,8 +601,7 @@ def attn_head_importance(attns, grads):
     dev = attns[0].device
     L, (H, S, _) = len(attns), attns[0].shape
     Ih = torch.empty((L, H), dtype=F32, device=dev)
-    nbytes = _lib.load().xai_attn_head_importance_workspace_bytes(L, H, S)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace("xai_attn_head_importance_workspace_bytes", dev, L, H, S)
     atab, gtab = _table(attns, dev), _table(grads, dev)        # held until the launch: a freed table's block is reused at once
     _call("xai_attn_head_importance_f32", dev, _ptr(atab), _ptr(gtab), L, H, S, _ptr(Ih), _ptr(ws), nbytes)
     return Ih
@@ -720,7 +708,6 @@ def gig_step(x_input, x_baseline, grad, steps, fraction, max_dist, x, attr, l1_t
 
 # ------------------------------------------------------------------------------ AGI (K23-K25)
 AGI_REASON = {0: "running", 1: "reached the class", 2: "skipped: the class is init_pred", 3: "max_iter updates"}
-I64 = torch.int64
 
 
 def _agi_pairs(data, classes, x_cur, c_delta, state, name):
@@ -770,13 +757,10 @@ def agi_heatmap(c_delta, n_img, q_lo=80, q_hi=99, out=None, step_grad=None, qu=N
     if not (0.0 <= float(q_lo) <= 100.0 and 0.0 <= float(q_hi) <= 100.0):
         raise ValueError("agi_heatmap: percentiles must be in [0, 100]")
     K, C, H, W = c_delta.shape[0] // n_img, c_delta.shape[1], c_delta.shape[2], c_delta.shape[3]
-    if out is None:
-        out = torch.empty((n_img, H, W), dtype=F32, device=c_delta.device)
-    for t, nm, cnt in ((out, "out", n_img * H * W), (step_grad, "step_grad", n_img * C * H * W), (qu, "qu", 2 * n_img)):
-        if t is not None:
-            _need(t, F32, nm)
-            if t.numel() != cnt:
-                raise ValueError(f"agi_heatmap: {nm} must hold {cnt} elements")
+    hold = "agi_heatmap: {} must hold {} elements".format
+    out = _out(out, "out", (n_img, H, W), c_delta, hold("out", n_img * H * W))
+    _out(step_grad, "step_grad", (n_img, C, H, W), c_delta, hold("step_grad", n_img * C * H * W), alloc=None)
+    _out(qu, "qu", (n_img, 2), c_delta, hold("qu", 2 * n_img), alloc=None)
     _call("xai_agi_heatmap_f32", c_delta.device, _ptr(c_delta), n_img, K, C, H * W, float(q_lo), float(q_hi), _ptr(out), _ptr(step_grad),
           _ptr(qu))
     return out
@@ -816,12 +800,7 @@ def _ablation_rows(x, n_total, first, n, out):
     B, Cc, H, W = x.shape
     if not (n >= 1 and 0 <= first and first + n <= B * n_total):
         raise ValueError(f"rows [{first}, {first + n}) are not inside the {B} x {n_total} altered images")
-    if out is None:
-        return torch.empty((n, Cc, H, W), dtype=F32, device=x.device)
-    _need(out, F32, "out")
-    if out.numel() != n * Cc * H * W:
-        raise ValueError("out has the wrong size")
-    return out
+    return _out(out, "out", (n, Cc, H, W), x)
 
 
 def ablate_features(x, ids, id_min, n_total, baseline, first, n, out=None):
@@ -890,7 +869,6 @@ def ablation_finish_windows(s0, scores, window, strides, shape, g=None, want_att
 
 
 # ------------------------------------------------------------------------------ XRAI (K29, K30)
-U8 = torch.uint8
 XRAI_STATUS = {1: "masks remain but none has a gain above -inf (NaN or -inf in the attribution): the reference crashes at this "
                   "point with KeyError on remaining_masks[None] (XRAIBuilder.py:682)",
                2: "a full-mask gain is NaN: the order of the reference's sort (XRAIBuilder.py:754-755) is undefined"}
@@ -940,8 +918,7 @@ def xrai_rank(attr, bits, span, mask_first, min_pixel_diff, area_threshold, fast
     sel_key = torch.empty(M, dtype=I32, device=dev)
     sel_gain = torch.empty(M, dtype=F32, device=dev)
     state = torch.empty((B, 4), dtype=I32, device=dev)
-    nbytes = _lib.load().xai_xrai_workspace_bytes(B, H, W, M)
-    ws = torch.empty(nbytes, dtype=U8, device=dev)
+    ws, nbytes = _workspace("xai_xrai_workspace_bytes", dev, B, H, W, M)
     _call("xai_xrai_rank_f32", dev, _ptr(attr), _ptr(bits) if M else None, _ptr(span) if M else None, _ptr(mask_first), B, M, H, W,
           int(min_pixel_diff), float(area_threshold), int(bool(fast)), _ptr(out), _ptr(pixel_iter), _ptr(sel_key) if M else None,
           _ptr(sel_gain) if M else None, _ptr(state), _ptr(ws), nbytes)
@@ -949,9 +926,6 @@ def xrai_rank(attr, bits, span, mask_first, min_pixel_diff, area_threshold, fast
 
 
 # ------------------------------------------------------------------------------ LIME (K31, K32, K33)
-F64 = torch.float64
-
-
 def lime_max_features():
     """The largest number of superpixels of one image K32 fits."""
     return int(_lib.load().xai_lime_max_features())

@@ -1,7 +1,8 @@
-"""ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h).
+"""ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h) and of the extension library libxai_ext.so
+(include/xai_hip_ext.h: the entry points added after xai_hip.h was frozen at ABI 1.11).
 
-The header is the one description of the ABI: the argument types, the return types and the two version numbers below are read
-from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if the shared library is missing
+Each header is the one description of its ABI: the argument types, the return types and the two version numbers below are read
+from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing
 or a tensor is not on a HIP device the call raises.  Build with `make -C image-classification-xai_amd/csrc`
 (or `python -c "import __graft_entry__ as g; g.build()"`).
 """
@@ -12,8 +13,13 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libxai_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "xai_hip.h"))     # csrc/Makefile's -I../../include
+EXT_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext.so")
+EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext.h")
+ABI_DEFINES = ("XAI_ABI_VERSION", "XAI_ABI_MINOR")
+EXT_DEFINES = ("XAI_EXT_VERSION", "XAI_EXT_MINOR")
 
 _lib = None
+_ext = None
 
 
 class XaiHipError(RuntimeError):
@@ -28,24 +34,26 @@ _PROTOTYPE = re.compile(r"(int|size_t|const char\*) (xai_[a-z0-9_]+)\(([^()]*)\)
 _LAUNCH = ("_f32", "_f64", "_i32", "_u64")            # the entries that launch: they return a code and end in the caller's stream
 
 
-def parse_header(text):
+def parse_header(text, defines=ABI_DEFINES):
     """The text of include/xai_hip.h -> ({name: argtypes}, {name: restype}, (XAI_ABI_VERSION, XAI_ABI_MINOR)).  Strict: comments,
     preprocessor lines, the extern "C" braces and the stream typedef aside, every statement must be `<ret> xai_<name>(<params>)` in
-    the types listed above; anything else raises XaiHipError quoting the statement, nothing gets a default type."""
-    defines, body = {}, []
+    the types listed above; anything else raises XaiHipError quoting the statement, nothing gets a default type.
+    `defines`: the names of the header's two version defines (EXT_DEFINES for include/xai_hip_ext.h)."""
+    major_name, minor_name = defines
+    found, body = {}, []
     for line in re.sub(r"/\*.*?\*/", " ", text, flags=re.S).splitlines():
         if line.rstrip().endswith("\\"):
             raise XaiHipError(f"continued line: {line.strip()!r}")
         if not line.lstrip().startswith("#"):
             body.append(line)
             continue
-        m = re.fullmatch(r"\s*#\s*define (XAI_ABI_VERSION|XAI_ABI_MINOR) (\d+)\s*", line)
+        m = re.fullmatch(rf"\s*#\s*define ({major_name}|{minor_name}) (\d+)\s*", line)
         if m:
-            if m.group(1) in defines:
+            if m.group(1) in found:
                 raise XaiHipError(f"defined twice: {line.strip()!r}")
-            defines[m.group(1)] = int(m.group(2))
-    if len(defines) != 2:
-        raise XaiHipError("no `#define XAI_ABI_VERSION <n>` and `#define XAI_ABI_MINOR <n>`")
+            found[m.group(1)] = int(m.group(2))
+    if len(found) != 2:
+        raise XaiHipError(f"no `#define {major_name} <n>` and `#define {minor_name} <n>`")
     m = re.fullmatch(r'\s*extern "C" \{(.*)\}\s*', "\n".join(body), flags=re.S)
     if not m:
         raise XaiHipError('the declarations are not inside one `extern "C" { ... }`')
@@ -73,7 +81,7 @@ def parse_header(text):
             raise XaiHipError(f"a launch entry (*{', *'.join(_LAUNCH)}) returns int and takes the stream last, no other takes one: {st!r}")
         argtypes[name] = [_SCALAR.get(t, C.c_void_p) for t in types]      # not in _SCALAR: one of _POINTER's spellings, checked above
         restypes[name] = _RETURN[ret]
-    return argtypes, restypes, (defines["XAI_ABI_VERSION"], defines["XAI_ABI_MINOR"])
+    return argtypes, restypes, (found[major_name], found[minor_name])
 
 
 def _read_header():
@@ -84,8 +92,18 @@ def _read_header():
         raise XaiHipError(f"{HEADER_PATH}: the C ABI cannot be bound from its header: {e}") from e
 
 
+def _read_ext_header():
+    try:
+        with open(EXT_HEADER_PATH) as f:
+            return parse_header(f.read(), EXT_DEFINES)
+    except (OSError, XaiHipError) as e:
+        raise XaiHipError(f"{EXT_HEADER_PATH}: the extension ABI cannot be bound from its header: {e}") from e
+
+
 # name -> argument types / return type of every prototype, and the XAI_ABI_VERSION / XAI_ABI_MINOR the header declares
 SIGNATURES, _RESTYPE, (ABI_VERSION, ABI_MINOR) = _read_header()
+# the same for the extension header and its XAI_EXT_VERSION / XAI_EXT_MINOR
+EXT_SIGNATURES, _EXT_RESTYPE, (EXT_VERSION, EXT_MINOR) = _read_ext_header()
 
 
 def load():
@@ -114,6 +132,30 @@ def load():
         fn.argtypes = argtypes
         fn.restype = _RESTYPE[name]
     _lib = lib
+    return lib
+
+
+def load_ext():
+    """Load the extension library once, as strictly as `load()`: absent -> XaiHipError, the version pair first, then every
+    prototype of include/xai_hip_ext.h (AttributeError if the .so is stale).  Never falls back."""
+    global _ext
+    if _ext is not None:
+        return _ext
+    csrc = os.path.join(os.path.dirname(_HERE), "csrc")
+    if not os.path.exists(EXT_LIB_PATH):
+        raise XaiHipError(f"{EXT_LIB_PATH} not found: the HIP extension library is not built. Run `make -C {csrc}` (needs hipcc, "
+                          "targets gfx950). There is deliberately no CPU fallback.")
+    lib = C.CDLL(EXT_LIB_PATH)
+    lib.xai_ext_version.restype = lib.xai_ext_version_minor.restype = C.c_int
+    major, minor = lib.xai_ext_version(), lib.xai_ext_version_minor()
+    if major != EXT_VERSION or minor < EXT_MINOR:
+        raise XaiHipError(f"{EXT_LIB_PATH} has ABI {major}.{minor}, this package needs {EXT_VERSION}.{EXT_MINOR} or a later minor "
+                          f"(include/xai_hip_ext.h); rebuild with `make -C {csrc}`")
+    for name, argtypes in EXT_SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError if the .so is stale
+        fn.argtypes = argtypes
+        fn.restype = _EXT_RESTYPE[name]
+    _ext = lib
     return lib
 
 

@@ -38,6 +38,13 @@ def _call(name, dev, *args):
         _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
 
 
+def _call_ext(name, dev, *args):
+    """`_call` for an entry of the extension library (include/xai_hip_ext.h); the error texts are xai_strerror's."""
+    lib = _lib.load_ext()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+
+
 def _base_args(baseline, like, name="baseline"):
     """tensor baseline -> (ptr, 0.0); python scalar -> (None, value)."""
     if isinstance(baseline, torch.Tensor):
@@ -1002,3 +1009,59 @@ def lime_paint(table, seg):
     out = torch.empty((B, H, W), dtype=F32, device=seg.device)
     _call("xai_lime_paint_f32", seg.device, _ptr(table), _ptr(seg), B, table.shape[1], H, W, _ptr(out))
     return out
+
+
+# ------------------------------------------------------------------------------ GradientShap (K34, K35; libxai_ext.so)
+def _gshap_rows(x, baselines, idx, n_rows, n_samples, name):
+    """x (B, ...) per image or (B * n_samples, ...) per row, baselines (N_b, ...) of the same item shape, idx int64 (n_rows,)
+    -> (x_per_row, N_b, elements per item)"""
+    _need(x, F32, "x"); _need(baselines, F32, "baselines"); _need(idx, I64, "idx")
+    n_samples = int(n_samples)
+    if n_samples < 1 or n_rows % n_samples:
+        raise ValueError(f"{name}: {n_rows} rows are no multiple of n_samples = {n_samples}")
+    if x.dim() < 2 or baselines.dim() != x.dim() or baselines.shape[1:] != x.shape[1:] or baselines.shape[0] == 0 or x[0].numel() == 0:
+        raise ValueError(f"{name}: baselines must be (N_b,) + {tuple(x.shape[1:])}, got {tuple(baselines.shape)}")
+    if x.shape[0] not in (n_rows, n_rows // n_samples):
+        raise ValueError(f"{name}: x must hold {n_rows // n_samples} images or {n_rows} rows, got {x.shape[0]}")
+    if idx.numel() != n_rows:
+        raise ValueError(f"{name}: idx must hold {n_rows} values, got {idx.numel()}")
+    # n_samples == 1: one row per image either way, the two layouts coincide
+    return int(x.shape[0] == n_rows and n_samples > 1), baselines.shape[0], x[0].numel()
+
+
+def gshap_scale(x, baselines, alpha, idx, n_samples, out=None):
+    """K34: out[r] = alpha[r] * xr[r] + (1 - alpha[r]) * baselines[idx[r]] for the R = alpha.numel() rows of GradientShap, two
+    products and a sum in fp32.  x (R / n_samples, ...) one input per image (row r reads image r // n_samples) or (R, ...) one per
+    row; baselines (N_b, ...); alpha float32 (R,), idx int64 (R,) in [0, N_b) on the device -> (R, ...)."""
+    _need(alpha, F32, "alpha")
+    R = alpha.numel()
+    per_row, n_base, E = _gshap_rows(x, baselines, idx, R, n_samples, "gshap_scale")
+    out = _out(out, "out", (R,) + tuple(x.shape[1:]), x)
+    _call_ext("xai_gshap_scale_f32", x.device, _ptr(x), _ptr(baselines), _ptr(alpha), _ptr(idx), R, int(n_samples), E, n_base, per_row,
+              _ptr(out))
+    return out
+
+
+def gshap_finish(grads, x, baselines, idx, n_samples, want_attr=True, want_map=False, attr=None, map=None):
+    """K35: grads (B * n_samples, C, H, W) -> attr (B, C, H, W) = the mean over an image's samples of (xr - baselines[idx]) * grads
+    (summed ascending from +0, divided by n_samples) and/or the harness map (B, H, W) = |sum over channels, left to right|.
+    x per image or per row as for K34.  -> attr, map, or (attr, map).  `attr` / `map`: preallocated outputs."""
+    _need(grads, F32, "grads")
+    if grads.dim() != 4:
+        raise ValueError("grads must be (B * n_samples, C, H, W)")
+    R, Cc, H, W = grads.shape
+    per_row, n_base, _ = _gshap_rows(x, baselines, idx, R, n_samples, "gshap_finish")
+    if x.shape[1:] != grads.shape[1:]:
+        raise ValueError(f"gshap_finish: x must be (.., {Cc}, {H}, {W}), got {tuple(x.shape)}")
+    if not (want_attr or want_map):
+        raise ValueError("nothing to compute: neither the attribution nor the map")
+    B = R // int(n_samples)
+    if want_attr:
+        attr = _out(attr, "attr", (B, Cc, H, W), grads)
+    if want_map:
+        map = _out(map, "map", (B, H, W), grads)
+    _call_ext("xai_gshap_finish_f32", grads.device, _ptr(grads), _ptr(x), _ptr(baselines), _ptr(idx), B, int(n_samples), Cc, H * W, n_base,
+              per_row, _ptr(attr if want_attr else None), _ptr(map if want_map else None))
+    if want_attr and want_map:
+        return attr, map
+    return attr if want_attr else map

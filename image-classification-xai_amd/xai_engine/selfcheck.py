@@ -1,6 +1,6 @@
 """Installation self-check: `python -m xai_engine.selfcheck [--device cuda:0]`.
 
-Runs every kernel of libxai_hip.so once on random data and compares it with the equivalent torch
+Runs every kernel of libxai_hip.so and libxai_ext.so once on random data and compares it with the equivalent torch
 expression evaluated ON THE SAME DEVICE (this is a smoke test for a deployment, not the parity suite --
 that lives in tests/ and uses the CPU oracle).  Exit code 0 when everything agrees.
 """
@@ -149,6 +149,22 @@ def run(device="cuda:0", verbose=True):
         at, mp = K.guided_map(gg, cm, want_attr=True, want_map=True)
         want = gg * F.interpolate(cm[:, None], shp[2:], mode="nearest")
         check(f"guided_map {shp[2]}x{shp[3]} (bitwise vs torch)", float((at != want).sum() + (mp != ((want[:, 0] + want[:, 1]) + want[:, 2]).abs()).sum()), 0.0)
+    # K34 / K35 (libxai_ext.so): GradientShap's interpolants, and its mean over the samples with the harness's |sum over channels|
+    for shp, nb, per_row in (((3, 56, 56), 3, False), ((3, 7, 7), 1, True)):
+        nB, nS = 2, 5
+        xs_, bl_, gg = rnd(nB * nS if per_row else nB, *shp), rnd(nb, *shp), rnd(nB * nS, *shp)
+        al_ = torch.rand(nB * nS, device=dev, generator=gen)
+        ix_ = torch.randint(0, nb, (nB * nS,), device=dev, generator=gen)
+        xr_, a4 = xs_ if per_row else xs_.repeat_interleave(nS, 0), al_.view(-1, 1, 1, 1)
+        tag = f"{shp[1]}x{shp[2]} {'per row' if per_row else 'per image'}"
+        check(f"gshap_scale {tag} (bitwise vs torch)", float((K.gshap_scale(xs_, bl_, al_, ix_, nS) != a4 * xr_ + (1 - a4) * bl_[ix_]).sum()), 0.0)
+        at, mp = K.gshap_finish(gg, xs_, bl_, ix_, nS, want_attr=True, want_map=True)
+        term = ((xr_ - bl_[ix_]) * gg).view(nB, nS, *shp)
+        want = torch.zeros_like(term[:, 0])
+        for s in range(nS):
+            want = want + term[:, s]
+        want = want / torch.full((), nS, dtype=want.dtype, device=dev)           # a tensor divisor: a true division on the device
+        check(f"gshap_finish {tag} (bitwise vs torch)", float((at != want).sum() + (mp != ((want[:, 0] + want[:, 1]) + want[:, 2]).abs()).sum()), 0.0)
     # K16 and the stream workers
     rows, wts = rnd(37, 200).abs(), rnd(37)
     wsum, psum = K.masked_sums(rows, wts)

@@ -32,8 +32,9 @@ from .streams import LOGIT_RTOL, CapturedCall, ThreadGraphs
 
 KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LERF_res", "MORF_res", "MONO_pos", "MONO_neg")
 # ("lime" stands in front of "sg": the reference's place for it is between ggc and fa, :168-170, but the tuple's tail and the
-# neighbours of "xrai" are pinned by the rows that came before it)
-CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "lime", "sg", "xrai", "gc", "gbp", "ggc", "fa", "occ")
+# neighbours of "xrai" are pinned by the rows that came before it; "gs", the reference's :164-167 behind ggc, stands behind "lime"
+# for the same reason)
+CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "lime", "gs", "sg", "xrai", "gc", "gbp", "ggc", "fa", "occ")
 TRANS_ATTR_FUNCS = ("agi", "lime")   # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 
@@ -100,6 +101,14 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         model.eval()
         sal = lime.lime_batch(torch.as_tensor(trans_img).to(torch.float32)[None].to(dev), model, segmenter, num_samples=1000, top_labels=5,
                               hide_color=0, random_state=testing_dict.get("lime_random_state"))[0]
+    elif attr_function == "gs":
+        # :164-167: captum's GradientShap(model) with one baseline, torch.randn(1, 3, 224, 224) drawn on the CPU from torch's global
+        # generator (here at the harness's img_hw) and then uploaded, so a seeded run draws the reference's baseline; 5 samples,
+        # no noise, NumPy's global state for the coefficients; |sum over channels| (:181) straight from K35
+        from .gshap import gradient_shap_batch
+        baselines = torch.randn(1, 3, img_hw, img_hw)
+        sal = gradient_shap_batch(input_tensor.to(dev), model, target_class, baselines.to(dev), n_samples=5, want_attr=False,
+                                  want_map=True)[0]
     elif attr_function == "sg":
         saliency_map = smoothGrad("IG", input_tensor, model, 50, baseline, target_class, device)
     elif attr_function == "xrai":

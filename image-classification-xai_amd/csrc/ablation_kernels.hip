@@ -154,26 +154,16 @@ int launch_ablate(const float* x, const int32_t* ids, int ids_C, int id_min, con
   XAI_REQUIRE(first + n <= static_cast<int64_t>(B) * n_total, XAI_E_SHAPE);
   const int64_t hw = static_cast<int64_t>(H) * W;
   const bool vec = xai_can_vec4(hw, {x, out, ids, baseline});
-  const int64_t tiles = xai_ceil_div(hw, kBlock * (vec ? 4 : 1));
-  int per, zdim = 1;
-  if (static_cast<int64_t>(n) * C * hw * 4 >= (int64_t(64) << 20) && C <= 64) {
-    per = n >= 2 ? 2 : 1;                        // HBM-sized pass: one channel x two rows per lane (K6's shape)
-    zdim = C;
-  } else {
-    const int c0 = static_cast<int>(std::min<int64_t>(n, std::max<int64_t>(1, xai_ceil_div(2048, tiles))));
-    per = static_cast<int>(xai_ceil_div(n, c0));
-  }
-  const int chunks = static_cast<int>(xai_ceil_div(n, per));
-  XAI_REQUIRE(chunks <= 65535 && tiles <= INT32_MAX, XAI_E_UNSUPPORTED);
-  const dim3 grid(static_cast<unsigned>(tiles), chunks, zdim);
+  // HBM-sized pass (64 MiB): one channel x two rows per lane
+  const XaiRowPlan plan = xai_row_chunk_plan(hw, kBlock, vec, n, C, 1, int64_t(64) << 20, true);
+  XAI_REQUIRE(plan.ok && plan.tiles <= INT32_MAX, XAI_E_UNSUPPORTED);
+  const dim3 grid(static_cast<unsigned>(plan.tiles), static_cast<unsigned>(plan.chunks), plan.zdim);
   const int64_t id_cstride = ids_C > 1 ? hw : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL((ablate_kernel<4, WIN>), grid, dim3(kBlock), 0, st, x, ids, id_cstride, id_min, g, baseline, baseline_scalar, C,
-                       hw, n_total, static_cast<int>(first), n, per, out);
-  else
-    hipLaunchKernelGGL((ablate_kernel<1, WIN>), grid, dim3(kBlock), 0, st, x, ids, id_cstride, id_min, g, baseline, baseline_scalar, C,
-                       hw, n_total, static_cast<int>(first), n, per, out);
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL((ablate_kernel<V4 ? 4 : 1, WIN>), grid, dim3(kBlock), 0, st, x, ids, id_cstride, id_min, g, baseline,
+                       baseline_scalar, C, hw, n_total, static_cast<int>(first), n, plan.per, out);
+  });
   return xai_launch_status();
 }
 

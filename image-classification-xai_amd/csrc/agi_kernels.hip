@@ -280,12 +280,11 @@ XAI_EXPORT int xai_agi_init_f32(const float* logits, const float* data, const in
   XAI_REQUIRE(static_cast<int64_t>(n_img) * n_cls <= 65535 && n_elem < (int64_t{1} << 31), XAI_E_UNSUPPORTED);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const int n_pair = n_img * n_cls;
-  if (xai_can_vec4(n_elem, {data, x_cur, c_delta}))
-    hipLaunchKernelGGL(agi_init_kernel<4>, dim3(chunks_for(n_elem, 4), n_pair), dim3(kBlock), 0, st, logits, data, classes, n_cls,
-                       n_out, n_elem, init_pred, x_cur, c_delta, state);
-  else
-    hipLaunchKernelGGL(agi_init_kernel<1>, dim3(chunks_for(n_elem, 1), n_pair), dim3(kBlock), 0, st, logits, data, classes, n_cls,
-                       n_out, n_elem, init_pred, x_cur, c_delta, state);
+  xai_dispatch(xai_can_vec4(n_elem, {data, x_cur, c_delta}), [&](auto V4) {
+    constexpr int V = V4 ? 4 : 1;
+    hipLaunchKernelGGL(agi_init_kernel<V>, dim3(chunks_for(n_elem, V), n_pair), dim3(kBlock), 0, st, logits, data, classes, n_cls, n_out,
+                       n_elem, init_pred, x_cur, c_delta, state);
+  });
   return xai_launch_status();
 }
 
@@ -304,12 +303,11 @@ XAI_EXPORT int xai_agi_step_f32(const float* logits, const float* g_adv, const f
                      n_out, max_iter, state);
   int rc = xai_launch_status();
   if (rc != XAI_OK) return rc;
-  if (xai_can_vec4(n_elem, {g_adv, g_lab, data, x_cur, c_delta}))
-    hipLaunchKernelGGL(agi_update_kernel<4>, dim3(chunks_for(n_elem, 4), n_pair), dim3(kBlock), 0, st, g_adv, g_lab, data, n_cls,
-                       n_elem, epsilon, state, x_cur, c_delta);
-  else
-    hipLaunchKernelGGL(agi_update_kernel<1>, dim3(chunks_for(n_elem, 1), n_pair), dim3(kBlock), 0, st, g_adv, g_lab, data, n_cls,
-                       n_elem, epsilon, state, x_cur, c_delta);
+  xai_dispatch(xai_can_vec4(n_elem, {g_adv, g_lab, data, x_cur, c_delta}), [&](auto V4) {
+    constexpr int V = V4 ? 4 : 1;
+    hipLaunchKernelGGL(agi_update_kernel<V>, dim3(chunks_for(n_elem, V), n_pair), dim3(kBlock), 0, st, g_adv, g_lab, data, n_cls, n_elem,
+                       epsilon, state, x_cur, c_delta);
+  });
   return xai_launch_status();
 }
 

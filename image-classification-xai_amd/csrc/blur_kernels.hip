@@ -191,18 +191,13 @@ XAI_EXPORT int xai_blur_sep_f32(const float* x, const float* k1d, int klen, int 
   const int pitch = klen == 31 ? 96 : ((TW + 2 * r) | 1);
   const size_t lds32 = static_cast<size_t>((32 + 2 * r) * pitch + 3 + (32 + 2 * r) * TW) * sizeof(float);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (tiles16 >= 8 * static_cast<int64_t>(xai_cu_count()) && lds32 <= 64 * 1024) {
-    constexpr int TH = 32;
-    const size_t lds = lds32;
-    dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH, B * C);
-    if (klen == 31) hipLaunchKernelGGL((blur_sep_kernel<TH, 31>), grid, dim3(kBlock), lds, st, x, k1d, klen, H, W, out);
-    else            hipLaunchKernelGGL((blur_sep_kernel<TH, 0>), grid, dim3(kBlock), lds, st, x, k1d, klen, H, W, out);
-  } else {
-    constexpr int TH = 16;
+  xai_dispatch(tiles16 >= 8 * static_cast<int64_t>(xai_cu_count()) && lds32 <= 64 * 1024, [&](auto TALL) {
+    constexpr int TH = TALL ? 32 : 16;
     const size_t lds = static_cast<size_t>((TH + 2 * r) * pitch + 3 + (TH + 2 * r) * TW) * sizeof(float);
-    dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH, B * C);
-    if (klen == 31) hipLaunchKernelGGL((blur_sep_kernel<TH, 31>), grid, dim3(kBlock), lds, st, x, k1d, klen, H, W, out);
-    else            hipLaunchKernelGGL((blur_sep_kernel<TH, 0>), grid, dim3(kBlock), lds, st, x, k1d, klen, H, W, out);
-  }
+    const dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH, B * C);
+    xai_dispatch(klen == 31, [&](auto K31) {
+      hipLaunchKernelGGL((blur_sep_kernel<TH, K31 ? 31 : 0>), grid, dim3(kBlock), lds, st, x, k1d, klen, H, W, out);
+    });
+  });
   return xai_launch_status();
 }

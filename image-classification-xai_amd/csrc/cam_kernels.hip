@@ -130,13 +130,12 @@ XAI_EXPORT int xai_gradcam_f32(const float* act, const float* grad, int B, int C
   float* dst = slices == 1 ? cam : static_cast<float*>(ws);
   const size_t lds = static_cast<size_t>(kWaves) * hw * sizeof(float);
   dim3 grid(slices, B), block(kWaves * kWave);
-#define XAI_CAM(P) hipLaunchKernelGGL(gradcam_kernel<P>, grid, block, lds, st, act, grad, C, hw, relu, per, dst)
-  if (hw <= 64) XAI_CAM(1);
-  else if (hw <= 128) XAI_CAM(2);
-  else if (hw <= 256) XAI_CAM(4);
-  else if (hw <= 512) XAI_CAM(8);
-  else XAI_CAM(16);
-#undef XAI_CAM
+  const auto launch = [&](auto P) { hipLaunchKernelGGL(gradcam_kernel<decltype(P)::value>, grid, block, lds, st, act, grad, C, hw, relu, per, dst); };
+  if (hw <= 64) launch(std::integral_constant<int, 1>{});
+  else if (hw <= 128) launch(std::integral_constant<int, 2>{});
+  else if (hw <= 256) launch(std::integral_constant<int, 4>{});
+  else if (hw <= 512) launch(std::integral_constant<int, 8>{});
+  else launch(std::integral_constant<int, 16>{});
   if (slices > 1)
     hipLaunchKernelGGL(gradcam_finish_kernel, dim3((hw + 255) / 256, B), dim3(256), 0, st, static_cast<const float*>(ws), slices, hw,
                        relu, cam);
@@ -220,14 +219,11 @@ XAI_EXPORT int xai_guided_map_f32(const float* grad, const float* cam, int B, in
   XAI_REQUIRE(cam == nullptr || (h > 0 && w > 0), XAI_E_SHAPE);
   const bool vec = xai_can_vec4(W, {grad, attr, map});
   const int64_t n_units = static_cast<int64_t>(B) * H * (W / (vec ? 4 : 1));
-  const int64_t blocks = xai_ceil_div(n_units, 256);
-  XAI_REQUIRE(blocks <= INT32_MAX, XAI_E_UNSUPPORTED);
+  unsigned blocks;
+  XAI_REQUIRE(xai_blocks_checked(n_units, 256, &blocks), XAI_E_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL(guided_map_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, grad, cam, C, H, W, h, w, n_units, attr,
-                       map);
-  else
-    hipLaunchKernelGGL(guided_map_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, grad, cam, C, H, W, h, w, n_units, attr,
-                       map);
+  xai_dispatch(vec, [&](auto VEC) {
+    hipLaunchKernelGGL(guided_map_kernel<VEC>, dim3(blocks), dim3(256), 0, st, grad, cam, C, H, W, h, w, n_units, attr, map);
+  });
   return xai_launch_status();
 }

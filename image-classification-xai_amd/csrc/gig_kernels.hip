@@ -244,10 +244,9 @@ XAI_EXPORT int xai_gig_init_f32(const float* x_input, const float* x_baseline, i
   XAI_REQUIRE(n_img > 0 && n_elem > 0, XAI_E_SHAPE);
   XAI_REQUIRE(n_img <= 65535 && n_elem <= kMaxElems, XAI_E_UNSUPPORTED);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (xai_can_vec4(n_elem, {x_input, x_baseline, x, attr}))
-    hipLaunchKernelGGL(gig_init_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
-  else
-    hipLaunchKernelGGL(gig_init_kernel<1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
+  xai_dispatch(xai_can_vec4(n_elem, {x_input, x_baseline, x, attr}), [&](auto V4) {
+    hipLaunchKernelGGL(gig_init_kernel<V4 ? 4 : 1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, n_elem, x, attr, l1_total, state);
+  });
   return xai_launch_status();
 }
 
@@ -264,11 +263,9 @@ XAI_EXPORT int xai_gig_step_f32(const float* x_input, const float* x_baseline, c
   const float r = fraction * static_cast<float>(n_elem - 1);
   const uint32_t rank = static_cast<uint32_t>(floorf(r));
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (xai_can_vec4(n_elem, {x_input, x_baseline, grad, x, attr}))
-    hipLaunchKernelGGL(gig_step_kernel<4>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, grad, n_elem, steps, max_dist, rank, x,
-                       attr, l1_total, state);
-  else
-    hipLaunchKernelGGL(gig_step_kernel<1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, grad, n_elem, steps, max_dist, rank, x,
-                       attr, l1_total, state);
+  xai_dispatch(xai_can_vec4(n_elem, {x_input, x_baseline, grad, x, attr}), [&](auto V4) {
+    hipLaunchKernelGGL(gig_step_kernel<V4 ? 4 : 1>, dim3(n_img), dim3(kThreads), 0, st, x_input, x_baseline, grad, n_elem, steps, max_dist,
+                       rank, x, attr, l1_total, state);
+  });
   return xai_launch_status();
 }

@@ -139,15 +139,13 @@ XAI_EXPORT int xai_gshap_scale_f32(const float* x, const float* baselines, const
   XAI_REQUIRE(n_rows % n_samples == 0, XAI_E_SHAPE);
   const bool vec = xai_can_vec4(n_elem, {x, baselines, out});
   const int64_t n_units = static_cast<int64_t>(n_rows / n_samples) * (n_elem / (vec ? 4 : 1));
-  const int64_t blocks = xai_ceil_div(n_units, 256);
-  XAI_REQUIRE(blocks <= INT32_MAX, XAI_E_UNSUPPORTED);
+  unsigned blocks;
+  XAI_REQUIRE(xai_blocks_checked(n_units, 256, &blocks), XAI_E_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL(gshap_scale_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, x, baselines, alpha, idx, n_samples,
-                       n_elem, n_base, x_per_row, n_units, out);
-  else
-    hipLaunchKernelGGL(gshap_scale_kernel<1>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, x, baselines, alpha, idx, n_samples,
-                       n_elem, n_base, x_per_row, n_units, out);
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL(gshap_scale_kernel<V4 ? 4 : 1>, dim3(blocks), dim3(256), 0, st, x, baselines, alpha, idx, n_samples, n_elem,
+                       n_base, x_per_row, n_units, out);
+  });
   return xai_launch_status();
 }
 
@@ -162,14 +160,12 @@ XAI_EXPORT int xai_gshap_finish_f32(const float* grads, const float* x, const fl
   XAI_REQUIRE(static_cast<int64_t>(B) * n_samples <= INT32_MAX, XAI_E_UNSUPPORTED);
   const bool vec = xai_can_vec4(HW, {grads, x, baselines, attr, map});
   const int64_t n_units = static_cast<int64_t>(B) * (HW / (vec ? 4 : 1));
-  const int64_t blocks = xai_ceil_div(n_units, 256);
-  XAI_REQUIRE(blocks <= INT32_MAX, XAI_E_UNSUPPORTED);
+  unsigned blocks;
+  XAI_REQUIRE(xai_blocks_checked(n_units, 256, &blocks), XAI_E_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL(gshap_finish_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, grads, x, baselines, idx, n_samples,
-                       C, HW, n_base, x_per_row, n_units, attr, map);
-  else
-    hipLaunchKernelGGL(gshap_finish_kernel<1>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, grads, x, baselines, idx, n_samples,
-                       C, HW, n_base, x_per_row, n_units, attr, map);
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL(gshap_finish_kernel<V4 ? 4 : 1>, dim3(blocks), dim3(256), 0, st, grads, x, baselines, idx, n_samples, C, HW,
+                       n_base, x_per_row, n_units, attr, map);
+  });
   return xai_launch_status();
 }

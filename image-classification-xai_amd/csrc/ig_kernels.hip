@@ -387,23 +387,16 @@ XAI_EXPORT int xai_ig_interp_f32(const float* x, const float* baseline, float ba
   // two step rows per lane: on this part HBM writes like MANY concurrent row streams (5.98 TB/s at 2 rows per
   // lane vs 5.42 TB/s at 50, tune/tune_write.hip); x and b re-reads hit L2
   const bool vec = xai_can_vec4(n_elem, {x, baseline, out});
-  const int64_t tiles = xai_ceil_div(n_elem, kBlock * (vec ? 4 : 1));
-  int per, chunks;
-  const bool hbm_sized = static_cast<int64_t>(n_img) * n_alpha * n_elem * 4 >= (int64_t(256) << 20);
-  if (hbm_sized) {
-    per = n_alpha >= 2 ? 2 : 1;                                   // HBM-sized output: many short streams, non-temporal
-  } else {                                                        // cache-sized output: just enough workgroups to fill the chip
-    const int c0 = static_cast<int>(std::min<int64_t>(n_alpha, std::max<int64_t>(1, xai_ceil_div(2048, tiles * n_img))));
-    per = static_cast<int>(xai_ceil_div(n_alpha, c0));
-  }
-  chunks = static_cast<int>(xai_ceil_div(n_alpha, per));
-  XAI_REQUIRE(chunks <= 65535, XAI_E_UNSUPPORTED);
-  dim3 grid(static_cast<unsigned>(tiles), chunks, n_img);
-#define XAI_INTERP(W, NT) \
-  hipLaunchKernelGGL((ig_interp_kernel<W, NT>), grid, dim3(kBlock), 0, st, x, baseline, baseline_scalar, alphas, alpha_img_stride, n_alpha, n_elem, per, out)
-  if (vec) { if (hbm_sized) XAI_INTERP(4, true); else XAI_INTERP(4, false); }
-  else     { if (hbm_sized) XAI_INTERP(1, true); else XAI_INTERP(1, false); }
-#undef XAI_INTERP
+  // HBM-sized output (256 MiB over all images): non-temporal; a cache-sized one gets just enough workgroups to fill the chip
+  const XaiRowPlan plan = xai_row_chunk_plan(n_elem, kBlock, vec, n_alpha, 1, n_img, int64_t(256) << 20, false);
+  XAI_REQUIRE(plan.ok, XAI_E_UNSUPPORTED);
+  const dim3 grid(static_cast<unsigned>(plan.tiles), static_cast<unsigned>(plan.chunks), n_img);
+  xai_dispatch(vec, [&](auto V4) {
+    xai_dispatch(plan.hbm, [&](auto NT) {
+      hipLaunchKernelGGL((ig_interp_kernel<V4 ? 4 : 1, NT>), grid, dim3(kBlock), 0, st, x, baseline, baseline_scalar, alphas,
+                         alpha_img_stride, n_alpha, n_elem, plan.per, out);
+    });
+  });
   return xai_launch_status();
 }
 
@@ -418,6 +411,12 @@ XAI_EXPORT int xai_ig_cutoff_f32(const float* logits, int n_img, int n_steps, fl
 // The launch of K2.  ev0 / ev1 (both or neither): the kernel's own start / stop timestamps are recorded into the caller's
 // events by the dispatch itself (hipExtLaunchKernelGGL) -- a timing without the ~5 us of dispatch latency that two events
 // bracketing a launch include.
+template <typename K, typename... A>
+static void launch_timed(K kernel, dim3 grid, dim3 block, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, A... args) {
+  if (ev0) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, ev0, ev1, 0, args...);
+  else hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+
 static int ig_accum_impl(const float* grads, int n_img, int n_steps, const int32_t* n_use_dev, int n_use_host,
                          const float* step_w1, const float* step_w2, const float* x, const float* baseline,
                          float baseline_scalar, int C, int64_t hw, float* out_chw, float* out_abs_hw,
@@ -435,30 +434,26 @@ static int ig_accum_impl(const float* grads, int n_img, int n_steps, const int32
     const int64_t items = static_cast<int64_t>(n_img) * (hw / 4);
     const int cus = xai_cu_count();
     const bool big = items >= static_cast<int64_t>(cus) * 2 * 256 * 2;
-#define XAI_STREAM(BLK, IT, SU, CC, WT, GRID) \
-  do { if (ev0) hipExtLaunchKernelGGL((ig_accum_stream_kernel<BLK, IT, SU, CC, WT>), dim3(GRID), dim3(BLK), 0, st, ev0, ev1, 0, grads, n_steps, \
-                                      n_use_dev, n_use_host, step_w1, step_w2, x, baseline, baseline_scalar, hw, n_img, out_chw, out_abs_hw); \
-       else hipLaunchKernelGGL((ig_accum_stream_kernel<BLK, IT, SU, CC, WT>), dim3(GRID), dim3(BLK), 0, st, grads, n_steps, n_use_dev, n_use_host, \
-                               step_w1, step_w2, x, baseline, baseline_scalar, hw, n_img, out_chw, out_abs_hw); } while (0)
-  // small (cache-resident, latency-bound) problems: few lanes, so each keeps 5 steps x C loads in flight
-#define XAI_STREAM_C(CC, WT) \
-  do { if (big) XAI_STREAM(256, 4, 1, CC, WT, static_cast<unsigned>(cus * 2)); \
-       else XAI_STREAM(64, 1, 5, CC, WT, static_cast<unsigned>(xai_ceil_div(items, 64))); } while (0)
-    if (C == 3) { if (step_w1) XAI_STREAM_C(3, true); else XAI_STREAM_C(3, false); }
-    else        { if (step_w1) XAI_STREAM_C(1, true); else XAI_STREAM_C(1, false); }
-#undef XAI_STREAM_C
-#undef XAI_STREAM
+    xai_dispatch(C == 3, [&](auto C3) {
+      xai_dispatch(step_w1 != nullptr, [&](auto WT) {
+        xai_dispatch(big, [&](auto BIG) {
+          // small (cache-resident, latency-bound) problems: few lanes, so each keeps 5 steps x C loads in flight
+          constexpr int BLK = BIG ? 256 : 64, IT = BIG ? 4 : 1, SU = BIG ? 1 : 5, CC = C3 ? 3 : 1;
+          const unsigned wgs = static_cast<unsigned>(BIG ? cus * 2 : xai_ceil_div(items, 64));
+          launch_timed(ig_accum_stream_kernel<BLK, IT, SU, CC, WT>, dim3(wgs), dim3(BLK), st, ev0, ev1, grads, n_steps, n_use_dev,
+                       n_use_host, step_w1, step_w2, x, baseline, baseline_scalar, hw, n_img, out_chw, out_abs_hw);
+        });
+      });
+    });
     return xai_launch_status();
   }
-  dim3 grid(static_cast<unsigned>(xai_ceil_div(hw, kBlock * (vec ? 4 : 1))), n_img);
-#define XAI_ACCUM(W, WT) \
-  do { if (ev0) hipExtLaunchKernelGGL((ig_accum_kernel<W, WT>), grid, dim3(kBlock), 0, st, ev0, ev1, 0, grads, n_steps, n_use_dev, n_use_host, \
-                                      step_w1, step_w2, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw); \
-       else hipLaunchKernelGGL((ig_accum_kernel<W, WT>), grid, dim3(kBlock), 0, st, grads, n_steps, n_use_dev, n_use_host, step_w1, \
-                               step_w2, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw); } while (0)
-  if (vec) { if (step_w1) XAI_ACCUM(4, true); else XAI_ACCUM(4, false); }
-  else     { if (step_w1) XAI_ACCUM(1, true); else XAI_ACCUM(1, false); }
-#undef XAI_ACCUM
+  const dim3 grid(xai_grid_x(hw, kBlock, vec), n_img);
+  xai_dispatch(vec, [&](auto V4) {
+    xai_dispatch(step_w1 != nullptr, [&](auto WT) {
+      launch_timed(ig_accum_kernel<V4 ? 4 : 1, WT>, grid, dim3(kBlock), st, ev0, ev1, grads, n_steps, n_use_dev, n_use_host, step_w1,
+                   step_w2, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw);
+    });
+  });
   return xai_launch_status();
 }
 
@@ -484,10 +479,10 @@ XAI_EXPORT int xai_ig_store_grads_f32(const float* src, float* dst, int64_t n_el
   XAI_REQUIRE(n_elem > 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = static_cast<unsigned>(xai_cu_count() * 8);
-  if (xai_can_vec4(n_elem, {src, dst}))
-    hipLaunchKernelGGL(store_stream_kernel, dim3(grid), dim3(kBlock), 0, st, src, dst, n_elem / 4);
-  else
-    hipLaunchKernelGGL(store_stream_scalar_kernel, dim3(grid), dim3(kBlock), 0, st, src, dst, n_elem);
+  xai_dispatch(xai_can_vec4(n_elem, {src, dst}), [&](auto V4) {
+    constexpr auto kernel = V4 ? store_stream_kernel : store_stream_scalar_kernel;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, src, dst, n_elem / (V4 ? 4 : 1));
+  });
   return xai_launch_status();
 }
 
@@ -496,9 +491,8 @@ XAI_EXPORT int xai_ig_accum_add_f32(const float* grads, int n_batch, float* acc,
   XAI_REQUIRE(n_batch > 0 && n_elem > 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool vec = xai_can_vec4(n_elem, {grads, acc});
-  dim3 grid(static_cast<unsigned>(xai_ceil_div(n_elem, kBlock * (vec ? 4 : 1))));
-  if (vec) hipLaunchKernelGGL(ig_accum_add_kernel<4>, grid, dim3(kBlock), 0, st, grads, n_batch, acc, n_elem);
-  else     hipLaunchKernelGGL(ig_accum_add_kernel<1>, grid, dim3(kBlock), 0, st, grads, n_batch, acc, n_elem);
+  const dim3 grid(xai_grid_x(n_elem, kBlock, vec));
+  xai_dispatch(vec, [&](auto V4) { hipLaunchKernelGGL(ig_accum_add_kernel<V4 ? 4 : 1>, grid, dim3(kBlock), 0, st, grads, n_batch, acc, n_elem); });
   return xai_launch_status();
 }
 
@@ -510,9 +504,10 @@ XAI_EXPORT int xai_ig_finish_f32(const float* acc, int n_img, int n_steps, const
   XAI_REQUIRE(n_img <= 65535, XAI_E_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool vec = xai_can_vec4(hw, {acc, x, baseline, out_chw, out_abs_hw});
-  dim3 grid(static_cast<unsigned>(xai_ceil_div(hw, kBlock * (vec ? 4 : 1))), n_img);
-  if (vec) hipLaunchKernelGGL(ig_finish_kernel<4>, grid, dim3(kBlock), 0, st, acc, n_steps, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw);
-  else     hipLaunchKernelGGL(ig_finish_kernel<1>, grid, dim3(kBlock), 0, st, acc, n_steps, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw);
+  const dim3 grid(xai_grid_x(hw, kBlock, vec), n_img);
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL(ig_finish_kernel<V4 ? 4 : 1>, grid, dim3(kBlock), 0, st, acc, n_steps, x, baseline, baseline_scalar, C, hw, out_chw, out_abs_hw);
+  });
   return xai_launch_status();
 }
 
@@ -529,8 +524,7 @@ XAI_EXPORT int xai_idgi_accum_f32(const float* grads, int n_steps, const float* 
   XAI_REQUIRE(n_steps > 1 && n_elem > 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool vec = xai_can_vec4(n_elem, {grads, out});
-  dim3 grid(static_cast<unsigned>(xai_ceil_div(n_elem, kBlock * (vec ? 4 : 1))));
-  if (vec) hipLaunchKernelGGL(idgi_accum_kernel<4>, grid, dim3(kBlock), 0, st, grads, n_steps, logits, sumsq, n_elem, out);
-  else     hipLaunchKernelGGL(idgi_accum_kernel<1>, grid, dim3(kBlock), 0, st, grads, n_steps, logits, sumsq, n_elem, out);
+  const dim3 grid(xai_grid_x(n_elem, kBlock, vec));
+  xai_dispatch(vec, [&](auto V4) { hipLaunchKernelGGL(idgi_accum_kernel<V4 ? 4 : 1>, grid, dim3(kBlock), 0, st, grads, n_steps, logits, sumsq, n_elem, out); });
   return xai_launch_status();
 }

@@ -312,12 +312,6 @@ __global__ __launch_bounds__(kFitThreads) void fit_kernel(const uint64_t* __rest
   }
 }
 
-template <int V>
-void launch_compose(const float* x, const int32_t* seg, const uint64_t* rows, const int32_t* Dv, int words, const float* hide,
-                    const float* fudged, int C, int64_t hw, int n_samples, int first, int n, int per, dim3 grid, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(compose_kernel<V>, grid, dim3(kBlock), 0, st, x, seg, rows, Dv, words, hide, fudged, C, hw, n_samples, first, n, per, out);
-}
-
 }  // namespace
 
 XAI_EXPORT int xai_lime_max_features(void) { return kMaxD; }
@@ -333,21 +327,17 @@ XAI_EXPORT int xai_lime_compose_f32(const float* x, const int32_t* seg, const ui
   XAI_REQUIRE(words <= kRowWordsLds, XAI_E_UNSUPPORTED);
   const int64_t hw = static_cast<int64_t>(H) * W, chw = hw * C;
   const bool vec = xai_can_vec4(chw, {x, out, fudged});
-  const int64_t tiles = xai_ceil_div(chw, kBlock * (vec ? 4 : 1));
-  int per;
-  if (static_cast<int64_t>(n) * chw * 4 >= (int64_t(64) << 20)) {
-    per = n >= 2 ? 2 : 1;                        // HBM-sized pass: two rows per lane (K26's shape)
-  } else {
-    const int c0 = static_cast<int>(std::min<int64_t>(n, std::max<int64_t>(1, xai_ceil_div(2048, tiles))));
-    per = static_cast<int>(xai_ceil_div(n, c0));
-  }
-  per = std::max(1, std::min(per, kRowWordsLds / words));
+  // the row spans the channels; HBM-sized pass (64 MiB): two rows per lane.  The rows of a chunk must also fit the LDS stage.
+  const XaiRowPlan plan = xai_row_chunk_plan(chw, kBlock, vec, n, 1, 1, int64_t(64) << 20, false);
+  const int per = std::max(1, std::min(plan.per, kRowWordsLds / words));
   const int64_t chunks = xai_ceil_div(n, per);
-  XAI_REQUIRE(chunks <= 65535 && tiles <= INT32_MAX, XAI_E_UNSUPPORTED);
-  const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(chunks));
+  XAI_REQUIRE(chunks <= 65535 && plan.tiles <= INT32_MAX, XAI_E_UNSUPPORTED);
+  const dim3 grid(static_cast<unsigned>(plan.tiles), static_cast<unsigned>(chunks));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec) launch_compose<4>(x, seg, rows, D, words, hide, fudged, C, hw, n_samples, static_cast<int>(first), n, per, grid, out, st);
-  else launch_compose<1>(x, seg, rows, D, words, hide, fudged, C, hw, n_samples, static_cast<int>(first), n, per, grid, out, st);
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL(compose_kernel<V4 ? 4 : 1>, grid, dim3(kBlock), 0, st, x, seg, rows, D, words, hide, fudged, C, hw, n_samples,
+                       static_cast<int>(first), n, per, out);
+  });
   return xai_launch_status();
 }
 
@@ -369,9 +359,8 @@ XAI_EXPORT int xai_lime_paint_f32(const float* table, const int32_t* seg, int B,
   XAI_REQUIRE_PTR(table); XAI_REQUIRE_PTR(seg); XAI_REQUIRE_PTR(out);
   XAI_REQUIRE(B > 0 && d_stride > 0 && H > 0 && W > 0, XAI_E_SHAPE);
   const int64_t hw = static_cast<int64_t>(H) * W, total = hw * B;
-  const int64_t blocks = xai_ceil_div(total, kBlock);
-  XAI_REQUIRE(blocks <= INT32_MAX, XAI_E_UNSUPPORTED);
-  hipLaunchKernelGGL(paint_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), table, seg,
-                     d_stride, hw, total, out);
+  unsigned blocks;
+  XAI_REQUIRE(xai_blocks_checked(total, kBlock, &blocks), XAI_E_UNSUPPORTED);
+  hipLaunchKernelGGL(paint_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), table, seg, d_stride, hw, total, out);
   return xai_launch_status();
 }

@@ -302,13 +302,11 @@ XAI_EXPORT int xai_masked_sums_f32(const float* rows, const float* weights, int 
                                    xai_stream_t stream) {
   XAI_REQUIRE_PTR(rows); XAI_REQUIRE_PTR(weights); XAI_REQUIRE_PTR(out_weighted); XAI_REQUIRE_PTR(out_plain);
   XAI_REQUIRE(N > 0 && P > 0, XAI_E_SHAPE);
-  if (xai_can_vec4(P, {rows})) {
-    hipLaunchKernelGGL(masked_sums_kernel<4>, dim3(static_cast<unsigned>(xai_ceil_div(P, kBlock * 4))), dim3(kBlock), 0,
+  const bool vec = xai_can_vec4(P, {rows});
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL(masked_sums_kernel<V4 ? 4 : 1>, dim3(xai_grid_x(P, kBlock, vec)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), rows, weights, N, P, out_weighted, out_plain);
-  } else {
-    hipLaunchKernelGGL(masked_sums_kernel<1>, dim3(static_cast<unsigned>(xai_ceil_div(P, kBlock))), dim3(kBlock), 0,
-                       static_cast<hipStream_t>(stream), rows, weights, N, P, out_weighted, out_plain);
-  }
+  });
   return xai_launch_status();
 }
 
@@ -320,10 +318,9 @@ XAI_EXPORT int xai_up_rownorm_f32(const float* src, int R, int h, int w, int H, 
   XAI_REQUIRE(H <= kMaxTaps, XAI_E_UNSUPPORTED);
   XAI_REQUIRE(H >= h && W >= w, XAI_E_UNSUPPORTED);     // shrinking: the reference's antialias filter is no longer these two taps
   const size_t lds = (static_cast<size_t>((h * W + 3) & ~3) + 4 * static_cast<size_t>(H)) * sizeof(float);
-  if (xai_can_vec4(W, {out}))
-    hipLaunchKernelGGL(up_rownorm_kernel<true>, dim3(R), dim3(kBlock), lds, static_cast<hipStream_t>(stream), src, h, w, H, W, out);
-  else
-    hipLaunchKernelGGL(up_rownorm_kernel<false>, dim3(R), dim3(kBlock), lds, static_cast<hipStream_t>(stream), src, h, w, H, W, out);
+  xai_dispatch(xai_can_vec4(W, {out}), [&](auto VEC) {
+    hipLaunchKernelGGL(up_rownorm_kernel<VEC>, dim3(R), dim3(kBlock), lds, static_cast<hipStream_t>(stream), src, h, w, H, W, out);
+  });
   return xai_launch_status();
 }
 
@@ -340,10 +337,9 @@ XAI_EXPORT int xai_rownorm_f32(const float* x, int R, int64_t P, float* out, xai
     if (slices > 32) slices = 32;
   }
   const unsigned grid = static_cast<unsigned>(kXcds * slices * xai_ceil_div(R, kXcds));
-  if (xai_can_vec4(P, {x, out}))
-    hipLaunchKernelGGL(rownorm_kernel<true>, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, R, P, slices, out);
-  else
-    hipLaunchKernelGGL(rownorm_kernel<false>, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, R, P, slices, out);
+  xai_dispatch(xai_can_vec4(P, {x, out}), [&](auto VEC) {
+    hipLaunchKernelGGL(rownorm_kernel<VEC>, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, R, P, slices, out);
+  });
   return xai_launch_status();
 }
 
@@ -353,13 +349,10 @@ XAI_EXPORT int xai_cluster_sum_f32(const float* rows, const int32_t* members, co
   XAI_REQUIRE(K > 0 && P > 0, XAI_E_SHAPE);
   XAI_REQUIRE(K <= 65535, XAI_E_UNSUPPORTED);
   const bool vec = xai_can_vec4(P, {rows, out});
-  if (vec) {
-    dim3 grid(static_cast<unsigned>(xai_ceil_div(P / 4, kBlock)), K);
-    hipLaunchKernelGGL(cluster_sum_kernel<true>, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), rows, members, offs, P, out);
-  } else {
-    dim3 grid(static_cast<unsigned>(xai_ceil_div(P, kBlock)), K);
-    hipLaunchKernelGGL(cluster_sum_kernel<false>, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), rows, members, offs, P, out);
-  }
+  const dim3 grid(xai_grid_x(P, kBlock, vec), K);        // vec: P % 4 == 0, so this is ceil((P / 4) / kBlock)
+  xai_dispatch(vec, [&](auto VEC) {
+    hipLaunchKernelGGL(cluster_sum_kernel<VEC>, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), rows, members, offs, P, out);
+  });
   return xai_launch_status();
 }
 
@@ -368,14 +361,11 @@ XAI_EXPORT int xai_causal_apply_f32(const float* x, const float* masks, const fl
   XAI_REQUIRE_PTR(x); XAI_REQUIRE_PTR(masks); XAI_REQUIRE_PTR(noise); XAI_REQUIRE_PTR(stack);
   XAI_REQUIRE(N > 0 && C > 0 && HW > 0, XAI_E_SHAPE);
   XAI_REQUIRE(N <= 65535, XAI_E_UNSUPPORTED);
-  if (xai_can_vec4(HW, {x, masks, noise, stack})) {
-    dim3 grid(static_cast<unsigned>(xai_ceil_div(HW, kBlock * 4)), N);
-    hipLaunchKernelGGL(causal_apply_kernel_v4, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, masks, noise, N, C, HW,
-                       noise_scale, stack);
-  } else {
-    dim3 grid(static_cast<unsigned>(xai_ceil_div(HW, kBlock)), N);
-    hipLaunchKernelGGL(causal_apply_kernel, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, masks, noise, N, C, HW,
-                       noise_scale, stack);
-  }
+  const bool vec = xai_can_vec4(HW, {x, masks, noise, stack});
+  const dim3 grid(xai_grid_x(HW, kBlock, vec), N);
+  xai_dispatch(vec, [&](auto V4) {
+    constexpr auto kernel = V4 ? causal_apply_kernel_v4 : causal_apply_kernel;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), x, masks, noise, N, C, HW, noise_scale, stack);
+  });
   return xai_launch_status();
 }

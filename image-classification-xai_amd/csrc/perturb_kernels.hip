@@ -127,20 +127,14 @@ XAI_EXPORT int xai_perturb_batch_f32(const float* start, const float* finish, co
   XAI_REQUIRE(C > 0 && hw > 0 && n_batch > 0 && first_step >= 0, XAI_E_SHAPE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool vec = xai_can_vec4(hw, {start, finish, flip_step, out});
-  const int64_t tiles = xai_ceil_div(hw, kBlock * (vec ? 4 : 1));
-  int per, chunks, zdim = 1;
-  if (static_cast<int64_t>(n_batch) * C * hw * 4 >= (int64_t(64) << 20) && C <= 64) {
-    per = n_batch >= 2 ? 2 : 1;                  // HBM-sized batch: one channel x two step images per lane
-    zdim = C;
-  } else {
-    const int c0 = static_cast<int>(std::min<int64_t>(n_batch, std::max<int64_t>(1, xai_ceil_div(2048, tiles))));
-    per = static_cast<int>(xai_ceil_div(n_batch, c0));
-  }
-  chunks = static_cast<int>(xai_ceil_div(n_batch, per));
-  XAI_REQUIRE(chunks <= 65535, XAI_E_UNSUPPORTED);
-  dim3 grid(static_cast<unsigned>(tiles), chunks, zdim);
-  if (vec) hipLaunchKernelGGL(perturb_kernel<4>, grid, dim3(kBlock), 0, st, start, finish, flip_step, C, hw, first_step, n_batch, per, out);
-  else     hipLaunchKernelGGL(perturb_kernel<1>, grid, dim3(kBlock), 0, st, start, finish, flip_step, C, hw, first_step, n_batch, per, out);
+  // HBM-sized batch (64 MiB): one channel x two step images per lane
+  const XaiRowPlan plan = xai_row_chunk_plan(hw, kBlock, vec, n_batch, C, 1, int64_t(64) << 20, true);
+  XAI_REQUIRE(plan.ok, XAI_E_UNSUPPORTED);
+  const dim3 grid(static_cast<unsigned>(plan.tiles), static_cast<unsigned>(plan.chunks), plan.zdim);
+  xai_dispatch(vec, [&](auto V4) {
+    hipLaunchKernelGGL(perturb_kernel<V4 ? 4 : 1>, grid, dim3(kBlock), 0, st, start, finish, flip_step, C, hw, first_step, n_batch,
+                       plan.per, out);
+  });
   return xai_launch_status();
 }
 

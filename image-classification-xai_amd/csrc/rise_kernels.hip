@@ -299,26 +299,25 @@ XAI_EXPORT int xai_rise_apply_f32(const uint8_t* grid, const int32_t* shift, int
   XAI_REQUIRE(hw < (int64_t(1) << 31), XAI_E_UNSUPPORTED);
   const double rh = static_cast<double>(s) / static_cast<double>((s + 1) * cell_h), rw = static_cast<double>(s) / static_cast<double>((s + 1) * cell_w);
   const bool vec = xai_can_vec4(W, {image, masked_out, masks_out});
+  const dim3 g(xai_grid_x(hw, kBlock, vec), n_masks);
   if (vec && s == 8 && (reinterpret_cast<uintptr_t>(grid) & 7u) == 0) {
-    dim3 g(static_cast<unsigned>(xai_ceil_div(hw, kBlock * 4)), n_masks);
     // Store policy by what the classifier will find: a batch that fits the 256 MiB Infinity Cache with room to spare is
     // stored normally (the convolution that consumes it next reads it from cache); a larger one cannot stay resident
     // anyway and is streamed with non-temporal stores, which on this part write 13-15 % faster
     // (csrc/tune/tune_rise.hip, profiles/r02_tune_rise.txt: 1000 masks 104.9 -> 92.4 us).
     const int64_t out_bytes = static_cast<int64_t>(n_masks) * hw * 4 * ((masked_out ? C : 0) + (masks_out ? 1 : 0));
     const bool nt = out_bytes > (int64_t(128) << 20);
-    const bool c3 = (C == 3);
-#define XAI_RISE_S8(NT, C3) \
-    hipLaunchKernelGGL((rise_apply_kernel_s8<NT, C3>), g, dim3(kBlock), 0, st, grid, shift, cell_h, cell_w, rh, rw, image, C, H, W, masked_out, masks_out)
-    if (nt) { if (c3) XAI_RISE_S8(true, true); else XAI_RISE_S8(true, false); }
-    else    { if (c3) XAI_RISE_S8(false, true); else XAI_RISE_S8(false, false); }
-#undef XAI_RISE_S8
-  } else if (vec) {
-    dim3 g(static_cast<unsigned>(xai_ceil_div(hw, kBlock * 4)), n_masks);
-    hipLaunchKernelGGL(rise_apply_kernel_v4, g, dim3(kBlock), s * s, st, grid, shift, s, cell_h, cell_w, rh, rw, image, C, H, W, masked_out, masks_out);
+    xai_dispatch(nt, [&](auto NT) {
+      xai_dispatch(C == 3, [&](auto C3) {
+        hipLaunchKernelGGL((rise_apply_kernel_s8<NT, C3>), g, dim3(kBlock), 0, st, grid, shift, cell_h, cell_w, rh, rw, image, C, H, W,
+                           masked_out, masks_out);
+      });
+    });
   } else {
-    dim3 g(static_cast<unsigned>(xai_ceil_div(hw, kBlock)), n_masks);
-    hipLaunchKernelGGL(rise_apply_kernel, g, dim3(kBlock), s * s, st, grid, shift, s, cell_h, cell_w, rh, rw, image, C, H, W, masked_out, masks_out);
+    xai_dispatch(vec, [&](auto V4) {
+      constexpr auto kernel = V4 ? rise_apply_kernel_v4 : rise_apply_kernel;
+      hipLaunchKernelGGL(kernel, g, dim3(kBlock), s * s, st, grid, shift, s, cell_h, cell_w, rh, rw, image, C, H, W, masked_out, masks_out);
+    });
   }
   return xai_launch_status();
 }

@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <initializer_list>
+#include <type_traits>
 #include "xai_hip.h"
+#include "xai_launch_plan.h"
 
 #define XAI_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -34,6 +36,22 @@ static inline bool xai_can_vec4(int64_t n, std::initializer_list<const void*> pt
 }
 
 static inline int64_t xai_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- host launch blocks: DESIGN.md ("Host launch blocks") has the rule for what may be shared.
+// f(std::true_type) or f(std::false_type): a launch written once in a generic lambda names its kernel from the constant,
+// kernel<F ? 4 : 1> or kernel<F>; nested calls handle two flags.
+template <typename Fn>
+static inline void xai_dispatch(bool flag, Fn&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+// gridDim.x of a launch over n floats, one lane per 4 (vec) or 1 of them
+static inline unsigned xai_grid_x(int64_t n, int block, bool vec) { return unsigned(xai_ceil_div(n, int64_t(block) * (vec ? 4 : 1))); }
+// blocks of a 1-D grid of one lane per unit -> false where they do not fit gridDim.x
+static inline bool xai_blocks_checked(int64_t n_units, int block, unsigned* blocks) {
+  *blocks = static_cast<unsigned>(xai_ceil_div(n_units, block));
+  return xai_ceil_div(n_units, block) <= INT32_MAX;
+}
 
 // Compute units of the current device (256 on MI355X).  One definition for the whole library (abi.hip): the per-device
 // value is queried once and published through a std::atomic, so concurrent first calls from several host threads race

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One SHA-256 per output of every xai_engine.kernels entry outside the classifier fusion (bn_*, maxpool_*, guided_map), on
-small seeded inputs: run it on two builds of libxai_hip.so and compare the lists line by line.
-    python profiles/experiments/exp_same_bytes.py [--lib other/libxai_hip.so] > hashes.txt
+small seeded inputs: run it on two builds of libxai_hip.so (and libxai_ext.so) and compare the lists line by line.
+    python profiles/experiments/exp_same_bytes.py [--lib other/libxai_hip.so] [--ext-lib other/libxai_ext.so] > hashes.txt
 A tolerance would let a changed summation order through; equal bytes do not.  The inputs take both flavours of every entry
 (element counts that are and are not multiples of 4, views offset by one float) and give the shared reductions, the radix
 select and the argmax their edge cases: more elements than lanes and fewer, ties, +-0, +-inf, NaN first and last, rows of -inf.
@@ -277,15 +277,40 @@ def xrai_entries():
             emit(f"xrai_rank masks {H}x{W} r={radius}", *K.xrai_rank(dev(attr[:1]), bits_m, span_m, dev(torch.tensor([0, 4], dtype=torch.int32)), 1, 1.0))
 
 
+def lime_gshap_entries():
+    for tag, shape, sh in variants():
+        C, H, W = shape
+        x = dev(randn(2, *shape), sh)
+        seg = dev(torch.randint(-1, 70, (2, H, W), generator=GEN, dtype=torch.int32))       # -1 and 66 .. 69 are no row's to switch off
+        bits = torch.randint(0, 2, (10, 66), generator=GEN)
+        bits[0], bits[1] = 1, 0
+        rows = torch.zeros(10, 2, dtype=torch.int64)
+        for z in range(66):
+            rows[:, z // 64] |= bits[:, z] << (z % 64)
+        rows, D = dev(rows), dev(torch.tensor([66, 40], dtype=torch.int32))
+        emit(f"lime_compose {tag}", K.lime_compose(x, seg, rows, D, dev(randn(C)), 3, 6),
+             K.lime_compose(x, seg, rows, D, None, 0, 10, fudged=dev(randn(2, *shape), sh)))
+        x_rows, base = dev(randn(8, *shape), sh), dev(randn(3, *shape), sh)
+        alpha, idx = dev(torch.rand(8, generator=GEN)), dev(torch.randint(0, 3, (8,), generator=GEN))
+        emit(f"gshap_scale {tag}", K.gshap_scale(x, base, alpha, idx, 4, out=dev(torch.zeros(8, *shape), sh)),
+             K.gshap_scale(x_rows, base, alpha, idx, 4, out=dev(torch.zeros(8, *shape), sh)))
+        g = dev(spiced(8, *shape), sh)
+        emit(f"gshap_finish {tag}", *K.gshap_finish(g, x, base, idx, 4, want_map=True, attr=dev(torch.zeros(2, *shape), sh)),
+             K.gshap_finish(g, x_rows, base, idx, 4, want_attr=False, want_map=True))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--lib", help="another build of libxai_hip.so to load instead of the package's")
+    ap.add_argument("--ext-lib", help="another build of libxai_ext.so to load instead of the package's")
     args = ap.parse_args()
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
+    if args.ext_lib:
+        _lib.EXT_LIB_PATH = os.path.abspath(args.ext_lib)
     _lib.load()
     for part in (ig_entries, cam_rise_blur_entries, insdel_entries, masker_entries, vit_entries, gig_entries, agi_entries, ablation_entries,
-                 xrai_entries):
+                 xrai_entries, lime_gshap_entries):
         part()
 
 

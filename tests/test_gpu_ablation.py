@@ -7,6 +7,7 @@ both restated operation for operation.  Engine vs the restatement run on the sam
 with another solver and a score difference amplifies that, so the floor is measured in the same test from the reference flow alone
 (restatement at batch 1 vs restatement at the pass size, both pure torch) and the engine must stay within max(BAR, 2 x floor): its
 error is one more sample of the same batching noise.  Measured on an MI355X (profiles/r07_ablation.txt): see that file."""
+import functools
 import os
 
 import numpy as np
@@ -107,6 +108,38 @@ def test_k26_occlusion_mode_equals_the_restatement_bit_for_bit(K):
     _check_k26_windows(K, x, (3, 40, 40), 7, -0.5, gen, "window == image")
     _check_k26_windows(K, x, (3, 40, 12), (3, 99, 5), _spiced((3, 40, 40), gen), gen, "window == image along one axis")
     _check_k26_windows(K, _spiced((2, 3, 29, 31), gen), (3, 7, 9), (3, 7, 4), 0, gen, "odd width")
+
+
+HBM_ROWS = 1366          # rows of 3 x 64 x 64 floats (49 152 B): 1366 x 49 152 = 67 141 632 B >= 64 MiB > 1365 x 49 152 B
+
+
+@functools.lru_cache(maxsize=None)
+def _hbm_case(mode):
+    """Two images of 3 x 64 x 64 and a run of HBM_ROWS rows that starts inside image 0 and ends inside image 1
+    -> x, the mode's geometry, first, the restated rows of the run."""
+    gen = torch.Generator().manual_seed(64)
+    x = _spiced((2, 3, 64, 64), gen)
+    if mode == "features":
+        geo = torch.randint(5, 705, (64, 64), generator=gen)                 # 700 ids, some absent: 1400 rows
+        geo[0, 0], geo[63, 63] = 5, 704
+        masks, first = list(R.feature_masks(geo, (3, 64, 64))), 17
+    else:
+        geo = ((3, 4, 4), (3, 2, 2))                                          # 31 x 31 windows: 1922 rows
+        masks, first = list(R.window_masks((3, 64, 64), *geo)), 100
+    rows = [(b, m) for b in range(2) for m in masks][first:first + HBM_ROWS]
+    return x, geo, first, torch.stack([R.ablated(x[b], m, -0.75) for b, m in rows])
+
+
+@pytest.mark.parametrize("n", [HBM_ROWS, HBM_ROWS - 1])
+@pytest.mark.parametrize("mode", ["features", "windows"])
+def test_k26_hbm_sized_pass_equals_the_restatement_bit_for_bit(K, mode, n):
+    """The smallest pass at or over the 64 MiB from which a lane writes one channel of two rows, and the largest under it."""
+    x, geo, first, want = _hbm_case(mode)
+    if mode == "features":
+        got = K.ablate_features(x.to(DEV), geo.to(torch.int32).to(DEV), 5, 700, -0.75, first, n)
+    else:
+        got = K.ablate_windows(x.to(DEV), geo[0][1:], geo[1][1:], -0.75, first, n)
+    _same_bits(got, want[:n], f"{mode} n={n}")
 
 
 def test_k26_writes_into_a_given_buffer_and_checks_the_run(K):

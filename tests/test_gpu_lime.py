@@ -119,8 +119,33 @@ def test_k31_composes_bit_for_bit(shape, dpair, mode):
         np.testing.assert_array_equal(_bits(both), _bits(full[:3]))
 
 
+HBM_ROWS = 1366          # rows of 3 x 64 x 64 floats (49 152 B): 1366 x 49 152 = 67 141 632 B >= 64 MiB > 1365 x 49 152 B
+
+
+@functools.lru_cache(maxsize=None)
+def _hbm_case():
+    """Two images of 3 x 64 x 64 with 63 and 65 superpixels and HBM_ROWS / 2 rows each -> x, seg, mats, hide, the restated list."""
+    rng = np.random.default_rng(31)
+    x = rng.standard_normal((2, 3, 64, 64)).astype(np.float32)
+    hide = rng.standard_normal(3).astype(np.float32)
+    seg = np.stack([rng.integers(0, D, (64, 64)) for D in (63, 65)]).astype(np.int32)
+    mats = [rng.integers(0, 2, (HBM_ROWS // 2, D)) for D in (63, 65)]
+    want = np.stack([R.perturbed(x[b], seg[b], row, hide[:, None, None]) for b in range(2) for row in mats[b]])
+    return x, seg, mats, hide, want
+
+
+@pytest.mark.parametrize("n", [HBM_ROWS, HBM_ROWS - 1])
+def test_k31_hbm_sized_pass_composes_bit_for_bit(n):
+    """The smallest pass at or over the 64 MiB from which a lane writes two rows, and the largest under it."""
+    from xai_engine import kernels as K
+    x, seg, mats, hide, want = _hbm_case()
+    rows, D = _rows(mats)
+    got = K.lime_compose(torch.from_numpy(x).to(DEV), torch.from_numpy(seg).to(DEV), rows, D, torch.from_numpy(hide).to(DEV), 0, n)
+    np.testing.assert_array_equal(_bits(got.cpu().numpy()), _bits(want[:n]))
+
+
 # ------------------------------------------------------------------------------------------------------------- K32
-FP64 = ("coef", "intercept", "score", "local_pred", "dist", "weight")
+FP64 =("coef", "intercept", "score", "local_pred", "dist", "weight")
 
 
 def _fit(mats, Ys, words=None, **kw):

@@ -9,10 +9,18 @@
 // bit 3: fused multiply-add for the last step); xai_engine/prepare.py uses the one that reproduces PyTorch-ROCm's own
 // eval-mode kernels bit for bit (found by profiles/experiments/exp_bn_variants.py).
 #include "xai_common.h"
+#include "xai_bn_index.h"
 
 namespace {
 
 constexpr int kBlock = 256;
+
+// all tensors a launch would access 16 bytes at a time -> their addresses OR-ed, for xai_bn_path
+static inline uintptr_t bn_low_bits(std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return bits;
+}
 
 // every activation / gradient tensor here is read exactly once by these kernels: non-temporal loads keep them from pushing
 // the just-written outputs (which the next convolution reads at once) out of L2 / Infinity Cache (ld4_nt, xai_common.h)
@@ -54,13 +62,115 @@ struct BnParams {
   float eps;
 };
 
+// ---- the flat 16-byte path (XAI_BN_FLAT4, xai_bn_index.h): n % 4 == 0 and every tensor 16-byte aligned, but HW % 4 != 0
+// (layer4: HW = 49).  A lane owns flat elements 4t .. 4t+3 exactly as on the vector path and moves them with one 16-byte
+// access per tensor; only the channel differs per element.  It comes from i / HW and % C once per lane (32-bit where n < 2^31) and stepping, and the
+// BN parameters are fetched per distinct channel, not per element.  Same expressions per element in the same order as the
+// other two paths.  The VEC = false instantiations take it on a wave-uniform kernel argument (`flat`).
+struct BnChannel {
+  float m, is, w, b;                        // mean, inv_std, weight, bias of one channel (the backward uses is and w only)
+};
+
+// p[k] = load(channel of element k) for the four flat elements from s on.  HW >= 4: at most two channels, both fetched
+// unconditionally and selected per element.  Below that up to four: fetched again wherever r wraps.
+template <typename Load>
+__device__ __forceinline__ void lane_channels(BnChannel (&p)[4], XaiBnLane s, int HW, int C, Load load) {
+  if (HW >= 4) {
+    const int split = xai_bn_lane_split(s, HW);
+    const BnChannel a = load(s.c), b = load(xai_bn_next_channel(s.c, C));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = k < split ? a : b;
+  } else {
+    p[0] = load(s.c);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      s = xai_bn_lane_step(s, HW, C);
+      p[k] = s.r != 0 ? p[k - 1] : load(s.c);
+    }
+  }
+}
+
+// o[k] = act( bn(x[i+k]) [+ identity[i+k] | + bn2(identity[i+k])] ), stored to y as one float4; i + 3 < n
+template <bool ADD, bool RELU>
+__device__ __forceinline__ void flat_fwd4(const float* __restrict__ x, const float* __restrict__ idt, const float* __restrict__ w,
+                                          const float* __restrict__ b, const float* __restrict__ mean, const float* __restrict__ var,
+                                          float eps, const BnParams& bn2, int variant, int C, int HW, int64_t n, int64_t i,
+                                          float* __restrict__ y, float (&o)[4]) {
+  const XaiBnLane s = xai_bn_lane_first(i, n, HW, C);
+  BnChannel p[4];
+  lane_channels(p, s, HW, C, [&](int c) { return BnChannel{mean[c], inv_std(var[c], eps, variant), w[c], b[c]}; });
+  const float4 v = ld4_nt(x + i);
+  const float xv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = bn_value(xv[k], p[k].m, p[k].is, p[k].w, p[k].b, variant);
+  if (ADD) {
+    const float4 t = ld4_nt(idt + i);
+    float a[4] = {t.x, t.y, t.z, t.w};
+    if (bn2.w != nullptr) {
+      BnChannel q[4];
+      lane_channels(q, s, HW, C, [&](int c) { return BnChannel{bn2.mean[c], inv_std(bn2.var[c], bn2.eps, variant), bn2.w[c], bn2.b[c]}; });
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = bn_value(a[k], q[k].m, q[k].is, q[k].w, q[k].b, variant);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] += a[k];
+  }
+  if (RELU) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
+  }
+  st4(y + i, make_float4(o[0], o[1], o[2], o[3]));
+}
+
+// g = gy (+ gy2) [guided clamp];  g1 = open[k] ? g : 0;  gx = bn_grad(g1);  g_identity = g1 | bn_grad through bn2;  i + 3 < n
+__device__ __forceinline__ float guided_clamp(float g);    // defined with the guided kernels below
+
+template <bool ADD, bool GUIDED>
+__device__ __forceinline__ void flat_bwd4(const float* __restrict__ gy, const float* __restrict__ gy2, const bool (&open)[4],
+                                          const float* __restrict__ w, const float* __restrict__ var, float eps, const BnParams& bn2,
+                                          int variant, int C, int HW, int64_t n, int64_t i, float* __restrict__ gx,
+                                          float* __restrict__ gid) {
+  const XaiBnLane s = xai_bn_lane_first(i, n, HW, C);
+  BnChannel p[4];
+  lane_channels(p, s, HW, C, [&](int c) { return BnChannel{0.f, inv_std(var[c], eps, variant), w[c], 0.f}; });
+  const float4 t = ld4_nt(gy + i);
+  float g[4] = {t.x, t.y, t.z, t.w};
+  if (gy2 != nullptr) {
+    const float4 h = ld4_nt(gy2 + i);
+    g[0] += h.x; g[1] += h.y; g[2] += h.z; g[3] += h.w;
+  }
+  float g1[4], o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (GUIDED) g[k] = guided_clamp(g[k]);
+    g1[k] = open[k] ? g[k] : 0.f;
+    o[k] = bn_grad(g1[k], p[k].is, p[k].w, variant);
+  }
+  st4(gx + i, make_float4(o[0], o[1], o[2], o[3]));
+  if (ADD) {
+    if (bn2.w != nullptr) {                             // g_identity goes through the identity operand's own BatchNorm
+      BnChannel q[4];
+      lane_channels(q, s, HW, C, [&](int c) { return BnChannel{0.f, inv_std(bn2.var[c], bn2.eps, variant), bn2.w[c], 0.f}; });
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g1[k] = bn_grad(g1[k], q[k].is, q[k].w, variant);
+    }
+    st4(gid + i, make_float4(g1[0], g1[1], g1[2], g1[3]));
+  }
+}
+
 template <bool VEC, bool ADD, bool RELU>
 __global__ __launch_bounds__(kBlock) void bn_act_fwd_kernel(const float* __restrict__ x, const float* __restrict__ idt,
                                                             const float* __restrict__ w, const float* __restrict__ b,
                                                             const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                                            BnParams bn2, int variant, int C, int HW, int64_t n, float* __restrict__ y) {
-  const int64_t i = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * (VEC ? 4 : 1);
+                                                            BnParams bn2, int variant, int C, int HW, int64_t n, int flat,
+                                                            float* __restrict__ y) {
+  const int64_t i = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * (VEC ? 4 : flat ? 4 : 1);
   if (i >= n) return;
+  if (!VEC && flat) {
+    float o[4];
+    flat_fwd4<ADD, RELU>(x, idt, w, b, mean, var, eps, bn2, variant, C, HW, n, i, y, o);
+    return;
+  }
   const int c = static_cast<int>((i / HW) % C);
   const float m = mean[c], is = inv_std(var[c], eps, variant), wc = w[c], bc = b[c];
   const bool second = ADD && bn2.w != nullptr;
@@ -93,10 +203,16 @@ template <bool VEC, bool ADD>
 __global__ __launch_bounds__(kBlock) void bn_relu_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ gy2,
                                                              const float* __restrict__ y, const float* __restrict__ w,
                                                              const float* __restrict__ var, float eps, BnParams bn2, int variant,
-                                                             int C, int HW, int64_t n, float* __restrict__ gx,
+                                                             int C, int HW, int64_t n, int flat, float* __restrict__ gx,
                                                              float* __restrict__ gid) {
-  const int64_t i = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * (VEC ? 4 : 1);
+  const int64_t i = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * (VEC ? 4 : flat ? 4 : 1);
   if (i >= n) return;
+  if (!VEC && flat) {
+    const float4 o = ld4_nt(y + i);
+    const bool open[4] = {o.x > 0.f, o.y > 0.f, o.z > 0.f, o.w > 0.f};
+    flat_bwd4<ADD, false>(gy, gy2, open, w, var, eps, bn2, variant, C, HW, n, i, gx, gid);
+    return;
+  }
   const int c = static_cast<int>((i / HW) % C);
   const float is = inv_std(var[c], eps, variant), wc = w[c];
   const bool second = ADD && bn2.w != nullptr;          // g_identity then goes through the identity operand's own BatchNorm
@@ -138,11 +254,13 @@ XAI_EXPORT int xai_bn_act_fwd_f32(const float* x, const float* identity, const f
   }
   const BnParams bn2{weight2, bias2, mean2, var2, eps2};
   const int64_t n = static_cast<int64_t>(N) * C * HW;
-  const bool vec = xai_can_vec4(HW, {x, y, identity});
-  const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * (vec ? 4 : 1)));
+  const XaiBnPath path = xai_bn_path(n, HW, bn_low_bits({x, y, identity}));
+  const bool vec = path == XAI_BN_VEC4;
+  const int flat = path == XAI_BN_FLAT4;                // taken inside the VEC = false instantiations
+  const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * (path == XAI_BN_SCALAR ? 1 : 4)));
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define XAI_BN_FWD(V, A, R) \
-  hipLaunchKernelGGL((bn_act_fwd_kernel<V, A, R>), dim3(grid), dim3(kBlock), 0, st, x, identity, weight, bias, mean, var, eps, bn2, variant, C, HW, n, y)
+  hipLaunchKernelGGL((bn_act_fwd_kernel<V, A, R>), dim3(grid), dim3(kBlock), 0, st, x, identity, weight, bias, mean, var, eps, bn2, variant, C, HW, n, flat, y)
   if (identity != nullptr) {
     XAI_REQUIRE(relu != 0, XAI_E_UNSUPPORTED);
     if (vec) XAI_BN_FWD(true, true, true); else XAI_BN_FWD(false, true, true);
@@ -165,11 +283,13 @@ XAI_EXPORT int xai_bn_relu_bwd_f32(const float* gy, const float* gy2, const floa
     XAI_REQUIRE_PTR(g_identity); XAI_REQUIRE_PTR(var2);
   }
   const BnParams bn2{weight2, nullptr, nullptr, var2, eps2};
-  const bool vec = xai_can_vec4(HW, {gy, y, gx, g_identity, gy2});
-  const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * (vec ? 4 : 1)));
+  const XaiBnPath path = xai_bn_path(n, HW, bn_low_bits({gy, y, gx, g_identity, gy2}));
+  const bool vec = path == XAI_BN_VEC4;
+  const int flat = path == XAI_BN_FLAT4;
+  const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * (path == XAI_BN_SCALAR ? 1 : 4)));
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define XAI_BN_BWD(V, A) \
-  hipLaunchKernelGGL((bn_relu_bwd_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, y, weight, var, eps, bn2, variant, C, HW, n, gx, g_identity)
+  hipLaunchKernelGGL((bn_relu_bwd_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, y, weight, var, eps, bn2, variant, C, HW, n, flat, gx, g_identity)
   if (g_identity != nullptr) {
     if (vec) XAI_BN_BWD(true, true); else XAI_BN_BWD(false, true);
   } else {
@@ -189,8 +309,9 @@ XAI_EXPORT int xai_bn_relu_bwd_f32(const float* gy, const float* gy2, const floa
 // A lane owns elements 4t .. 4t+3, so a wavefront owns exactly one group and word c of the group is the wave ballot of
 // component c; lanes 0..3 store the four words with ordinary vector stores.  Every word of the mask is written, the tail
 // group's bits of elements >= n as 0: nothing relies on a zero-fill.  When HW % 4 != 0 (layer4: HW = 49) the four
-// elements of a lane can straddle two channels and any n is allowed; they are then loaded one by one with the channel
-// taken per element -- same arithmetic per element, same layout.
+// elements of a lane can straddle two channels and any n is allowed: with n % 4 == 0 and aligned tensors they take the flat
+// 16-byte path above (`flat`), otherwise they are loaded one by one with the channel taken per element -- same arithmetic
+// per element, same layout.
 namespace {
 
 constexpr int kGateGroup = 256;                 // elements per mask group = 4 per lane * 64 lanes
@@ -205,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_fwd_mask_kernel(const float* _
                                                                   const float* __restrict__ w, const float* __restrict__ b,
                                                                   const float* __restrict__ mean, const float* __restrict__ var,
                                                                   float eps, BnParams bn2, int variant, int C, int HW, int64_t n,
-                                                                  float* __restrict__ y, uint64_t* __restrict__ mask) {
+                                                                  int flat, float* __restrict__ y, uint64_t* __restrict__ mask) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t group = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   if (group * kGateGroup >= n) return;                  // wave-uniform: this wavefront owns no element and no mask word
@@ -232,6 +353,8 @@ __global__ __launch_bounds__(kBlock) void bn_relu_fwd_mask_kernel(const float* _
       for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
       st4(y + i, make_float4(o[0], o[1], o[2], o[3]));
     }
+  } else if (flat) {                                    // n % 4 == 0 here too: a lane is inside or outside as a whole
+    if (i < n) flat_fwd4<ADD, true>(x, idt, w, b, mean, var, eps, bn2, variant, C, HW, n, i, y, o);
   } else {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -259,7 +382,7 @@ template <bool VEC, bool ADD, bool GUIDED>
 __global__ __launch_bounds__(kBlock) void bn_relu_bwd_mask_kernel(const float* __restrict__ gy, const float* __restrict__ gy2,
                                                                   const uint64_t* __restrict__ mask, const float* __restrict__ w,
                                                                   const float* __restrict__ var, float eps, BnParams bn2, int variant,
-                                                                  int C, int HW, int64_t n, float* __restrict__ gx,
+                                                                  int C, int HW, int64_t n, int flat, float* __restrict__ gx,
                                                                   float* __restrict__ gid) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t group = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -287,6 +410,8 @@ __global__ __launch_bounds__(kBlock) void bn_relu_bwd_mask_kernel(const float* _
       st4(gid + i, second ? make_float4(bn_grad(g1.x, is2, w2, variant), bn_grad(g1.y, is2, w2, variant), bn_grad(g1.z, is2, w2, variant),
                                         bn_grad(g1.w, is2, w2, variant))
                           : g1);
+  } else if (flat) {
+    flat_bwd4<ADD, GUIDED>(gy, gy2, open, w, var, eps, bn2, variant, C, HW, n, i, gx, gid);
   } else {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -323,12 +448,14 @@ XAI_EXPORT int xai_bn_relu_fwd_mask_f32(const float* x, const float* identity, c
   }
   const BnParams bn2{weight2, bias2, mean2, var2, eps2};
   const int64_t n = static_cast<int64_t>(N) * C * HW;
-  const bool vec = xai_can_vec4(HW, {x, y, identity});
+  const XaiBnPath path = xai_bn_path(n, HW, bn_low_bits({x, y, identity}));
+  const bool vec = path == XAI_BN_VEC4;
+  const int flat = path == XAI_BN_FLAT4;
   const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * 4));
   hipStream_t st = static_cast<hipStream_t>(stream);
   uint64_t* mk = static_cast<uint64_t*>(mask);
 #define XAI_BN_FWDM(V, A) \
-  hipLaunchKernelGGL((bn_relu_fwd_mask_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, x, identity, weight, bias, mean, var, eps, bn2, variant, C, HW, n, y, mk)
+  hipLaunchKernelGGL((bn_relu_fwd_mask_kernel<V, A>), dim3(grid), dim3(kBlock), 0, st, x, identity, weight, bias, mean, var, eps, bn2, variant, C, HW, n, flat, y, mk)
   if (identity != nullptr) {
     if (vec) XAI_BN_FWDM(true, true); else XAI_BN_FWDM(false, true);
   } else {
@@ -350,12 +477,14 @@ static int bn_relu_bwd_mask_launch(const float* gy, const float* gy2, const void
     XAI_REQUIRE_PTR(g_identity); XAI_REQUIRE_PTR(var2);
   }
   const BnParams bn2{weight2, nullptr, nullptr, var2, eps2};
-  const bool vec = xai_can_vec4(HW, {gy, gx, g_identity, gy2});
+  const XaiBnPath path = xai_bn_path(n, HW, bn_low_bits({gy, gx, g_identity, gy2}));
+  const bool vec = path == XAI_BN_VEC4;
+  const int flat = path == XAI_BN_FLAT4;
   const unsigned grid = static_cast<unsigned>(xai_ceil_div(n, static_cast<int64_t>(kBlock) * 4));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint64_t* mk = static_cast<const uint64_t*>(mask);
 #define XAI_BN_BWDM(V, A) \
-  hipLaunchKernelGGL((bn_relu_bwd_mask_kernel<V, A, GUIDED>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, mk, weight, var, eps, bn2, variant, C, HW, n, gx, g_identity)
+  hipLaunchKernelGGL((bn_relu_bwd_mask_kernel<V, A, GUIDED>), dim3(grid), dim3(kBlock), 0, st, gy, gy2, mk, weight, var, eps, bn2, variant, C, HW, n, flat, gx, g_identity)
   if (g_identity != nullptr) {
     if (vec) XAI_BN_BWDM(true, true); else XAI_BN_BWDM(false, true);
   } else {
@@ -608,6 +737,11 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_tiled_kernel(const float*
   }
 }
 
+// kernel 3, stride 2, pad 1 (every shipped classifier's stem) has its geometry at compile time: bn_relu_maxpool_fwd_kernel_fixed
+// below, shared with the autograd stem; code == nullptr: this forward-only form (fmaxf, no code written)
+void launch_stem_fwd_321(const float* x, const float* weight, const float* bias, const float* mean, const float* var, float eps, int variant,
+                         int N, int C, int H, int W, int PH, int PW, size_t lds, float* y, uint8_t* code, hipStream_t st);
+
 }  // namespace
 
 XAI_EXPORT int xai_bn_relu_maxpool_fwd_f32(const float* x, const float* weight, const float* bias, const float* mean, const float* var,
@@ -618,7 +752,9 @@ XAI_EXPORT int xai_bn_relu_maxpool_fwd_f32(const float* x, const float* weight, 
               XAI_E_SHAPE);
   XAI_REQUIRE(static_cast<int64_t>(N) * C <= 65535 && static_cast<int64_t>(H) * W <= INT32_MAX, XAI_E_UNSUPPORTED);
   const size_t lds = static_cast<size_t>((kPoolRows - 1) * stride + kernel) * (W + 2 * pad) * sizeof(float);
-  if (lds <= 48 * 1024) {
+  if (lds <= 48 * 1024 && kernel == 3 && stride == 2 && pad == 1 && PH == (H - 1) / 2 + 1 && PW == (W - 1) / 2 + 1) {
+    launch_stem_fwd_321(x, weight, bias, mean, var, eps, variant, N, C, H, W, PH, PW, lds, y, nullptr, static_cast<hipStream_t>(stream));
+  } else if (lds <= 48 * 1024) {
     dim3 grid(static_cast<unsigned>(xai_ceil_div(PH, kPoolRows)), N * C);
     hipLaunchKernelGGL(bn_relu_maxpool_tiled_kernel, grid, dim3(256), lds, static_cast<hipStream_t>(stream), x, weight, bias, mean, var, eps,
                        variant, C, H, W, PH, PW, kernel, stride, pad, y);
@@ -696,6 +832,71 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_code_kernel(const float* 
   }
 }
 
+// The same kernel with the pool geometry at compile time and a 2-D lane mapping: no integer division is left (the form above
+// spends most of its instructions on i / TWp per staged input and q / PW per output).  Staging: lane (ty, tx) of a TX-wide,
+// 256 / TX-high arrangement takes tile rows ty, ty + TY, .. of columns tx, tx + TX, ..; all of a lane's loads of one column are
+// in flight before its first LDS store.  Output: lanes TX / 2 wide over the pooled row (TX >= W + 2 P makes that one trip at
+// stride 2).  Grid (row tiles, C, N): the channel is blockIdx.y.  Same tile values, same scan, same y and code.
+// CODE = false is the forward-only bn_relu_maxpool_tiled_kernel in the same way: fmaxf in place of relu_keep_nan, no code.
+template <int K, int S, int P, int TX, bool CODE>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel_fixed(const float* __restrict__ x, const float* __restrict__ w,
+                                                                         const float* __restrict__ b, const float* __restrict__ mean,
+                                                                         const float* __restrict__ var, float eps, int variant, int H,
+                                                                         int W, int PH, int PW, float* __restrict__ y,
+                                                                         uint8_t* __restrict__ code) {
+  extern __shared__ float tile[];                       // [rows][W + 2 * P]
+  constexpr int TY = 256 / TX, TXO = TX / 2, TYO = 256 / TXO;
+  constexpr int kRows = (kPoolRows - 1) * S + K, U = (kRows + TY - 1) / TY;
+  const int c = blockIdx.y;
+  const int64_t plane = static_cast<int64_t>(blockIdx.z) * gridDim.y + c;
+  const float m = mean[c], is = inv_std(var[c], eps, variant), wc = w[c], bc = b[c];
+  const int ph0 = blockIdx.x * kPoolRows;
+  const int n_out = min(kPoolRows, PH - ph0);
+  const int rows = (n_out - 1) * S + K;
+  const int h_first = ph0 * S - P;                      // input row of tile row 0 (may be negative)
+  const int TWp = W + 2 * P;
+  const float* src = x + plane * H * W;
+  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+  for (int cx = tx; cx < TWp; cx += TX) {
+    const int ww = cx - P;
+    const bool col_in = ww >= 0 && ww < W;
+    float v[U];
+    bool in[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r = ty + u * TY, h = h_first + r;
+      in[u] = col_in && r < rows && h >= 0 && h < H;
+      v[u] = in[u] ? src[h * W + ww] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r = ty + u * TY;
+      if (r < rows) {
+        const float t = bn_value(v[u], m, is, wc, bc, variant);
+        tile[r * TWp + cx] = in[u] ? (CODE ? relu_keep_nan(t) : fmaxf(t, 0.f)) : -INFINITY;
+      }
+    }
+  }
+  __syncthreads();
+  const int txo = threadIdx.x & (TXO - 1), tyo = threadIdx.x / TXO;
+  for (int pr = tyo; pr < n_out; pr += TYO)
+    for (int pw = txo; pw < PW; pw += TXO) {
+      const float* t = tile + (pr * S) * TWp + pw * S;
+      float best = -INFINITY;
+      int arg = 0;
+#pragma unroll
+      for (int a = 0; a < K; ++a)
+#pragma unroll
+        for (int bb = 0; bb < K; ++bb) {
+          const float v = t[a * TWp + bb];
+          if (v > best || v != v) { best = v; arg = a * K + bb; }
+        }
+      const int64_t o = (plane * PH + ph0 + pr) * PW + pw;
+      y[o] = best;
+      if (CODE) code[o] = static_cast<uint8_t>(best <= 0.f ? kStemClosed : arg);
+    }
+}
+
 // GUIDED: guided_clamp on the position's SUM over the windows that selected it (the complete gradient of the ReLU's output, as the
 // pool's backward scatters it), not per window: overlapping windows can bring gradients of both signs to one position.
 template <int NW, bool GUIDED>
@@ -757,6 +958,91 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel(const float* _
   }
 }
 
+// The same backward for kernel 3, stride 2, pad 1 at compile time, without LDS and without an integer division.  A lane owns
+// input rows 2m, 2m + 1 and columns 4j .. 4j + 3: every window that can select one of those eight positions lies in pooled
+// rows m, m + 1 and pooled columns 2j .. 2j + 2, so the lane loads those six codes and gradients (gy + gy2 formed at once),
+// all loads in flight together, and then adds per position, from +0, the windows that selected it in (ph, pw) ascending order:
+// the loops below are the ones of the form above with their bounds known, so the sums are the same sums.  Lanes are TX wide
+// over the columns and 256 / TX row pairs high; `vec`: W % 4 == 0 and gx 16-byte aligned, one float4 store per row.
+// Grid (row-pair tiles, C, N).
+template <int K, int S, int P, int TX, bool GUIDED>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel_fixed(const float* __restrict__ gy, const float* __restrict__ gy2,
+                                                                        const uint8_t* __restrict__ code, const float* __restrict__ w,
+                                                                        const float* __restrict__ var, float eps, int variant, int H,
+                                                                        int W, int PH, int PW, int vec, float* __restrict__ gx) {
+  static_assert(K == 3 && S == 2 && P == 1, "row pairs and column quads below cover exactly the windows of 3/2/1");
+  constexpr int TY = 256 / TX;
+  const int c = blockIdx.y;
+  const int64_t plane = static_cast<int64_t>(blockIdx.z) * gridDim.y + c;
+  const float is = inv_std(var[c], eps, variant), wc = w[c];
+  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+  const int m = blockIdx.x * TY + ty;
+  if (2 * m >= H) return;
+  const uint8_t* cp = code + plane * PH * PW;
+  const float* gp = gy + plane * PH * PW;
+  const float* gp2 = gy2 != nullptr ? gy2 + plane * PH * PW : nullptr;
+  float* dst = gx + plane * H * W;
+  for (int j = tx; 4 * j < W; j += TX) {
+    int cd[2][3];
+    float gv[2][3];
+#pragma unroll
+    for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+      for (int b2 = 0; b2 < 3; ++b2) {
+        const int ph = m + a2, pw = 2 * j + b2;
+        const bool ok = ph < PH && pw < PW;               // outside: no such window; its slot never matches
+        const int q = ok ? ph * PW + pw : 0;
+        const int raw = cp[q];
+        cd[a2][b2] = ok ? raw : kStemClosed;
+        gv[a2][b2] = gp[q];
+        if (gp2 != nullptr) gv[a2][b2] += gp2[q];
+      }
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const int h = 2 * m + rr;
+      if (h < H) {
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float g = 0.f;
+#pragma unroll
+          for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+            for (int b2 = 0; b2 < 3; ++b2) {
+              const int a = rr + P - S * a2, bb = e + P - S * b2;   // this position inside window (m + a2, 2j + b2)
+              if (a >= 0 && a < K && bb >= 0 && bb < K)
+                if (cd[a2][b2] == a * K + bb) g += gv[a2][b2];
+            }
+          if (GUIDED) g = guided_clamp(g);
+          o[e] = bn_grad(g, is, wc, variant);
+        }
+        float* row = dst + h * W + 4 * j;
+        if (vec) {
+          st4(row, make_float4(o[0], o[1], o[2], o[3]));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (4 * j + e < W) row[e] = o[e];
+        }
+      }
+    }
+  }
+}
+
+// lanes across the staged row: the smallest of 64, 128, 256 that covers W + 2 columns in one trip (256 loops beyond that)
+void launch_stem_fwd_321(const float* x, const float* weight, const float* bias, const float* mean, const float* var, float eps, int variant,
+                         int N, int C, int H, int W, int PH, int PW, size_t lds, float* y, uint8_t* code, hipStream_t st) {
+  dim3 grid(static_cast<unsigned>(xai_ceil_div(PH, kPoolRows)), C, N);
+  xai_dispatch(code != nullptr, [&](auto coded) {
+#define XAI_STEM_FWD(TX) \
+  hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel_fixed<3, 2, 1, TX, decltype(coded)::value>), grid, dim3(256), lds, st, x, weight, bias, mean, var, eps, variant, H, W, PH, PW, y, code)
+    if (W + 2 <= 64) XAI_STEM_FWD(64);
+    else if (W + 2 <= 128) XAI_STEM_FWD(128);
+    else XAI_STEM_FWD(256);
+#undef XAI_STEM_FWD
+  });
+}
+
 // what both stem entry points accept: a plain square pool whose windows all hold an input element, codes that fit a byte
 // next to kStemClosed, consistent pooled extents (the kernels index by them), planes on grid.y
 static int stem_geometry_status(int N, int C, int H, int W, int PH, int PW, int kernel, int stride, int pad, int variant) {
@@ -781,9 +1067,14 @@ XAI_EXPORT int xai_bn_relu_maxpool_fwd_code_f32(const float* x, const float* wei
   if (rc != XAI_OK) return rc;
   const size_t lds = static_cast<size_t>((kPoolRows - 1) * stride + kernel) * (W + 2 * pad) * sizeof(float);
   XAI_REQUIRE(lds <= 48 * 1024, XAI_E_UNSUPPORTED);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (kernel == 3 && stride == 2 && pad == 1) {         // every shipped classifier's stem: geometry at compile time
+    launch_stem_fwd_321(x, weight, bias, mean, var, eps, variant, N, C, H, W, PH, PW, lds, y, code, st);
+    return xai_launch_status();
+  }
   dim3 grid(static_cast<unsigned>(xai_ceil_div(PH, kPoolRows)), N * C);
-  hipLaunchKernelGGL(bn_relu_maxpool_code_kernel, grid, dim3(256), lds, static_cast<hipStream_t>(stream), x, weight, bias, mean, var, eps,
-                     variant, C, H, W, PH, PW, kernel, stride, pad, y, code);
+  hipLaunchKernelGGL(bn_relu_maxpool_code_kernel, grid, dim3(256), lds, st, x, weight, bias, mean, var, eps, variant, C, H, W, PH, PW, kernel,
+                     stride, pad, y, code);
   return xai_launch_status();
 }
 
@@ -797,8 +1088,20 @@ static int bn_relu_maxpool_bwd_launch(const float* gy, const float* gy2, const u
   const int pooled_rows = (kBwdRows + kernel - 2) / stride + 2;                   // upper bound of the pooled rows one tile needs
   const size_t lds = static_cast<size_t>(pooled_rows) * PW * 8;
   XAI_REQUIRE(lds <= 48 * 1024, XAI_E_UNSUPPORTED);
-  dim3 grid(static_cast<unsigned>(xai_ceil_div(H, kBwdRows)), N * C);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (kernel == 3 && stride == 2 && pad == 1) {         // every shipped classifier's stem: geometry at compile time, no LDS
+    const int vec = xai_can_vec4(W, {gx});
+    const int pairs = (H + 1) / 2;
+#define XAI_STEM_BWD(TX) \
+  hipLaunchKernelGGL((bn_relu_maxpool_bwd_kernel_fixed<3, 2, 1, TX, GUIDED>), dim3(static_cast<unsigned>(xai_ceil_div(pairs, 256 / TX)), C, N), \
+                     dim3(256), 0, st, gy, gy2, code, weight, var, eps, variant, H, W, PH, PW, vec, gx)
+    if (W <= 64) XAI_STEM_BWD(16);
+    else if (W <= 128) XAI_STEM_BWD(32);
+    else XAI_STEM_BWD(64);
+#undef XAI_STEM_BWD
+    return xai_launch_status();
+  }
+  dim3 grid(static_cast<unsigned>(xai_ceil_div(H, kBwdRows)), N * C);
   if ((kernel + stride - 1) / stride == 1)
     hipLaunchKernelGGL((bn_relu_maxpool_bwd_kernel<1, GUIDED>), grid, dim3(256), lds, st, gy, gy2, code, weight, var, eps, variant, C, H, W, PH, PW,
                        kernel, stride, pad, gx);

@@ -163,6 +163,35 @@ def main():
     ms = timeit(lambda: K.bn_relu_bwd_mask(gy, gate, wv, vv, 1e-5, BN_VARIANT, want_identity=True))
     rep("bn_relu_bwd_mask + g_identity", 3 * nb + nb // 32, ms)
     del act, idt, gy, yv, ym, gate
+    # layer4 of the benchmark's pass (HW = 49: the flat 16-byte path): residual forms at 50 x 2048 x 7 x 7, plain forms at
+    # 50 x 512 x 7 x 7.  Yardstick: the float4 kernels on the SAME buffers viewed with HW = 196 (same n, same bytes).
+    for tag, shape, twin, residual in (("50x2048x7x7", (50, 2048, 7, 7), (50, 512, 14, 14), True), ("50x512x7x7", (50, 512, 7, 7), (50, 128, 14, 14), False)):
+        a4, i4, g4, h4 = (torch.randn(shape, device=DEV) for _ in range(4))
+        nb = a4.numel() * 4
+        for view, note in ((shape, "HW=49"), (twin, "HW=196 twin")):
+            Cv = view[1]
+            wv, bv, mv, vv = (torch.rand(Cv, device=DEV) + 0.5 for _ in range(4))
+            w2, b2, m2, v2 = (torch.rand(Cv, device=DEV) + 0.5 for _ in range(4))
+            av, iv, gv, hv = (t.view(view) for t in (a4, i4, g4, h4))
+            idv = iv if residual else None
+            ops = 3 if residual else 2
+            ms = timeit(lambda: K.bn_act_fwd(av, idv, wv, bv, mv, vv, 1e-5, BN_VARIANT))
+            rep(f"bn_act_fwd {tag}", ops * nb, ms, note)
+            yv, gate = K.bn_relu_fwd_mask(av, idv, wv, bv, mv, vv, 1e-5, BN_VARIANT)
+            ms = timeit(lambda: K.bn_relu_fwd_mask(av, idv, wv, bv, mv, vv, 1e-5, BN_VARIANT, mask=gate))
+            rep(f"bn_relu_fwd_mask {tag}", ops * nb + nb // 32, ms, note)
+            ms = timeit(lambda: K.bn_relu_bwd(gv, yv, wv, vv, 1e-5, BN_VARIANT, want_identity=residual, gy2=hv))
+            rep(f"bn_relu_bwd 2 grads {tag}", (ops + 2) * nb, ms, note)
+            ms = timeit(lambda: K.bn_relu_bwd_mask(gv, gate, wv, vv, 1e-5, BN_VARIANT, want_identity=residual, gy2=hv))
+            rep(f"bn_relu_bwd_mask 2 grads {tag}", (ops + 1) * nb + nb // 32, ms, note)
+            ms = timeit(lambda: K.bn_relu_bwd_mask(gv, gate, wv, vv, 1e-5, BN_VARIANT, want_identity=residual, gy2=hv, guided=True))
+            rep(f"bn_relu_bwd_mask guided {tag}", (ops + 1) * nb + nb // 32, ms, note)
+            if residual:                                  # the down-sample block: the identity operand has a BatchNorm of its own
+                ms = timeit(lambda: K.bn_relu_fwd_mask(av, iv, wv, bv, mv, vv, 1e-5, BN_VARIANT, bn2=(w2, b2, m2, v2, 1e-5), mask=gate))
+                rep(f"bn_relu_fwd_mask +bn2 {tag}", 3 * nb + nb // 32, ms, note)
+                ms = timeit(lambda: K.bn_relu_bwd_mask(gv, gate, wv, vv, 1e-5, BN_VARIANT, gy2=hv, bn2=(w2, v2, 1e-5)))
+                rep(f"bn_relu_bwd_mask +bn2 {tag}", 4 * nb + nb // 32, ms, note)
+        del a4, i4, g4, h4, av, iv, gv, hv, yv, gate
     # the stem of one benchmark pass (50 x 64 x 112 x 112 -> 56 x 56) with autograd, and the five-kernel chain it replaces
     sx = torch.randn(50, 64, 112, 112, device=DEV)
     sw, sb, sm, sv = (torch.rand(64, device=DEV) + 0.5 for _ in range(4))

@@ -135,9 +135,10 @@ def _harness_map(samples, H, W, shared):
     """resize -> |sum over channels| of evaluatePerturbation.py:92,181 from the g x g samples (B, C, g, g) -> (B, H, W).  With one id
     plane for all channels the C planes are identical and |a + a + a| is the up-sample kernel's scale 3, abs (as the gc row)."""
     B, C, g, _ = samples.shape
+    # g is the caller's: resize_bilinear is K3 while g <= H, W and the reference's antialiased resize beyond
     if shared and C <= 3:
-        return K.bilinear_up(samples[:, 0].contiguous(), H, W, scale=float(C), take_abs=True)
-    return abs_channel_sum(K.bilinear_up(samples.reshape(B * C, g, g), H, W).view(B, C, H, W))
+        return K.resize_bilinear(samples[:, 0].contiguous(), H, W, scale=float(C), take_abs=True)
+    return abs_channel_sum(K.resize_bilinear(samples.reshape(B * C, g, g), H, W).view(B, C, H, W))
 
 
 def _run(x, model, tgt, n_total, fill, pass_size, streams, graphs):

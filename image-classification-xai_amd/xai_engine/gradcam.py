@@ -143,15 +143,17 @@ def patch_captum():
 def gradcam_saliency(model, layer, inputs, target, out_hw, channels=3, graphs=False):
     """The (B,H,W) map get_CNN_attr produces for "gc": |sum of `channels` copies of the
     up-sampled, ReLU'd cam| (reference evaluatePerturbation.py:147-153,181), fused into the
-    up-sample kernel as scale = channels, take_abs.  `graphs`: as ONE replay of this thread's hipGraph of the pass
-    (`CapturedGradCam`, kept per model, input shape, layer and output size)."""
+    up-sample kernel as scale = channels, take_abs.  A layer of higher resolution than `out_hw` along either axis is resized as
+    the reference does it, antialiased (`K.resize_bilinear`): K3's plain bilinear is that resize only while no axis shrinks.
+    `graphs`: as ONE replay of this thread's hipGraph of the pass (`CapturedGradCam`, kept per model, input shape, layer and
+    output size)."""
     if graphs:
         hw = (int(out_hw[0]), int(out_hw[1]))
         cap = _PASSES.get(model, inputs.device, (tuple(inputs.shape), id(layer), hw, channels),
                           lambda: CapturedGradCam(model, layer, inputs, hw, channels))
         return cap(inputs, target)
     cam = LayerGradCam(model, layer).attribute(inputs, target, relu_attributions=True)
-    return K.bilinear_up(cam[:, 0].contiguous(), out_hw[0], out_hw[1], scale=float(channels), take_abs=True)
+    return K.resize_bilinear(cam[:, 0].contiguous(), out_hw[0], out_hw[1], scale=float(channels), take_abs=True)
 
 
 class CapturedGradCam(CapturedCall):

@@ -206,12 +206,33 @@ def gradcam(act, grad, relu=True):
 
 
 def bilinear_up(src, H, W, scale=1.0, take_abs=False):
-    """(B,h,w) -> (B,H,W), align_corners=False."""
+    """(B,h,w) -> (B,H,W), align_corners=False.  Plain two-tap bilinear on both axes: equal to the reference's antialiased
+    resize (torchvision Resize(antialias=True)) only when no axis shrinks -- `resize_bilinear` is the call that follows the
+    reference either way."""
     _need(src, F32, "src")
     B, h, w = src.shape
     dst = torch.empty((B, H, W), dtype=F32, device=src.device)
     _call("xai_bilinear_up_f32", src.device, _ptr(src), B, h, w, int(H), int(W), float(scale), int(bool(take_abs)), _ptr(dst))
     return dst
+
+
+def resize_bilinear(src, H, W, scale=1.0, take_abs=False):
+    """The reference's `Resize((H, W), antialias=True)` of (B,h,w) maps, times `scale`, optionally |.|: K3's `bilinear_up` while no
+    axis shrinks (there the antialias filter is the two bilinear taps); with a shrinking axis the filter widens, and the map is
+    torch's antialiased interpolation on the device.  A torch build without that op on the device is an error, never the plain
+    bilinear."""
+    _need(src, F32, "src")
+    B, h, w = src.shape
+    H, W = int(H), int(W)
+    if H >= h and W >= w:
+        return bilinear_up(src, H, W, scale=scale, take_abs=take_abs)
+    try:
+        out = torch.nn.functional.interpolate(src[:, None], size=(H, W), mode="bilinear", align_corners=False, antialias=True)[:, 0]
+    except (RuntimeError, NotImplementedError) as e:
+        raise _lib.XaiHipError(f"resize_bilinear: ({h}, {w}) -> ({H}, {W}) shrinks an axis, which needs the antialiased bilinear "
+                               f"interpolation, and this torch build has none for {src.device}: {e}") from e
+    out = out * float(scale)
+    return out.abs() if take_abs else out
 
 
 # ------------------------------------------------------------------------------ RISE

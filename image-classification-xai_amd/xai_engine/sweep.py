@@ -207,6 +207,7 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
     else:
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit
+    # sal is the (1, p, p) patch grid of an img_hw-pixel input, p = img_hw / patch size: no axis shrinks, plain bilinear is the reference's resize
     return K.bilinear_up(sal.detach().float().contiguous(), img_hw, img_hw, scale=1.0, take_abs=True)[0].cpu().numpy()
 
 

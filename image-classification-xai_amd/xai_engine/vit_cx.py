@@ -149,5 +149,6 @@ def ViT_CX(model, image, target_layer, target_category=None, distance_threshold=
     mask_clustering_norm, _ = cluster_masks(mask, distance_threshold)
     scorer = causal_score(model_softmax, (H, W), gpu_batch=gpu_batch, device=device, device_noise=device_noise)
     sal = scorer(image, mask_clustering_norm, class_p, target_category=target_category, noise=noise)
+    # no axis shrinks here: K.up_rownorm above has refused an (H, W) below the feature map's (h, w)
     feature_map = K.bilinear_up(fmap, H, W).cpu() if return_feature_map else None
     return sal.cpu(), feature_map

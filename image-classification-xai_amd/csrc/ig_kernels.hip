@@ -82,8 +82,13 @@ __global__ __launch_bounds__(kWave) void ig_cutoff_kernel(const float* __restric
   const float* lg = logits + static_cast<int64_t>(blockIdx.x) * n_steps;
   const int lane = threadIdx.x;
   float m = -INFINITY;
-  for (int s = lane; s < n_steps; s += kWave) m = fmaxf(m, lg[s]);
-  m = wave_max(m);
+  int nan = 0;                                      // fmaxf drops a NaN; torch.max keeps it, and nothing is above a NaN threshold
+  for (int s = lane; s < n_steps; s += kWave) {
+    const float v = lg[s];
+    nan |= (v != v);
+    m = fmaxf(m, v);
+  }
+  m = wave_max(nan) ? NAN : wave_max(m);
   const float thr = m * alpha_star;
   int first = INT32_MAX;
   for (int s = lane; s < n_steps; s += kWave)

@@ -1,5 +1,6 @@
-"""ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h) and of the extension library libxai_ext.so
-(include/xai_hip_ext.h: the entry points added after xai_hip.h was frozen at ABI 1.11).
+"""ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h) and of the extension libraries libxai_ext.so
+(include/xai_hip_ext.h: the entry points added after xai_hip.h was frozen at ABI 1.11) and libxai_ext2.so
+(include/xai_hip_ext2.h: the ones added after xai_hip_ext.h was frozen too).
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers below are read
 from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing
@@ -17,9 +18,13 @@ EXT_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext.so")
 EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext.h")
 ABI_DEFINES = ("XAI_ABI_VERSION", "XAI_ABI_MINOR")
 EXT_DEFINES = ("XAI_EXT_VERSION", "XAI_EXT_MINOR")
+EXT2_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext2.so")
+EXT2_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext2.h")
+EXT2_DEFINES = ("XAI_EXT2_VERSION", "XAI_EXT2_MINOR")
 
 _lib = None
 _ext = None
+_ext2 = None
 
 
 class XaiHipError(RuntimeError):
@@ -100,10 +105,20 @@ def _read_ext_header():
         raise XaiHipError(f"{EXT_HEADER_PATH}: the extension ABI cannot be bound from its header: {e}") from e
 
 
+def _read_ext2_header():
+    try:
+        with open(EXT2_HEADER_PATH) as f:
+            return parse_header(f.read(), EXT2_DEFINES)
+    except (OSError, XaiHipError) as e:
+        raise XaiHipError(f"{EXT2_HEADER_PATH}: the second extension ABI cannot be bound from its header: {e}") from e
+
+
 # name -> argument types / return type of every prototype, and the XAI_ABI_VERSION / XAI_ABI_MINOR the header declares
 SIGNATURES, _RESTYPE, (ABI_VERSION, ABI_MINOR) = _read_header()
 # the same for the extension header and its XAI_EXT_VERSION / XAI_EXT_MINOR
 EXT_SIGNATURES, _EXT_RESTYPE, (EXT_VERSION, EXT_MINOR) = _read_ext_header()
+# and for the second extension header and its XAI_EXT2_VERSION / XAI_EXT2_MINOR
+EXT2_SIGNATURES, _EXT2_RESTYPE, (EXT2_VERSION, EXT2_MINOR) = _read_ext2_header()
 
 
 def load():
@@ -156,6 +171,30 @@ def load_ext():
         fn.argtypes = argtypes
         fn.restype = _EXT_RESTYPE[name]
     _ext = lib
+    return lib
+
+
+def load_ext2():
+    """Load the second extension library once, as strictly as `load_ext()`: absent -> XaiHipError, the version pair first, then
+    every prototype of include/xai_hip_ext2.h (AttributeError if the .so is stale).  Never falls back."""
+    global _ext2
+    if _ext2 is not None:
+        return _ext2
+    csrc = os.path.join(os.path.dirname(_HERE), "csrc")
+    if not os.path.exists(EXT2_LIB_PATH):
+        raise XaiHipError(f"{EXT2_LIB_PATH} not found: the second HIP extension library is not built. Run `make -C {csrc}` (needs "
+                          "hipcc, targets gfx950). There is deliberately no CPU fallback.")
+    lib = C.CDLL(EXT2_LIB_PATH)
+    lib.xai_ext2_version.restype = lib.xai_ext2_version_minor.restype = C.c_int
+    major, minor = lib.xai_ext2_version(), lib.xai_ext2_version_minor()
+    if major != EXT2_VERSION or minor < EXT2_MINOR:
+        raise XaiHipError(f"{EXT2_LIB_PATH} has ABI {major}.{minor}, this package needs {EXT2_VERSION}.{EXT2_MINOR} or a later minor "
+                          f"(include/xai_hip_ext2.h); rebuild with `make -C {csrc}`")
+    for name, argtypes in EXT2_SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError if the .so is stale
+        fn.argtypes = argtypes
+        fn.restype = _EXT2_RESTYPE[name]
+    _ext2 = lib
     return lib
 
 

@@ -226,14 +226,14 @@ def evaluate_perturbation(testing_dict, rank=0, world=1, fused=True, out_dir="pe
         return (_sweep.get_VIT_attr if is_vit else _sweep.get_CNN_attr)(x, None, target, td_attr)
 
     # rows that need the un-normalised image the harness loaded (the reference passes trans_img, :584) get load_image's tensor
-    extra = not is_vit and testing_dict["attr_func"] in _sweep.TRANS_ATTR_FUNCS
+    extra = testing_dict["attr_func"] in (_sweep.VIT_TRANS_ATTR_FUNCS if is_vit else _sweep.TRANS_ATTR_FUNCS)
     if extra:
         images = images.with_trans()
 
         def attr_fn(x, target, trans_and_name):             # noqa: F811
             trans, name = trans_and_name
             try:
-                return _sweep.get_CNN_attr(x, trans, target, td_attr)
+                return (_sweep.get_VIT_attr if is_vit else _sweep.get_CNN_attr)(x, trans, target, td_attr)
             except ValueError as e:
                 raise ValueError(f"{name}: {e}") from e
 

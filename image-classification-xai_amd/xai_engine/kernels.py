@@ -1086,3 +1086,87 @@ def gshap_finish(grads, x, baselines, idx, n_samples, want_attr=True, want_map=F
     if want_attr and want_map:
         return attr, map
     return attr if want_attr else map
+
+
+# ------------------------------------------------------------------------------ MDA (K36, K37, K38; libxai_ext2.so)
+def _call_ext2(name, dev, *args):
+    """`_call` for an entry of the second extension library (include/xai_hip_ext2.h); the error texts are xai_strerror's."""
+    lib = _lib.load_ext2()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+
+
+def mda_max_segments():
+    """The largest number of segments of one image K37 takes."""
+    return int(_lib.load_ext2().xai_mda_max_segments())
+
+
+def mda_max_width():
+    """The largest sub-search width (candidates per step) K37 takes."""
+    return int(_lib.load_ext2().xai_mda_max_width())
+
+
+def _mda_images(start, finish, seg, name):
+    """start, finish (n_img, C, H, W) float32, seg (n_img, H, W) int32 -> (n_img, C, H * W)"""
+    _need(start, F32, "start"); _need(finish, F32, "finish"); _need(seg, I32, "seg")
+    if start.dim() != 4 or finish.shape != start.shape or start.numel() == 0:
+        raise ValueError(f"{name}: start and finish must be (n_img, C, H, W) of one shape")
+    n_img, Cc, H, W = start.shape
+    if tuple(seg.shape) != (n_img, H, W):
+        raise ValueError(f"{name}: seg must be ({n_img}, {H}, {W}), got {tuple(seg.shape)}")
+    return n_img, Cc, H * W
+
+
+def mda_compose(start, finish, seg, cand, out=None):
+    """K36: out[img][r] = start[img] with the pixels of segment cand[img][r] taken from finish[img] (a select; a label no pixel
+    carries, such as K37's -1, gives a copy of start).  start, finish (n_img, C, H, W); seg int32 (n_img, H, W); cand int32
+    (n_img, L) -> (n_img * L, C, H, W)."""
+    n_img, Cc, hw = _mda_images(start, finish, seg, "mda_compose")
+    _need(cand, I32, "cand")
+    if cand.dim() != 2 or cand.shape[0] != n_img or cand.shape[1] == 0:
+        raise ValueError(f"mda_compose: cand must be ({n_img}, L), got {tuple(cand.shape)}")
+    L = cand.shape[1]
+    out = _out(out, "out", (n_img * L,) + tuple(start.shape[1:]), start)
+    _call_ext2("xai_mda_compose_f32", start.device, _ptr(start), _ptr(finish), _ptr(seg), _ptr(cand), n_img, L, Cc, hw, _ptr(out))
+    return out
+
+
+def mda_select(resp, order, plan, stop_ref, mode, cutoff, mr, chosen, taken, cand, state, stop_test=None):
+    """K37: one search step's decision for every image, in place on the caller's arrays: resp float32 (n_img, L); order int32
+    (n_img, S); plan int32 (n_img, plan_stride, 3) rows of (slot, n_cand, cutoff_slot); stop_ref float32 (n_img, 2) = (blur_pred,
+    |original_pred - blur_pred|) or None; mr float32, chosen, taken int32 (n_img, S); cand int32 (n_img, L); state int32 (n_img, 4)
+    = (steps taken, done, last winner, plan rows).  mode 1: argmax and the stop test against `cutoff` (stop_test: default
+    cutoff != 1, the reference's guard); mode 0: argmin."""
+    _need(resp, F32, "resp"); _need(order, I32, "order"); _need(plan, I32, "plan"); _need(mr, F32, "mr")
+    _need(chosen, I32, "chosen"); _need(taken, I32, "taken"); _need(cand, I32, "cand"); _need(state, I32, "state")
+    if resp.dim() != 2 or order.dim() != 2 or plan.dim() != 3 or plan.shape[2] != 3 or plan.shape[1] == 0:
+        raise ValueError("mda_select: resp must be (n_img, L), order (n_img, S) and plan (n_img, plan_stride, 3)")
+    n_img, L = resp.shape
+    S = order.shape[1]
+    if order.shape[0] != n_img or plan.shape[0] != n_img or L == 0 or S == 0:
+        raise ValueError("mda_select: resp, order and plan disagree about the number of images")
+    for t, shape, name in ((mr, (n_img, S), "mr"), (chosen, (n_img, S), "chosen"), (taken, (n_img, S), "taken"),
+                           (cand, (n_img, L), "cand"), (state, (n_img, 4), "state")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"mda_select: {name} must be {shape}, got {tuple(t.shape)}")
+    if mode not in (0, 1):
+        raise ValueError("mda_select: mode is 0 (argmin) or 1 (argmax and the stop test)")
+    stop_test = (mode == 1 and cutoff != 1) if stop_test is None else bool(stop_test)
+    if mode == 1 and stop_test:
+        if stop_ref is None:
+            raise ValueError("mda_select: the stop test needs stop_ref")
+        _need(stop_ref, F32, "stop_ref")
+        if tuple(stop_ref.shape) != (n_img, 2):
+            raise ValueError(f"mda_select: stop_ref must be ({n_img}, 2), got {tuple(stop_ref.shape)}")
+    _call_ext2("xai_mda_select_f32", resp.device, _ptr(resp), _ptr(order), _ptr(plan), _ptr(stop_ref), n_img, S, L, plan.shape[1],
+               int(mode), int(stop_test), float(cutoff), _ptr(mr), _ptr(chosen), _ptr(taken), _ptr(cand), _ptr(state))
+
+
+def mda_commit(finish, seg, state, start):
+    """K38: start[img] takes the pixels of segment state[img][2] (the last winner; < 0: none) from finish[img], in place."""
+    n_img, Cc, hw = _mda_images(start, finish, seg, "mda_commit")
+    _need(state, I32, "state")
+    if tuple(state.shape) != (n_img, 4):
+        raise ValueError(f"mda_commit: state must be ({n_img}, 4), got {tuple(state.shape)}")
+    _call_ext2("xai_mda_commit_f32", start.device, _ptr(finish), _ptr(seg), _ptr(state), n_img, Cc, hw, _ptr(start))
+    return start

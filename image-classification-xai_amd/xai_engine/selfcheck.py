@@ -309,6 +309,26 @@ def run(device="cuda:0", verbose=True):
     check("lime_fit", worst, 1e-9)
     ltab = rnd(2, 128)
     check("lime_paint", float(not torch.equal(K.lime_paint(ltab, lseg), ltab.gather(1, lseg.view(2, -1).long()).view(2, 20, 24))), 0.0)
+    # MDA (K36-K38, libxai_ext2.so): the select, one decision on a hand-made response row, the commit
+    mseg = torch.randint(0, 6, (2, 20, 24), device=dev, dtype=torch.int32)
+    mstart, mfinish = rnd(2, 3, 20, 24), rnd(2, 3, 20, 24)
+    mcand = torch.tensor([[3, 0, 5, -1], [1, 1, 4, 77]], dtype=torch.int32, device=dev)
+    mwant = torch.where(mseg[:, None, None] == mcand[:, :, None, None, None], mfinish[:, None], mstart[:, None]).reshape(8, 3, 20, 24)
+    check("mda_compose", float(not torch.equal(K.mda_compose(mstart, mfinish, mseg, mcand), mwant)), 0.0)
+    i32 = dict(dtype=torch.int32, device=dev)
+    mresp = torch.tensor([[0.2, 0.7, 0.7, 0.1], [0.3, 0.1, 0.1, 0.9]], device=dev)
+    morder = torch.tensor([[3, 0, 5, 2, 1, 4], [1, 4, 0, 2, 5, 3]], **i32)
+    mplan = torch.tensor([[[0, 3, 0], [1, 4, 1]], [[0, 3, -1], [1, 2, -1]]], **i32)
+    mmr, mchosen, mtaken = torch.zeros((2, 6), device=dev), torch.full((2, 6), -1, **i32), torch.zeros((2, 6), **i32)
+    mcur = torch.tensor([[3, 0, 5, -1], [1, 4, 0, -1]], **i32)
+    mstate = torch.tensor([[0, 0, -1, 2], [0, 0, -1, 2]], **i32)
+    K.mda_select(mresp, morder, mplan, torch.tensor([[0.1, 0.5], [0.1, 0.5]], device=dev), 1, 0.95, mmr, mchosen, mtaken, mcur, mstate)
+    # image 0: the first 0.7 (segment 0), (0.7 - 0.1) / 0.5 >= 0.95 stops it; image 1: 0.3 (segment 1), goes on with the next two untaken
+    good = (mchosen[:, 0].tolist() == [0, 1] and mstate.tolist() == [[1, 1, 0, 2], [1, 0, 1, 2]] and mcur.tolist() == [[-1] * 4, [4, 0, -1, -1]]
+            and mmr[:, 0].tolist() == [torch.tensor(0.95).item(), torch.tensor(0.3).item()] and mtaken.sum(1).tolist() == [1, 1])
+    check("mda_select", float(not good), 0.0)
+    mcommitted = torch.where(mseg[:, None] == mstate[:, 2].view(2, 1, 1, 1), mfinish, mstart)
+    check("mda_commit", float(not torch.equal(K.mda_commit(mfinish, mseg, mstate, mstart.clone()), mcommitted)), 0.0)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

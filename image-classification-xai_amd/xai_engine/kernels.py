@@ -1170,3 +1170,107 @@ def mda_commit(finish, seg, state, start):
         raise ValueError(f"mda_commit: state must be ({n_img}, 4), got {tuple(state.shape)}")
     _call_ext2("xai_mda_commit_f32", start.device, _ptr(finish), _ptr(seg), _ptr(state), n_img, Cc, hw, _ptr(start))
     return start
+
+
+# ------------------------------------------------------------------------------ sanity test (K39-K43; libxai_ext2.so)
+def _workspace_ext2(entry, dev, *extents):
+    """`_workspace` for a *_workspace_bytes entry of the second extension library; 0 bytes there means the extents are refused."""
+    nbytes = int(getattr(_lib.load_ext2(), entry)(*extents))
+    if nbytes <= 0:
+        raise ValueError(f"{entry}{extents}: no such workspace (an extent is not positive, or too large)")
+    return torch.empty(nbytes, dtype=U8, device=dev), nbytes
+
+
+def _maps(t, name):
+    """(n, H, W) float32 maps with at least one element"""
+    _need(t, F32, name)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{name} must be (n, H, W) with n, H, W >= 1, got {tuple(t.shape)}")
+    return t.shape
+
+
+def sanity_normalize(x, guard=True, out=None):
+    """K39: x (n, ...) float32 -> every map normalize_image'd (evaluateSanity.py:68-79; guard=False: sanityForMethods.py:60-72)."""
+    _need(x, F32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"sanity_normalize: x must be (n, ...) with at least one element per map, got {tuple(x.shape)}")
+    out = _out(out, "out", x.shape, x)
+    _call_ext2("xai_sanity_normalize_f32", x.device, _ptr(x), x.shape[0], x[0].numel(), int(bool(guard)), _ptr(out))
+    return out.view(x.shape)
+
+
+def ssim_tile():
+    """The extent of K40's square output tile."""
+    return int(_lib.load_ext2().xai_ssim_tile())
+
+
+def ssim_weights(sigma=1.5, truncate=3.5):
+    """The distinct weights of scipy.ndimage's Gaussian, outermost first and the centre last, computed as _gaussian_kernel1d does
+    (NumPy's exp and its sum, so the bits are scipy's): six fp64 numbers for sigma 1.5 and truncate 3.5."""
+    import numpy as np
+    radius = int(truncate * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return [float(v) for v in (phi / phi.sum())[:radius + 1]]
+
+
+def ssim(x, y, data_range=2.0, want_map=False):
+    """K40: x, y (n, H, W) float32 -> mean SSIM (n,) float64 [, the full S map (n, H, W) float32]: skimage's
+    structural_similarity(gaussian_weights=True, data_range=data_range) per pair."""
+    n, H, W = _maps(x, "x")
+    _shaped_like(y, x, "y", "x")
+    if H < 11 or W < 11:
+        raise ValueError(f"ssim: the Gaussian window is 11 x 11, the maps are {H} x {W}")
+    c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
+    ws, nbytes = _workspace_ext2("xai_ssim_workspace_bytes", x.device, n, H, W)
+    mean = torch.empty(n, dtype=F64, device=x.device)
+    S = torch.empty((n, H, W), dtype=F32, device=x.device) if want_map else None
+    _call_ext2("xai_ssim_f32", x.device, _ptr(x), _ptr(y), n, H, W, *ssim_weights(), c1, c2, _ptr(mean), _ptr(S), _ptr(ws),
+               nbytes)
+    return (mean, S) if want_map else mean
+
+
+def tie_ranks_chunk():
+    """The number of sorted positions one workgroup of K41 handles."""
+    return int(_lib.load_ext2().xai_tie_ranks_chunk())
+
+
+def tie_ranks(vals, order):
+    """K41: vals (n_rows, n) float32 and their stable ascending argsort (K8's `order`) -> int32 (n_rows, n): twice each element's
+    rankdata(method='average') rank."""
+    _need(vals, F32, "vals"); _need(order, I32, "order")
+    if vals.dim() != 2 or vals.numel() == 0 or order.shape != vals.shape:
+        raise ValueError(f"tie_ranks: vals and order must be (n_rows, n) of one shape, got {tuple(vals.shape)} and {tuple(order.shape)}")
+    out = torch.empty_like(order)
+    _call_ext2("xai_tie_ranks_i32", vals.device, _ptr(vals), _ptr(order), vals.shape[0], vals.shape[1], _ptr(out))
+    return out
+
+
+def rank_corr_max_n():
+    """The largest row length K42 takes."""
+    return int(_lib.load_ext2().xai_rank_corr_max_n())
+
+
+def rank_corr(ra, rb, a=None, b=None):
+    """K42: doubled ranks ra, rb int32 (n_pairs, n) [, the ranked values a, b float32 for the NaN test] -> float64 (n_pairs,):
+    scipy.stats.spearmanr's statistic of each pair."""
+    _need(ra, I32, "ra"); _need(rb, I32, "rb")
+    if ra.dim() != 2 or ra.numel() == 0 or rb.shape != ra.shape:
+        raise ValueError(f"rank_corr: ra and rb must be (n_pairs, n) of one shape, got {tuple(ra.shape)} and {tuple(rb.shape)}")
+    _shaped_like(a, ra, "a", "ra"); _shaped_like(b, ra, "b", "ra")
+    out = torch.empty(ra.shape[0], dtype=F64, device=ra.device)
+    _call_ext2("xai_rank_corr_f64", ra.device, _ptr(ra), _ptr(rb), _ptr(a), _ptr(b), ra.shape[0], ra.shape[1], _ptr(out))
+    return out
+
+
+def hog(img, cell=(16, 16)):
+    """K43: img (n, H, W) float32 -> float32 (n, (H // ch - 2) * (W // cw - 2) * 81): skimage.feature.hog(orientations=9,
+    pixels_per_cell=cell, cells_per_block=(3, 3), block_norm='L2-Hys') of every map, flattened as skimage flattens it."""
+    n, H, W = _maps(img, "img")
+    ch, cw = int(cell[0]), int(cell[1])
+    if ch < 1 or cw < 1 or H // ch < 3 or W // cw < 3:
+        raise ValueError(f"hog: {H} x {W} pixels in cells of {ch} x {cw} give fewer than 3 cells on an axis")
+    ws, nbytes = _workspace_ext2("xai_hog_workspace_bytes", img.device, n, H, W, ch, cw)
+    out = torch.empty((n, (H // ch - 2) * (W // cw - 2) * 81), dtype=F32, device=img.device)
+    _call_ext2("xai_hog_f32", img.device, _ptr(img), n, H, W, ch, cw, _ptr(out), _ptr(ws), nbytes)
+    return out

@@ -329,6 +329,48 @@ def run(device="cuda:0", verbose=True):
     check("mda_select", float(not good), 0.0)
     mcommitted = torch.where(mseg[:, None] == mstate[:, 2].view(2, 1, 1, 1), mfinish, mstart)
     check("mda_commit", float(not torch.equal(K.mda_commit(mfinish, mseg, mstate, mstart.clone()), mcommitted)), 0.0)
+    # sanity test (K39-K43, libxai_ext2.so): each kernel against torch on the device
+    sx = torch.rand(3, 40, 52, device=dev, generator=gen)
+    sx[1, 3, 4] = float("inf")
+    fixed = torch.where(sx.isinf(), torch.zeros_like(sx), sx)
+    lo, hi = fixed.amin((1, 2), keepdim=True), fixed.amax((1, 2), keepdim=True)
+    snorm = K.sanity_normalize(sx)
+    check("sanity_normalize", _rel(snorm, (fixed - lo) / (hi - lo)), 1e-6)
+    sa, sb = snorm[:2].contiguous(), torch.rand(2, 40, 52, device=dev, generator=gen)
+    taps = torch.tensor(K.ssim_weights(), dtype=torch.float64, device=dev)
+    taps = torch.cat([taps, taps[:5].flip(0)])
+
+    def gauss(t):             # scipy's mode='reflect' is the edge-repeating mirror: d c b a | a b c d | d c b a
+        t = torch.cat([t[:, :5].flip(1), t, t[:, -5:].flip(1)], 1)
+        t = torch.cat([t[:, :, :5].flip(2), t, t[:, :, -5:].flip(2)], 2)[:, None].double()
+        return F.conv2d(F.conv2d(t, taps.view(1, 1, 11, 1)), taps.view(1, 1, 1, 11))[:, 0]
+    ux, uy = gauss(sa), gauss(sb)
+    cn, c1, c2 = 121.0 / 120.0, (0.01 * 2.0) ** 2, (0.03 * 2.0) ** 2
+    vx, vy, vxy = cn * (gauss(sa * sa) - ux * ux), cn * (gauss(sb * sb) - uy * uy), cn * (gauss(sa * sb) - ux * uy)
+    smap = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+    smean, sfull = K.ssim(sa, sb, want_map=True)
+    check("ssim", max(_rel(sfull, smap), _rel(smean, smap[:, 5:-5, 5:-5].mean((1, 2)))), 1e-4)
+    rv = (torch.randn(4, 300, device=dev, generator=gen) * 3).round() / 2            # heavy ties
+    rorder, _ = K.rank(rv)
+    r2 = K.tie_ranks(rv, rorder)
+    less, leq = (rv[:, None, :] < rv[:, :, None]).sum(2), (rv[:, None, :] <= rv[:, :, None]).sum(2)
+    check("tie_ranks", float(not torch.equal(r2.long(), less + leq + 1)), 0.0)
+    ranks = r2.double() / 2
+    dv = ranks - ranks.mean(1, keepdim=True)
+    pearson = (dv[:2] * dv[2:]).sum(1) / ((dv[:2] ** 2).sum(1) * (dv[2:] ** 2).sum(1)).sqrt()
+    check("rank_corr", _rel(K.rank_corr(r2[:2], r2[2:], rv[:2], rv[2:]), pearson), 1e-12)
+    himg = torch.rand(2, 50, 70, device=dev, generator=gen)
+    g_row, g_col = torch.zeros_like(himg), torch.zeros_like(himg)
+    g_row[:, 1:-1], g_col[:, :, 1:-1] = himg[:, 2:] - himg[:, :-2], himg[:, :, 2:] - himg[:, :, :-2]
+    hmag = torch.hypot(g_col.double(), g_row.double())
+    hbin = (torch.rad2deg(torch.atan2(g_row.double(), g_col.double())).remainder(180.0) / 20.0).floor().long().clamp(0, 8)
+    cells = torch.zeros(2, 50, 70, 9, dtype=torch.float64, device=dev).scatter_(3, hbin[..., None], hmag[..., None])
+    cells = cells[:, :48, :64].reshape(2, 3, 16, 4, 16, 9).sum((2, 4)) / 256.0                          # (2, 3, 4, 9)
+    blocks = torch.stack([cells[:, :, j:j + 3] for j in range(2)], 1).reshape(2, 2, 81)                 # one block row, two block columns
+    blocks = blocks / (blocks.pow(2).sum(2, keepdim=True) + 1e-10).sqrt()
+    blocks = blocks.clamp(max=0.2)
+    blocks = blocks / (blocks.pow(2).sum(2, keepdim=True) + 1e-10).sqrt()
+    check("hog", float((K.hog(himg).double() - blocks.reshape(2, 162)).abs().max()), 1e-6)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

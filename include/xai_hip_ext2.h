@@ -27,9 +27,11 @@ typedef void* xai_stream_t; /* hipStream_t; the same typedef as xai_hip.h's */
 
 /* xai_ext2_version() = XAI_EXT2_VERSION: bumped when an existing prototype or its documented meaning changes.
  * xai_ext2_version_minor() = XAI_EXT2_MINOR: bumped whenever entry points are added:
- *   0 = xai_mda_max_segments, xai_mda_max_width, xai_mda_compose_f32, xai_mda_select_f32, xai_mda_commit_f32 */
+ *   0 = xai_mda_max_segments, xai_mda_max_width, xai_mda_compose_f32, xai_mda_select_f32, xai_mda_commit_f32
+ *   1 = xai_sanity_normalize_f32, xai_ssim_tile, xai_ssim_workspace_bytes, xai_ssim_f32, xai_tie_ranks_chunk, xai_tie_ranks_i32,
+ *       xai_rank_corr_max_n, xai_rank_corr_f64, xai_hog_workspace_bytes, xai_hog_f32 */
 #define XAI_EXT2_VERSION 1
-#define XAI_EXT2_MINOR 0
+#define XAI_EXT2_MINOR 1
 
 int xai_ext2_version(void);
 int xai_ext2_version_minor(void);
@@ -77,6 +79,83 @@ int xai_mda_select_f32(const float* resp, const int32_t* order, const int32_t* p
  *   finish, start : [n_img][C][HW];  seg : [n_img][HW];  state : [n_img][4] */
 int xai_mda_commit_f32(const float* finish, const int32_t* seg, const int32_t* state, int n_img, int C, int64_t HW,
                        float* start, xai_stream_t stream);
+
+/* ---- sanity test (xai_engine/sanity.py): the map comparison of evaluateSanity.py get_sanity ---- */
+
+/* K39 out[m] = normalize_image(x[m]) for every map m < n, in fp32 and in the reference's order:
+ *       mn, mx = min, max of the map with NumPy's NaN rule (one NaN makes both NaN)
+ *       guard != 0 and mx - mn == 0: the map is copied through unchanged
+ *       every +Inf and -Inf becomes 0;  mn, mx again on the fixed map;  out = (x - mn) / (mx - mn), a true fp32 division
+ *     so a map that is constant once its Inf are gone becomes all NaN (0 / 0).
+ * replaces  evaluateSanity.py:68-79 normalize_image (guard = 1);  util/test_methods/sanityForMethods.py:60-72 (guard = 0)
+ *   x, out : [n][hw] (out may be x);  16-byte accesses when hw % 4 == 0 and both are 16-byte aligned */
+int xai_sanity_normalize_f32(const float* x, int n, int64_t hw, int guard, float* out, xai_stream_t stream);
+
+/* the extent of K40's square output tile */
+int xai_ssim_tile(void);
+/* bytes of K40's scratch: one fp64 partial sum per tile and pair (0: an extent is not positive or the count leaves int) */
+int xai_ssim_workspace_bytes(int n, int H, int W);
+
+/* K40 mean[p] = structural_similarity(x[p], y[p], gaussian_weights=True) of skimage on one fp32 channel, for every pair p < n.
+ *     The filter is scipy.ndimage.gaussian_filter(sigma=1.5, truncate=3.5, mode='reflect') (radius 5) on x, y, x*x, y*y, x*y (each
+ *     product one fp32 multiply): along axis 0, rounded to fp32, then along axis 1; every sample accumulates in fp64 in scipy's
+ *     symmetric order, centre * w5 then (in[i+j] + in[i-j]) * w(j+5) for j = -5 .. -1; indices reflect as d c b a | a b c d | d c b a.
+ *     w0 .. w5 are scipy's weights exp(-0.5 / sigma^2 * k^2) / sum for k = -5 .. 0, computed by the caller; the kernel calls no exp.
+ *     Then in fp32, every operation rounded, with cov_norm = 121 / 120:
+ *       vx = cov_norm * (uxx - ux * ux), vy and vxy likewise
+ *       S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
+ *     C1 = (0.01 R)^2 and C2 = (0.03 R)^2 of the data range R come from the caller.
+ *     mean[p] is the fp64 mean of S over the interior (5 pixels cropped on every side): fp64 partial sums per tile in one fixed
+ *     tree, the tiles added in ascending order.  S, when not NULL, receives the full uncropped map (skimage's full=True).
+ * replaces  evaluateSanity.py:89 and :93 (sanityForMethods.py:82 and :86): ssim(..., gaussian_weights=True) per channel
+ *   x, y : [n][H][W];  mean : [n] fp64;  S : [n][H][W] or NULL;  ws : xai_ssim_workspace_bytes(n, H, W) bytes, 8-byte aligned
+ *   H < 11 or W < 11 -> XAI_E_SHAPE (skimage raises);  n > 65535 or more than 65535 tile rows -> XAI_E_UNSUPPORTED */
+int xai_ssim_f32(const float* x, const float* y, int n, int H, int W, double w0, double w1, double w2, double w3, double w4,
+                 double w5, float C1, float C2, double* mean, float* S, void* ws, size_t ws_bytes, xai_stream_t stream);
+
+/* the number of sorted positions one workgroup of K41 handles */
+int xai_tie_ranks_chunk(void);
+
+/* K41 ranks2[r][i] = 2 * rankdata(vals[r], method='average')[i] = lo + hi + 2, an exact integer, where lo .. hi are the sorted
+ *     positions of the elements equal (==, so -0 ties with +0) to vals[r][i].  `order` is the stable ascending argsort of each row,
+ *     as K8 (xai_rank_f32) writes it.  A tie group may have any length up to the whole row.  A row with a NaN gets ranks that mean
+ *     nothing (K42 answers NaN for it).
+ * replaces  evaluateSanity.py:97-98 (sanityForMethods.py:79, :90): the rankdata inside scipy.stats.spearmanr
+ *   vals : [n_rows][n];  order, ranks2 : [n_rows][n] int32;  n > 2^30 or n_rows > 65535 -> XAI_E_UNSUPPORTED */
+int xai_tie_ranks_i32(const float* vals, const int32_t* order, int n_rows, int64_t n, int32_t* ranks2, xai_stream_t stream);
+
+/* the largest row length K42 takes: 131072 */
+int xai_rank_corr_max_n(void);
+
+/* K42 out[p] = scipy.stats.spearmanr(a[p], b[p]).statistic from the doubled ranks ra[p], rb[p] of K41, bit for bit:
+ *       d = r - (n + 1);  Saa, Sbb, Sab = the exact int64 sums of da * da, db * db, da * db
+ *       inv = 1.0 / (n - 1);  c.. = (S.. / 4) * inv;  r = (cab / sqrt(cbb)) / sqrt(caa), clipped to [-1, 1]   -- numpy.corrcoef in fp64
+ *     A constant row gives 0 / 0 = NaN.  a, b are the ranked values (either may be NULL: not tested): a NaN in a[p] or b[p] makes
+ *     out[p] NaN, spearmanr's nan_policy='propagate'.
+ * replaces  evaluateSanity.py:97-98 (sanityForMethods.py:79, :90): spr(...) on the pixels and on the HOG vectors
+ *   ra, rb : [n_pairs][n] int32;  a, b : [n_pairs][n] or NULL;  out : [n_pairs] fp64
+ *   n < 2 -> XAI_E_SHAPE;  n > xai_rank_corr_max_n() -> XAI_E_UNSUPPORTED */
+int xai_rank_corr_f64(const int32_t* ra, const int32_t* rb, const float* a, const float* b, int n_pairs, int64_t n, double* out,
+                      xai_stream_t stream);
+
+/* bytes of K43's scratch: the fp64 cell histograms (0: an extent is not positive or the count leaves int) */
+int xai_hog_workspace_bytes(int n, int H, int W, int ch, int cw);
+
+/* K43 out[m] = skimage.feature.hog(img[m], orientations=9, pixels_per_cell=(ch, cw), cells_per_block=(3, 3), block_norm='L2-Hys')
+ *     on one fp32 channel:
+ *       g_row[1:-1, :] = img[2:, :] - img[:-2, :] in fp32, rows 0 and H-1 zero; g_col likewise along columns; both widened to fp64
+ *       mag = hypot(g_col, g_row);  ori = rad2deg(atan2(g_row, g_col)) modulo 180 by Python's rule (fmod, then + 180 if negative);
+ *           a value that rounds to exactly 180.0 falls in no bin
+ *       cells tile the top-left (H / ch) ch x (W / cw) cw pixels (a gradient at the last used row or column still reads the pixel
+ *           beyond it where there is one); bin i of a cell = the fp64 sum of mag over its pixels with 20 i <= ori < 20 (i + 1),
+ *           divided by ch * cw
+ *       every 3 x 3 block of cells at stride 1, in fp64:  v = b / sqrt(sum(b^2) + 1e-10);  v = min(v, 0.2);
+ *           v = v / sqrt(sum(v^2) + 1e-10);  stored as fp32
+ *     The sums are fixed trees, not row-major chains: a feature may differ from a NumPy restatement in the last fp32 bit.
+ * replaces  evaluateSanity.py:90-91 and :94-95 (sanityForMethods.py:83-84, :87-88): feature.hog(..., pixels_per_cell=(16, 16))
+ *   img : [n][H][W];  out : [n][H/ch - 2][W/cw - 2][3][3][9];  ws : xai_hog_workspace_bytes(n, H, W, ch, cw) bytes, 8-byte aligned
+ *   fewer than 3 cells on an axis -> XAI_E_SHAPE;  n or H / ch above 65535 -> XAI_E_UNSUPPORTED */
+int xai_hog_f32(const float* img, int n, int H, int W, int ch, int cw, float* out, void* ws, size_t ws_bytes, xai_stream_t stream);
 
 #ifdef __cplusplus
 }

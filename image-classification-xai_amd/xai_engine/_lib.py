@@ -1,6 +1,7 @@
 """ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h) and of the extension libraries libxai_ext.so
 (include/xai_hip_ext.h: the entry points added after xai_hip.h was frozen at ABI 1.11) and libxai_ext2.so
-(include/xai_hip_ext2.h: the ones added after xai_hip_ext.h was frozen too).
+(include/xai_hip_ext2.h: the ones added after xai_hip_ext.h was frozen too) and libxai_ext3.so (include/xai_hip_ext3.h: the ones
+added after xai_hip_ext2.h was pinned at 1.1).
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers below are read
 from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing
@@ -21,10 +22,14 @@ EXT_DEFINES = ("XAI_EXT_VERSION", "XAI_EXT_MINOR")
 EXT2_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext2.so")
 EXT2_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext2.h")
 EXT2_DEFINES = ("XAI_EXT2_VERSION", "XAI_EXT2_MINOR")
+EXT3_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext3.so")
+EXT3_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext3.h")
+EXT3_DEFINES = ("XAI_EXT3_VERSION", "XAI_EXT3_MINOR")
 
 _lib = None
 _ext = None
 _ext2 = None
+_ext3 = None
 
 
 class XaiHipError(RuntimeError):
@@ -113,12 +118,22 @@ def _read_ext2_header():
         raise XaiHipError(f"{EXT2_HEADER_PATH}: the second extension ABI cannot be bound from its header: {e}") from e
 
 
+def _read_ext3_header():
+    try:
+        with open(EXT3_HEADER_PATH) as f:
+            return parse_header(f.read(), EXT3_DEFINES)
+    except (OSError, XaiHipError) as e:
+        raise XaiHipError(f"{EXT3_HEADER_PATH}: the third extension ABI cannot be bound from its header: {e}") from e
+
+
 # name -> argument types / return type of every prototype, and the XAI_ABI_VERSION / XAI_ABI_MINOR the header declares
 SIGNATURES, _RESTYPE, (ABI_VERSION, ABI_MINOR) = _read_header()
 # the same for the extension header and its XAI_EXT_VERSION / XAI_EXT_MINOR
 EXT_SIGNATURES, _EXT_RESTYPE, (EXT_VERSION, EXT_MINOR) = _read_ext_header()
 # and for the second extension header and its XAI_EXT2_VERSION / XAI_EXT2_MINOR
 EXT2_SIGNATURES, _EXT2_RESTYPE, (EXT2_VERSION, EXT2_MINOR) = _read_ext2_header()
+# and for the third extension header and its XAI_EXT3_VERSION / XAI_EXT3_MINOR
+EXT3_SIGNATURES, _EXT3_RESTYPE, (EXT3_VERSION, EXT3_MINOR) = _read_ext3_header()
 
 
 def load():
@@ -195,6 +210,30 @@ def load_ext2():
         fn.argtypes = argtypes
         fn.restype = _EXT2_RESTYPE[name]
     _ext2 = lib
+    return lib
+
+
+def load_ext3():
+    """Load the third extension library once, as strictly as `load_ext2()`: absent -> XaiHipError, the version pair first, then
+    every prototype of include/xai_hip_ext3.h (AttributeError if the .so is stale).  Never falls back."""
+    global _ext3
+    if _ext3 is not None:
+        return _ext3
+    csrc = os.path.join(os.path.dirname(_HERE), "csrc")
+    if not os.path.exists(EXT3_LIB_PATH):
+        raise XaiHipError(f"{EXT3_LIB_PATH} not found: the third HIP extension library is not built. Run `make -C {csrc}` (needs "
+                          "hipcc, targets gfx950). There is deliberately no CPU fallback.")
+    lib = C.CDLL(EXT3_LIB_PATH)
+    lib.xai_ext3_version.restype = lib.xai_ext3_version_minor.restype = C.c_int
+    major, minor = lib.xai_ext3_version(), lib.xai_ext3_version_minor()
+    if major != EXT3_VERSION or minor < EXT3_MINOR:
+        raise XaiHipError(f"{EXT3_LIB_PATH} has ABI {major}.{minor}, this package needs {EXT3_VERSION}.{EXT3_MINOR} or a later minor "
+                          f"(include/xai_hip_ext3.h); rebuild with `make -C {csrc}`")
+    for name, argtypes in EXT3_SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError if the .so is stale
+        fn.argtypes = argtypes
+        fn.restype = _EXT3_RESTYPE[name]
+    _ext3 = lib
     return lib
 
 

@@ -1274,3 +1274,42 @@ def hog(img, cell=(16, 16)):
     out = torch.empty((n, (H // ch - 2) * (W // cw - 2) * 81), dtype=F32, device=img.device)
     _call_ext2("xai_hog_f32", img.device, _ptr(img), n, H, W, ch, cw, _ptr(out), _ptr(ws), nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------ segmentation evaluation (K44-K45; libxai_ext3.so)
+def _call_ext3(name, dev, *args):
+    """`_call` for an entry of the third extension library (include/xai_hip_ext3.h); the error texts are xai_strerror's."""
+    lib = _lib.load_ext3()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+
+
+def seg_normalize(x, out=None):
+    """K44: x (n, ...) float32 -> (out, thr, stats): every map min-max normalised in fp32 (evaluateImageNetSeg.py:215-217; Inf is not
+    replaced, a constant map becomes NaN), thr (n,) float32 the mean of each normalised map in the header's stated fp64 tree, stats
+    (n, 2) float32 the (min, max) used.  out may be x."""
+    _need(x, F32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"seg_normalize: x must be (n, ...) with at least one element per map, got {tuple(x.shape)}")
+    out = _out(out, "out", x.shape, x)
+    n = x.shape[0]
+    thr = torch.empty(n, dtype=F32, device=x.device)
+    stats = torch.empty((n, 2), dtype=F32, device=x.device)
+    _call_ext3("xai_seg_normalize_f32", x.device, _ptr(x), n, x[0].numel(), _ptr(out), _ptr(thr), _ptr(stats))
+    return out.view(x.shape), thr, stats
+
+
+def seg_counts(res, labels, thr):
+    """K45: res (n, H, W) float32, labels (n, H, W) int32, thr (n, T) float32 with 1 <= T <= 16 -> (counts, other): counts int32
+    (n, T, H, 2, 3) = pixels of a row by label (0 / 1) and state (<= thr, > thr, neither), other int32 (n,) = pixels whose label is
+    neither 0 nor 1."""
+    n, H, W = _maps(res, "res")
+    _shaped_like(labels, res, "labels", "res", dtype=I32)
+    _need(thr, F32, "thr")
+    if thr.dim() != 2 or thr.shape[0] != n or thr.shape[1] == 0:
+        raise ValueError(f"seg_counts: thr must be ({n}, T) with T >= 1, got {tuple(thr.shape)}")
+    T = thr.shape[1]
+    counts = torch.empty((n, T, H, 2, 3), dtype=I32, device=res.device)
+    other = torch.empty(n, dtype=I32, device=res.device)
+    _call_ext3("xai_seg_counts_i32", res.device, _ptr(res), _ptr(labels), _ptr(thr), n, H, W, T, _ptr(counts), _ptr(other))
+    return counts, other

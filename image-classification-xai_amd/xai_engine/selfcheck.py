@@ -371,6 +371,17 @@ def run(device="cuda:0", verbose=True):
     blocks = blocks.clamp(max=0.2)
     blocks = blocks / (blocks.pow(2).sum(2, keepdim=True) + 1e-10).sqrt()
     check("hog", float((K.hog(himg).double() - blocks.reshape(2, 162)).abs().max()), 1e-6)
+    gx = torch.randn(3, 37, 41, device=dev, generator=gen)
+    gnorm, gthr, _ = K.seg_normalize(gx)
+    glo, ghi = gx.amin((1, 2), keepdim=True), gx.amax((1, 2), keepdim=True)
+    gwant = (gx - glo) / (ghi - glo)
+    check("seg_normalize", max(_rel(gnorm, gwant), _rel(gthr, gwant.double().mean((1, 2)))), 1e-6)
+    glab = (torch.rand(3, 37, 41, device=dev, generator=gen) < 0.4).int()
+    gth = torch.stack([gthr, torch.full_like(gthr, 0.7)], 1).contiguous()
+    gcnt, gother = K.seg_counts(gnorm, glab, gth)
+    gstate = (gnorm[:, None] > gth[:, :, None, None]).long()                                           # (3, 2, 37, 41); no NaN here
+    cells = [torch.stack([((glab[:, None] == l) & (gstate == s)).sum(3) for s in (0, 1, 2)], -1) for l in (0, 1)]
+    check("seg_counts", float(not (torch.equal(gcnt.long(), torch.stack(cells, -2)) and int(gother.abs().sum()) == 0)), 0.0)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

@@ -160,18 +160,13 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
     return sal if device_maps else sal.cpu().numpy()
 
 
-def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
-    """(H,W) float32 numpy saliency map of a hooked ViT for the attention-space methods on the accelerated
-    path (reference evaluatePerturbation.py:192-370): patch map (1,p,p) -> bilinear up-sample to the image
-    (torchvision Resize(antialias=True) == plain bilinear when up-sampling) -> abs, the last two fused in
-    xai_bilinear_up_f32.  "attn_ig" (Baselines.IG) is commented out in the reference's table (:276-278) and
-    offered here because it is the config-4 method."""
+def vit_patch_map(input_tensor, target_class, testing_dict):
+    """The (1, p, p) patch-grid map of the attention-space rows of get_VIT_attr, on the device and before any resize; None for a
+    row that has no patch grid (VIT_CX, MDA) or that the table does not know.  Shared with segeval, whose resize takes no abs."""
     from .vit_attr import Baselines
     model = testing_dict["models"][0]
-    img_hw = testing_dict["img_hw"]
-    device = testing_dict["device"]
     attr_function = testing_dict["attr_func"]
-    dev = hip_device(device)
+    dev = hip_device(testing_dict["device"])
     explainer = Baselines(model)
     x = input_tensor.to(dev)
     if attr_function == "attn":
@@ -188,7 +183,37 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
         sal, _ = explainer.bidirectional(x, target_class, device=dev)
     elif attr_function == "attn_ig":
         sal = explainer.IG(x, target_class, device=dev)
-    elif attr_function == "VIT_CX":
+    elif attr_function == "TIS":
+        from .tis import TIS
+        # :236-239 (n_masks is the class default, 1024, in the reference; the key exists for models with fewer channels)
+        sal = TIS(model, n_masks=testing_dict.get("tis_n_masks", 1024), batch_size=64)(x, class_idx=target_class)[None]
+    elif attr_function == "InFlow":
+        # :240-242 passes option='b', which generate_RAVE does not take (a TypeError in the reference too): dropped here
+        sal, _ = explainer.generate_RAVE(x, target_class, device=dev)
+    else:
+        return None
+    return sal.detach().float().contiguous()
+
+
+def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
+    """(H,W) float32 numpy saliency map of a hooked ViT for the attention-space methods on the accelerated
+    path (reference evaluatePerturbation.py:192-370): patch map (1,p,p) -> bilinear up-sample to the image
+    (torchvision Resize(antialias=True) == plain bilinear when up-sampling) -> abs, the last two fused in
+    xai_bilinear_up_f32.  "attn_ig" (Baselines.IG) is commented out in the reference's table (:276-278) and
+    offered here because it is the config-4 method."""
+    from .vit_attr import Baselines
+    model = testing_dict["models"][0]
+    img_hw = testing_dict["img_hw"]
+    device = testing_dict["device"]
+    attr_function = testing_dict["attr_func"]
+    dev = hip_device(device)
+    sal = vit_patch_map(input_tensor, target_class, testing_dict)
+    if sal is not None:
+        # sal is the (1, p, p) patch grid of an img_hw-pixel input, p = img_hw / patch size: no axis shrinks, plain bilinear is the reference's resize
+        return K.bilinear_up(sal, img_hw, img_hw, scale=1.0, take_abs=True)[0].cpu().numpy()
+    explainer = Baselines(model)
+    x = input_tensor.to(dev)
+    if attr_function == "VIT_CX":
         # :231-235: ViT-CX map of the top-1 class (the reference does not pass target_class), min-max normalised, times
         # ones(H,W,3), then |sum over the 3 copies| = 3 * normalised map.  The reference passes gpu_batch=1; the batch only
         # groups the 2N masked forwards, 50 is ViT_CX's own default.
@@ -198,13 +223,6 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
         result = result.reshape(img_hw, img_hw)
         result = (result - result.min()) / (result.max() - result.min())
         return (result * 3.0).abs().numpy()
-    elif attr_function == "TIS":
-        from .tis import TIS
-        # :236-239 (n_masks is the class default, 1024, in the reference; the key exists for models with fewer channels)
-        sal = TIS(model, n_masks=testing_dict.get("tis_n_masks", 1024), batch_size=64)(x, class_idx=target_class)[None]
-    elif attr_function == "InFlow":
-        # :240-242 passes option='b', which generate_RAVE does not take (a TypeError in the reference too): dropped here
-        sal, _ = explainer.generate_RAVE(x, target_class, device=dev)
     elif attr_function == "MDA":
         # :243-263: the growing-kernel blur search, Baselines.bidirectional resized to the image and times ones(3), MDA with
         # num_patches ** 2 segments and max_batch_size 5, the map of its first return value (:181 |sum over channels|).
@@ -222,8 +240,6 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
     else:
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit
-    # sal is the (1, p, p) patch grid of an img_hw-pixel input, p = img_hw / patch size: no axis shrinks, plain bilinear is the reference's resize
-    return K.bilinear_up(sal.detach().float().contiguous(), img_hw, img_hw, scale=1.0, take_abs=True)[0].cpu().numpy()
 
 
 def run_perturbation(input_tensor, attribution, testing_dict, CLIP_test_info=None, blur=None):

@@ -1,7 +1,8 @@
 """ctypes binding of libxai_hip.so (C ABI: include/xai_hip.h) and of the extension libraries libxai_ext.so
 (include/xai_hip_ext.h: the entry points added after xai_hip.h was frozen at ABI 1.11) and libxai_ext2.so
 (include/xai_hip_ext2.h: the ones added after xai_hip_ext.h was frozen too) and libxai_ext3.so (include/xai_hip_ext3.h: the ones
-added after xai_hip_ext2.h was pinned at 1.1).
+added after xai_hip_ext2.h was pinned at 1.1) and libxai_ext4.so (include/xai_hip_ext4.h: the ones added after xai_hip_ext3.h was pinned
+at 1.0).
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers below are read
 from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing
@@ -25,11 +26,15 @@ EXT2_DEFINES = ("XAI_EXT2_VERSION", "XAI_EXT2_MINOR")
 EXT3_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext3.so")
 EXT3_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext3.h")
 EXT3_DEFINES = ("XAI_EXT3_VERSION", "XAI_EXT3_MINOR")
+EXT4_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext4.so")
+EXT4_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext4.h")
+EXT4_DEFINES = ("XAI_EXT4_VERSION", "XAI_EXT4_MINOR")
 
 _lib = None
 _ext = None
 _ext2 = None
 _ext3 = None
+_ext4 = None
 
 
 class XaiHipError(RuntimeError):
@@ -126,6 +131,14 @@ def _read_ext3_header():
         raise XaiHipError(f"{EXT3_HEADER_PATH}: the third extension ABI cannot be bound from its header: {e}") from e
 
 
+def _read_ext4_header():
+    try:
+        with open(EXT4_HEADER_PATH) as f:
+            return parse_header(f.read(), EXT4_DEFINES)
+    except (OSError, XaiHipError) as e:
+        raise XaiHipError(f"{EXT4_HEADER_PATH}: the fourth extension ABI cannot be bound from its header: {e}") from e
+
+
 # name -> argument types / return type of every prototype, and the XAI_ABI_VERSION / XAI_ABI_MINOR the header declares
 SIGNATURES, _RESTYPE, (ABI_VERSION, ABI_MINOR) = _read_header()
 # the same for the extension header and its XAI_EXT_VERSION / XAI_EXT_MINOR
@@ -134,6 +147,8 @@ EXT_SIGNATURES, _EXT_RESTYPE, (EXT_VERSION, EXT_MINOR) = _read_ext_header()
 EXT2_SIGNATURES, _EXT2_RESTYPE, (EXT2_VERSION, EXT2_MINOR) = _read_ext2_header()
 # and for the third extension header and its XAI_EXT3_VERSION / XAI_EXT3_MINOR
 EXT3_SIGNATURES, _EXT3_RESTYPE, (EXT3_VERSION, EXT3_MINOR) = _read_ext3_header()
+# and for the fourth extension header and its XAI_EXT4_VERSION / XAI_EXT4_MINOR
+EXT4_SIGNATURES, _EXT4_RESTYPE, (EXT4_VERSION, EXT4_MINOR) = _read_ext4_header()
 
 
 def load():
@@ -234,6 +249,30 @@ def load_ext3():
         fn.argtypes = argtypes
         fn.restype = _EXT3_RESTYPE[name]
     _ext3 = lib
+    return lib
+
+
+def load_ext4():
+    """Load the fourth extension library once, as strictly as `load_ext3()`: absent -> XaiHipError, the version pair first, then
+    every prototype of include/xai_hip_ext4.h (AttributeError if the .so is stale).  Never falls back."""
+    global _ext4
+    if _ext4 is not None:
+        return _ext4
+    csrc = os.path.join(os.path.dirname(_HERE), "csrc")
+    if not os.path.exists(EXT4_LIB_PATH):
+        raise XaiHipError(f"{EXT4_LIB_PATH} not found: the fourth HIP extension library is not built. Run `make -C {csrc}` (needs "
+                          "hipcc, targets gfx950). There is deliberately no CPU fallback.")
+    lib = C.CDLL(EXT4_LIB_PATH)
+    lib.xai_ext4_version.restype = lib.xai_ext4_version_minor.restype = C.c_int
+    major, minor = lib.xai_ext4_version(), lib.xai_ext4_version_minor()
+    if major != EXT4_VERSION or minor < EXT4_MINOR:
+        raise XaiHipError(f"{EXT4_LIB_PATH} has ABI {major}.{minor}, this package needs {EXT4_VERSION}.{EXT4_MINOR} or a later minor "
+                          f"(include/xai_hip_ext4.h); rebuild with `make -C {csrc}`")
+    for name, argtypes in EXT4_SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError if the .so is stale
+        fn.argtypes = argtypes
+        fn.restype = _EXT4_RESTYPE[name]
+    _ext4 = lib
     return lib
 
 

@@ -15,7 +15,7 @@ import torch
 
 from . import dist as xd
 from . import harness
-from .sweep import CNN_ATTR_FUNCS, VIT_ATTR_FUNCS, VIT_TRANS_ATTR_FUNCS
+from .sweep import CNN_ATTR_FUNCS, VIT_ATTR_FUNCS, VIT_LRP_ATTR_FUNCS, VIT_TRANS_ATTR_FUNCS
 from .zoo import resnet50, resnet101, resnet152, resnext101_64x4d, vit_base_patch16_224, vit_base_patch32_224
 
 MODELS = {
@@ -35,7 +35,7 @@ def build_parser():
     p.add_argument("--image_count", type=int, default=1000, help="How many images to test with.")
     p.add_argument("--model", type=str, default="R50", help="Classifier to use: " + ", ".join(MODELS))
     p.add_argument("--attr_func", type=str, default="ig", help="attr to use: R50/R101/R152/RNXT: {" + ", ".join(CNN_ATTR_FUNCS) + "}, VIT16/VIT32: {" +
-                   ", ".join(VIT_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS) + "}")
+                   ", ".join(VIT_ATTR_FUNCS + VIT_LRP_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS) + "}")
     p.add_argument("--cuda_num", type=int, default=0, help="GPU to use when not launched by torchrun.")
     p.add_argument("--dataset_path", type=str, default="../../../ImageNet", help="The path to your dataset input")
     p.add_argument("--class_map", type=str, default=None, help="correctly_classified_<MODEL>.txt (optional)")
@@ -64,7 +64,7 @@ def main(argv=None):
     args, _ = build_parser().parse_known_args(argv)
     if args.model not in MODELS:
         raise SystemExit(f"unknown --model {args.model}; choose from {sorted(MODELS)}")
-    if args.attr_func not in (VIT_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS if "VIT" in args.model else CNN_ATTR_FUNCS):
+    if args.attr_func not in (VIT_ATTR_FUNCS + VIT_LRP_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS if "VIT" in args.model else CNN_ATTR_FUNCS):
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit(1)
     torch.backends.cudnn.deterministic = not args.nondeterministic

@@ -14,7 +14,7 @@ import torch
 
 from . import sanity
 from .evaluate_perturbation import MODELS
-from .sweep import CNN_ATTR_FUNCS, VIT_ATTR_FUNCS, VIT_TRANS_ATTR_FUNCS
+from .sweep import CNN_ATTR_FUNCS, VIT_ATTR_FUNCS, VIT_LRP_ATTR_FUNCS, VIT_TRANS_ATTR_FUNCS
 
 
 def build_parser():
@@ -22,7 +22,7 @@ def build_parser():
     p.add_argument("--image_count", type=int, default=1000, help="How many images to test with.")
     p.add_argument("--model", type=str, default="R101", help="Classifier to use: " + ", ".join(MODELS))
     p.add_argument("--attr_func", type=str, default="ig", help="attr to use: R50/R101/R152/RNXT: {" + ", ".join(CNN_ATTR_FUNCS) +
-                   "}, VIT16/VIT32: {" + ", ".join(VIT_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS) + "}")
+                   "}, VIT16/VIT32: {" + ", ".join(VIT_ATTR_FUNCS + VIT_LRP_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS) + "}")
     p.add_argument("--cuda_num", type=int, default=0, help="The number of the GPU you want to use.")
     p.add_argument("--dataset_path", type=str, default="../../../ImageNet", help="The path to your dataset input")
     p.add_argument("--class_map", type=str, default=None, help="correctly_classified_<MODEL>.txt (optional)")
@@ -46,7 +46,7 @@ def main(argv=None):
     if args.model not in MODELS:
         raise SystemExit(f"unknown --model {args.model}; choose from {sorted(MODELS)}")
     is_vit = "VIT" in args.model
-    if args.attr_func not in (VIT_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS if is_vit else CNN_ATTR_FUNCS):
+    if args.attr_func not in (VIT_ATTR_FUNCS + VIT_LRP_ATTR_FUNCS + VIT_TRANS_ATTR_FUNCS if is_vit else CNN_ATTR_FUNCS):
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit(1)
     device = torch.device("cuda", args.cuda_num)

@@ -1313,3 +1313,127 @@ def seg_counts(res, labels, thr):
     other = torch.empty(n, dtype=I32, device=res.device)
     _call_ext3("xai_seg_counts_i32", res.device, _ptr(res), _ptr(labels), _ptr(thr), n, H, W, T, _ptr(counts), _ptr(other))
     return counts, other
+
+
+# ------------------------------------------------------------------------------ Transformer Attribution (K46-K52; libxai_ext4.so)
+def _call_ext4(name, dev, *args):
+    """`_call` for an entry of the fourth extension library (include/xai_hip_ext4.h); the error texts are xai_strerror's."""
+    lib = _lib.load_ext4()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+
+
+def _images(t, name):
+    """(B, elements per image) of an operand whose leading axis counts images"""
+    _need(t, F32, name)
+    if t.dim() < 1 or t.numel() == 0:
+        raise ValueError(f"{name} must be (B, ...) with at least one element per image, got {tuple(t.shape)}")
+    return t.shape[0], t[0].numel()
+
+
+def lrp_split(x, pos=None, neg=None):
+    """K46: x (B, ...) -> (clamp(x, min=0), clamp(x, max=0))"""
+    B, n = _images(x, "x")
+    pos, neg = _out(pos, "pos", x.shape, x), _out(neg, "neg", x.shape, x)
+    _call_ext4("xai_lrp_split_f32", x.device, _ptr(x), B, n, _ptr(pos), _ptr(neg))
+    return pos, neg
+
+
+def lrp_ratio(r, z1, z2=None, out=None):
+    """K47: safe_divide(r, z1 + z2) (layers_ours.py:10-13), or safe_divide(r, z1) without z2; out may be one of the operands"""
+    B, n = _images(r, "r")
+    _shaped_like(z1, r, "z1", "r"); _shaped_like(z2, r, "z2", "r")
+    if z1 is None:
+        raise TypeError("z1: expected a torch.Tensor, got NoneType")
+    out = _out(out, "out", r.shape, r)
+    _call_ext4("xai_lrp_ratio_f32", r.device, _ptr(r), _ptr(z1), _ptr(z2), B, n, _ptr(out))
+    return out
+
+
+def lrp_gather(x, g1, g2, out=None):
+    """K48: clamp(x, min=0) * g1 + clamp(x, max=0) * g2; out may be g1 or g2"""
+    B, n = _images(x, "x")
+    for t, name in ((g1, "g1"), (g2, "g2")):
+        _need(t, F32, name)
+        _shaped_like(t, x, name, "x")
+    out = _out(out, "out", x.shape, x)
+    _call_ext4("xai_lrp_gather_f32", x.device, _ptr(x), _ptr(g1), _ptr(g2), B, n, _ptr(out))
+    return out
+
+
+def lrp_half_product(x, c, out=None, slot=None):
+    """K49: x * c / 2.  Plain (slot None): any shape (B, ...), out like x.  slot 0 / 1 / 2: x, c (B, h, N, d) and `out` the
+    (B, N, 3 * h * d) cam_qkv buffer, of which only the slot's third is written."""
+    _need(x, F32, "x"); _need(c, F32, "c")
+    _shaped_like(c, x, "c", "x")
+    if slot is None:
+        B, n = _images(x, "x")
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"lrp_half_product: {n} elements per image are more than K49 takes")
+        out = _out(out, "out", x.shape, x)
+        _call_ext4("xai_lrp_half_product_f32", x.device, _ptr(x), _ptr(c), B, 1, n, 1, 1, 0, _ptr(out))
+        return out
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"lrp_half_product: a slot needs x of (B, h, N, d), got {tuple(x.shape)}")
+    if slot not in (0, 1, 2):
+        raise ValueError("slot must be 0, 1 or 2")
+    B, h, N, d = x.shape
+    if out is None:
+        raise TypeError("lrp_half_product: a slot needs the cam_qkv buffer as out")
+    _out(out, "out", (B, N, 3 * h * d), x, wrong=f"out must be the ({B}, {N}, {3 * h * d}) cam_qkv buffer")
+    _call_ext4("xai_lrp_half_product_f32", x.device, _ptr(x), _ptr(c), B, h, N, d, 3, int(slot), _ptr(out))
+    return out
+
+
+def lrp_add_chunk():
+    """the elements of an image one workgroup of K50 sums"""
+    return _lib.load_ext4().xai_lrp_add_chunk()
+
+
+def lrp_add(x0, x1, r, a=None, b=None, ws=None):
+    """K50: Add.relprop (layers_ours.py:106-125) per image, x0, x1, r (B, ...) -> (a, b); the sums are fp64 in the header's tree.
+    ws: a uint8 scratch of at least xai_lrp_add_workspace_bytes(B, n) bytes (allocated when None)."""
+    B, n = _images(r, "r")
+    for t, name in ((x0, "x0"), (x1, "x1")):
+        _need(t, F32, name)
+        _shaped_like(t, r, name, "r")
+    a, b = _out(a, "a", r.shape, r), _out(b, "b", r.shape, r)
+    nbytes = _lib.load_ext4().xai_lrp_add_workspace_bytes(B, n)
+    if nbytes == 0:
+        raise ValueError(f"lrp_add: {B} images of {n} elements are more than K50 takes")
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=U8, device=r.device)
+    _need(ws, U8, "ws")
+    _call_ext4("xai_lrp_add_parts_f32", r.device, _ptr(x0), _ptr(x1), _ptr(r), B, n, _ptr(a), _ptr(b), _ptr(ws), ws.numel())
+    _call_ext4("xai_lrp_add_scale_f32", r.device, _ptr(a), _ptr(b), B, n, _ptr(ws), ws.numel())
+    return a, b
+
+
+def lrp_clone(x, r1, r2, out=None):
+    """K51: x * (safe_divide(r1, x) + safe_divide(r2, x)); out may be r1 or r2"""
+    B, n = _images(x, "x")
+    for t, name in ((r1, "r1"), (r2, "r2")):
+        _need(t, F32, name)
+        _shaped_like(t, x, name, "x")
+    out = _out(out, "out", x.shape, x)
+    _call_ext4("xai_lrp_clone_f32", x.device, _ptr(x), _ptr(r1), _ptr(r2), B, n, _ptr(out))
+    return out
+
+
+LRP_MATRICES, LRP_ROLLOUT, LRP_CLS_ROW = 0, 1, 2
+
+
+def lrp_attn_matrices(cam, grad=None, mode=LRP_ROLLOUT):
+    """K52: cam (and grad, or None) (L, B, h, S, S) -> the head mean of clamp(grad * cam, min=0) of every block, heads added in
+    ascending order: LRP_MATRICES (B, L, S, S); LRP_ROLLOUT the same plus the identity, every row divided by its sum (what K19,
+    `rollout_row`, chains); LRP_CLS_ROW (B, L, S), row 0 only."""
+    _need(cam, F32, "cam")
+    if cam.dim() != 5 or cam.shape[-1] != cam.shape[-2] or cam.numel() == 0:
+        raise ValueError(f"cam must be (L, B, h, S, S), got {tuple(cam.shape)}")
+    _shaped_like(grad, cam, "grad", "cam")
+    if mode not in (LRP_MATRICES, LRP_ROLLOUT, LRP_CLS_ROW):
+        raise ValueError("mode must be LRP_MATRICES, LRP_ROLLOUT or LRP_CLS_ROW")
+    L, B, h, S, _ = cam.shape
+    out = torch.empty((B, L, S) if mode == LRP_CLS_ROW else (B, L, S, S), dtype=F32, device=cam.device)
+    _call_ext4("xai_lrp_attn_matrices_f32", cam.device, _ptr(cam), _ptr(grad), L, B, h, S, int(mode), _ptr(out))
+    return out

@@ -382,6 +382,38 @@ def run(device="cuda:0", verbose=True):
     gstate = (gnorm[:, None] > gth[:, :, None, None]).long()                                           # (3, 2, 37, 41); no NaN here
     cells = [torch.stack([((glab[:, None] == l) & (gstate == s)).sum(3) for s in (0, 1, 2)], -1) for l in (0, 1)]
     check("seg_counts", float(not (torch.equal(gcnt.long(), torch.stack(cells, -2)) and int(gother.abs().sum()) == 0)), 0.0)
+    # Transformer Attribution (K46-K52, libxai_ext4.so) against the torch expressions of layers_ours.py on the device
+    def sdiv(a, b):
+        den = b.clamp(min=1e-9) + b.clamp(max=1e-9)
+        den = den + den.eq(0).to(den.dtype) * 1e-9
+        return a / den * b.ne(0).to(b.dtype)
+    lx, lr, lg = rnd(2, 17, 48), rnd(2, 17, 48), rnd(2, 17, 48)
+    lx[0, 0, :4] = 0.0
+    lpos, lneg = K.lrp_split(lx)
+    check("lrp_split", float(not (torch.equal(lpos, lx.clamp(min=0)) and torch.equal(lneg, lx.clamp(max=0)))), 0.0)
+    check("lrp_ratio", _rel(K.lrp_ratio(lr, lx, lg), sdiv(lr, lx + lg)), 1e-6)
+    check("lrp_gather", _rel(K.lrp_gather(lx, lr, lg), lx.clamp(min=0) * lr + lx.clamp(max=0) * lg), 1e-6)
+    check("lrp_clone", _rel(K.lrp_clone(lx, lr, lg), lx * (sdiv(lr, lx) + sdiv(lg, lx))), 1e-6)
+    lq, lc = rnd(2, 4, 17, 12), rnd(2, 4, 17, 12)
+    lqkv = torch.zeros(2, 17, 3 * 48, device=dev)
+    K.lrp_half_product(lq, lc, out=lqkv, slot=1)
+    lwant = torch.zeros(2, 17, 3, 4, 12, device=dev)
+    lwant[:, :, 1] = (lq * lc / 2).permute(0, 2, 1, 3)
+    check("lrp_half_product", max(_rel(K.lrp_half_product(lq, lc), lq * lc / 2), _rel(lqkv, lwant.reshape(2, 17, 144))), 1e-6)
+    ax, ag, ar = lx.abs() + 0.5, lg.abs() + 0.5, lr.abs()              # no sum that cancels: K50's arithmetic, not the method's conditioning
+    la, lb = K.lrp_add(ax, ag, ar)
+    ls = sdiv(ar.double(), (ax + ag).double())
+    wa, wb = ax.double() * ls, ag.double() * ls
+    sa, sb, sr = wa.sum((1, 2), keepdim=True), wb.sum((1, 2), keepdim=True), ar.double().sum((1, 2), keepdim=True)
+    wa = wa * sdiv(sdiv(sa.abs(), sa.abs() + sb.abs()) * sr, sa)
+    wb = wb * sdiv(sdiv(sb.abs(), sa.abs() + sb.abs()) * sr, sb)
+    check("lrp_add", max(_rel(la, wa), _rel(lb, wb)), 1e-6)
+    lcam, lgrad = rnd(3, 2, 4, 17, 17), rnd(3, 2, 4, 17, 17)
+    lm = (lgrad * lcam).clamp(min=0).double().mean(2).transpose(0, 1)                                   # (2, 3, 17, 17)
+    laug = lm + torch.eye(17, device=dev, dtype=torch.float64)
+    laug = laug / laug.sum(-1, keepdim=True)
+    check("lrp_attn_matrices", max(_rel(K.lrp_attn_matrices(lcam, lgrad, K.LRP_MATRICES), lm), _rel(K.lrp_attn_matrices(lcam, lgrad, K.LRP_ROLLOUT), laug),
+                                   _rel(K.lrp_attn_matrices(lcam, None, K.LRP_CLS_ROW), lcam.clamp(min=0).double().mean(2).transpose(0, 1)[:, :, 0])), 1e-6)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

@@ -38,6 +38,7 @@ CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "lime"
 TRANS_ATTR_FUNCS = ("agi", "lime")   # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 VIT_TRANS_ATTR_FUNCS = ("MDA",)      # ViT rows that need `trans_img` (and, without skimage, testing_dict["mda_segments"])
+VIT_LRP_ATTR_FUNCS = ("t_attr",)     # ViT rows of the relevance pass (xai_engine/lrp.py); the segmentation evaluation does not offer them
 
 
 def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
@@ -190,6 +191,11 @@ def vit_patch_map(input_tensor, target_class, testing_dict):
     elif attr_function == "InFlow":
         # :240-242 passes option='b', which generate_RAVE does not take (a TypeError in the reference too): dropped here
         sal, _ = explainer.generate_RAVE(x, target_class, device=dev)
+    elif attr_function == "t_attr":
+        # :228-230: LRP(models[1]).generate_LRP(x, target, method="transformer_attribution", start_layer=0); the reference's
+        # models[1] is its relprop twin of models[0] with the same weights, here the pass runs on models[0] itself
+        from .lrp import LRP
+        sal = LRP(model, graphs=True).generate_LRP(x, target_class, method="transformer_attribution", start_layer=0, device=dev)
     else:
         return None
     return sal.detach().float().contiguous()

@@ -55,6 +55,9 @@ def build_parser():
                    "(:612-615).  Default: plain sums, always ten rows")
     p.add_argument("--streams", type=int, default=3, help="HIP streams consecutive images are queued on (fused sweep; results are bit-identical "
                    "to 1 with the default deterministic solvers)")
+    p.add_argument("--lime_quickshift", choices=("skimage", "device"), default="skimage", help="--attr_func lime: who computes the quickshift "
+                   "superpixels.  skimage (default): skimage.segmentation.quickshift on the host, the reference's dependency.  device: the "
+                   "same algorithm (scikit-image 0.18.3's, fp64) on the HIP kernels K53-K55; needs no scikit-image")
     p.add_argument("--out_dir", type=str, default="pert_test_results")
     p.add_argument("--checkpoint", type=str, default=None, help="path prefix for per-rank resume files (the reference loses a crashed run)")
     return p
@@ -86,7 +89,7 @@ def main(argv=None):
     testing_dict = {"models": [model, model], "imagenet_dataset": args.dataset_path, "normalize": norm, "img_hw": 224,
                     "batch_size": batch_size, "attr_func": args.attr_func, "model_name": args.model,
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
-                    "weights_path": args.weights or "", "num_patches": num_patches}
+                    "weights_path": args.weights or "", "num_patches": num_patches, "lime_quickshift": args.lime_quickshift}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, fused=not args.eight_runs, out_dir=args.out_dir,
                                                      checkpoint=args.checkpoint, streams=args.streams, reference_counter=args.reference_counter)
     if rank == 0:

@@ -1437,3 +1437,64 @@ def lrp_attn_matrices(cam, grad=None, mode=LRP_ROLLOUT):
     out = torch.empty((B, L, S) if mode == LRP_CLS_ROW else (B, L, S, S), dtype=F32, device=cam.device)
     _call_ext4("xai_lrp_attn_matrices_f32", cam.device, _ptr(cam), _ptr(grad), L, B, h, S, int(mode), _ptr(out))
     return out
+
+
+# ------------------------------------------------------------------------------ quickshift superpixels (K53-K55; libxai_ext5.so)
+def _call_ext5(name, dev, *args):
+    """`_call` for an entry of the fifth extension library (include/xai_hip_ext5.h); the error texts are xai_strerror's."""
+    lib = _lib.load_ext5()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+
+
+def quickshift_lds_bytes(C, kernel_size):
+    """The LDS bytes a workgroup of K53 / K54 stages; the entries refuse more than 65536 (include/xai_hip_ext5.h, THE CAP)"""
+    return _lib.load_ext5().xai_quickshift_lds_bytes(int(C), float(kernel_size))
+
+
+def _quickshift_shape(features, name="features"):
+    _need(features, F64, name)
+    if features.dim() != 4 or features.numel() == 0:
+        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(features.shape)}")
+    return tuple(features.shape)
+
+
+def quickshift_density(features, noise, kernel_size, out=None):
+    """K53: features (B, H, W, C) fp64, noise (B, H, W) fp64 -> the densities (B, H, W) fp64, the tie noise added"""
+    B, H, W, C = _quickshift_shape(features)
+    _need(noise, F64, "noise")
+    if tuple(noise.shape) != (B, H, W):
+        raise ValueError(f"noise must be {(B, H, W)}, got {tuple(noise.shape)}")
+    out = _out(out, "out", (B, H, W), features, dtype=F64)
+    _call_ext5("xai_quickshift_density_f64", features.device, _ptr(features), _ptr(noise), B, H, W, C, float(kernel_size), _ptr(out))
+    return out
+
+
+def quickshift_parent(features, dens, kernel_size, max_dist, want_tree=False):
+    """K54: -> (parent (B, H, W) int32 with the max_dist cut, closest (B, H, W) fp64, dist = sqrt(closest), tree): tree is the
+    parent before the cut (skimage's return_tree) with `want_tree`, else None"""
+    B, H, W, C = _quickshift_shape(features)
+    _need(dens, F64, "dens")
+    if tuple(dens.shape) != (B, H, W):
+        raise ValueError(f"dens must be {(B, H, W)}, got {tuple(dens.shape)}")
+    parent = torch.empty((B, H, W), dtype=I32, device=features.device)
+    tree = torch.empty_like(parent) if want_tree else None
+    closest = torch.empty((B, H, W), dtype=F64, device=features.device)
+    dist = torch.empty_like(closest)
+    _call_ext5("xai_quickshift_parent_f64", features.device, _ptr(features), _ptr(dens), B, H, W, C, float(kernel_size), float(max_dist),
+               _ptr(parent), _ptr(tree), _ptr(closest), _ptr(dist))
+    return parent, closest, dist, tree
+
+
+def quickshift_labels(parent, labels=None):
+    """K55: parent (B, H, W) int32 -> (labels (B, H, W) int32 = np.unique(roots, return_inverse=True)[1] per image, D (B,) int32)"""
+    _need(parent, I32, "parent")
+    if parent.dim() != 3 or parent.numel() == 0:
+        raise ValueError(f"parent must be (B, H, W) with at least one element, got {tuple(parent.shape)}")
+    B, H, W = parent.shape
+    labels = _out(labels, "labels", (B, H, W), parent, dtype=I32)
+    D = torch.empty((B,), dtype=I32, device=parent.device)
+    nbytes = _lib.load_ext5().xai_quickshift_workspace_bytes(B, H, W)
+    ws = torch.empty(max(nbytes, 4), dtype=U8, device=parent.device)
+    _call_ext5("xai_quickshift_labels_i32", parent.device, _ptr(parent), B, H, W, _ptr(labels), _ptr(D), _ptr(ws), ws.numel())
+    return labels, D

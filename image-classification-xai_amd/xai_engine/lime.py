@@ -14,7 +14,9 @@ superpixels.  Nothing is read back between the passes, K32 and K33.  Every disti
 `lime_batch` is the multi-image entry; `LimeImageExplainer` / `ImageExplanation` keep the reference's call shape
 (util/attribution_methods/lime/lime_image.py serves them), `get_lime_attr` / `batch_predict` / `make_tensor` are limeAttr.py's.
 The segmentation (quickshift, skimage, on the host) stays the reference's dependency: `quickshift_segments` calls it when
-skimage is installed, callers that pass `segments=` / `segmentation_fn=` need none.
+skimage is installed, callers that pass `segments=` / `segmentation_fn=` need none.  `device_quickshift_segments` is the opt-in
+segmenter that needs no skimage: the same quickshift on the kernels K53 - K55 (xai_engine/quickshift.py), accepted by identity by
+`lime_batch(segments=...)` and `explain_instance(segmentation_fn=...)`.
 
 Parity: sklearn's weighted Ridge and cosine distance are pinned through tests/golden/lime.npz (the reference's own run);
 skimage's quickshift is UNPINNED (unpinned third-party boundaries).
@@ -187,8 +189,10 @@ def lime_batch(x01, model, segments, num_samples=1000, top_labels=5, labels=None
 
     x01: (B, C, H, W) on a HIP device, the un-normalised image the reference perturbs (limeAttr.py feeds it to the classifier
     as it is).  segments: (B, H, W) or (H, W) integer superpixel ids 0 .. D_b - 1, array or tensor, or a callable
-    `(image_hwc, random_seed) -> (H, W)` run on the host per image.  data: one (num_samples, D_b) 0/1 matrix per image (a single
-    array for B = 1); None: drawn from `random_state` (None, an int or a RandomState) with the reference's calls in the
+    `(image_hwc, random_seed) -> (H, W)` run on the host per image, or `device_quickshift_segments` itself (taken by identity, as
+    `explain_instance` takes `batch_predict`): quickshift on K53 - K55 with the drawn seed; the labels never leave the device, only
+    D_b is read back (the data matrix is drawn from it), and a host copy is made only for `hide_color=None`.
+    data: one (num_samples, D_b) 0/1 matrix per image (a single array for B = 1); None: drawn from `random_state` (None, an int or a RandomState) with the reference's calls in the
     reference's order, per image the seed draw of lime_image.py:174-175 and then the matrix of :249-252.
     top_labels: explain the L most probable classes of every image (the unperturbed image's softmax, topk on the device); 0 / None:
     the classes `labels`, shared by the images.  hide_color: a number, one per channel, a (B, C, H, W) replacement image, or None
@@ -212,6 +216,7 @@ def lime_batch(x01, model, segments, num_samples=1000, top_labels=5, labels=None
     if data is not None and len(data) != B:
         raise ValueError(f"lime_batch: {len(data)} data matrices for {B} images")
 
+    device_seg = segments is device_quickshift_segments
     seg_dims = 0 if callable(segments) else (segments.dim() if torch.is_tensor(segments) else np.ndim(segments))
     if seg_dims == 3 and len(segments) != B:
         raise ValueError(f"lime_batch: segments of {len(segments)} images for {B} images")
@@ -219,15 +224,15 @@ def lime_batch(x01, model, segments, num_samples=1000, top_labels=5, labels=None
     segs, Ds, mats = [], [], []
     for b in range(B):
         seed = draw_seed(rs) if rs is not None else None
-        if callable(segments):
-            if host_x is None:
-                host_x = x.cpu().numpy()
-            s = segments(host_x[b].transpose(1, 2, 0), seed)
+        if callable(segments) and host_x is None:
+            host_x = x.cpu().numpy()
+        if device_seg:
+            s, D = _device_segments(host_x[b].transpose(1, 2, 0), seed, dev)      # ids 0 .. D - 1 by construction (K55)
         else:
-            s = segments if seg_dims == 2 else segments[b]
-        s, D = check_segments(s, "lime_batch")
-        if s.shape != (H, W):
-            raise ValueError(f"lime_batch: segments of image {b} are {s.shape}, the image is {(H, W)}")
+            s = segments(host_x[b].transpose(1, 2, 0), seed) if callable(segments) else segments if seg_dims == 2 else segments[b]
+            s, D = check_segments(s, "lime_batch")
+        if tuple(s.shape) != (H, W):
+            raise ValueError(f"lime_batch: segments of image {b} are {tuple(s.shape)}, the image is {(H, W)}")
         m = draw_data(rs, N, D) if rs is not None else np.asarray(data[b])
         if m.shape != (N, D):
             raise ValueError(f"lime_batch: data of image {b} must be {(N, D)}, got {m.shape}")
@@ -235,7 +240,11 @@ def lime_batch(x01, model, segments, num_samples=1000, top_labels=5, labels=None
     words = K.lime_words(max(Ds))
     d_stride = words * 64
     rows = torch.from_numpy(np.concatenate([pack_rows(m, words) for m in mats]).view(np.int64)).to(dev)
-    seg_t = torch.from_numpy(np.stack(segs)).to(dev)
+    if device_seg:
+        seg_t = torch.stack(segs)
+        segs = [t.cpu().numpy() for t in segs] if hide_color is None else None     # the mean colours are the host's (:186-192)
+    else:
+        seg_t = torch.from_numpy(np.stack(segs)).to(dev)
     D_t = torch.tensor(Ds, dtype=torch.int32).to(dev)
     hide, fudged = _hide_args(hide_color, x, segs)
 
@@ -307,6 +316,27 @@ def quickshift_segments(image, random_seed):
         raise ImportError("LIME's own segmentation needs scikit-image (skimage.segmentation.quickshift), which is not installed; "
                           "without it only callers that pass segments= / segmentation_fn= work") from e
     return quickshift(np.asarray(image), kernel_size=4, max_dist=200, ratio=0.2, random_seed=random_seed)
+
+
+QUICKSHIFT_ARGS = dict(kernel_size=4, max_dist=200, ratio=0.2)      # lime_image.py:177-180
+
+
+def _device_segments(image, random_seed, dev):
+    """LIME's quickshift of one (H, W, 3) host image on the kernels K53 - K55 -> ((H, W) int32 labels on `dev`, D).  The Lab
+    features and the tie noise are made on the host in fp64 (xai_engine/quickshift.py) and uploaded; only D is read back."""
+    from . import quickshift as Q
+    f = Q.quickshift_features(image, QUICKSHIFT_ARGS["ratio"])
+    noise = Q.tie_noise(random_seed, f.shape[0], f.shape[1])
+    labels, D = Q.quickshift_batch(torch.from_numpy(f)[None].to(dev), torch.from_numpy(noise)[None].to(dev),
+                                   QUICKSHIFT_ARGS["kernel_size"], QUICKSHIFT_ARGS["max_dist"])
+    return labels[0], int(read_back(D)[0])
+
+
+def device_quickshift_segments(image, random_seed):
+    """`quickshift_segments` without skimage: the same algorithm (scikit-image 0.18.3's, fp64) with the same arguments on the current
+    HIP device (K53 - K55).  image: (H, W, 3) -> (H, W) int64 ids on the host.  `lime_batch` and `explain_instance` take this
+    function by identity; `lime_batch` then keeps the labels on the device."""
+    return _device_segments(image, random_seed, hip_device("cuda"))[0].cpu().numpy().astype(np.int64)
 
 
 def make_tensor(img):
@@ -382,7 +412,8 @@ class LimeImageExplainer(object):
                          num_samples=1000, batch_size=10, segmentation_fn=None, distance_metric='cosine', model_regressor=None,
                          random_seed=None):
         """-> ImageExplanation.  image: (H, W, 3) array (a 2-d one is repeated to three channels); classifier_fn: this module's
-        `batch_predict`; segmentation_fn: a host callable image -> (H, W) ids (None: quickshift, needs skimage); batch_size: rows per
+        `batch_predict`; segmentation_fn: a host callable image -> (H, W) ids (None: quickshift, needs skimage;
+        `device_quickshift_segments`, taken by identity: quickshift on the device with the drawn seed); batch_size: rows per
         classifier pass, the reference's default of 10 being what this engine replaces (-> PASS_SIZE)."""
         name = "LimeImageExplainer.explain_instance"
         if classifier_fn is not batch_predict:
@@ -401,6 +432,8 @@ class LimeImageExplainer(object):
             random_seed = draw_seed(self.random_state)
         if segmentation_fn is None:
             segments = quickshift_segments(image, random_seed)
+        elif segmentation_fn is device_quickshift_segments:
+            segments = _device_segments(image, random_seed, hip_device(device))[0].cpu().numpy().astype(np.int64)
         else:
             segments = segmentation_fn(image)
         seg32, D = check_segments(segments, name)

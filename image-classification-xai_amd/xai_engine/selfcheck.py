@@ -5,6 +5,7 @@ expression evaluated ON THE SAME DEVICE (this is a smoke test for a deployment, 
 that lives in tests/ and uses the CPU oracle).  Exit code 0 when everything agrees.
 """
 import argparse
+import math
 import sys
 
 import torch
@@ -414,6 +415,37 @@ def run(device="cuda:0", verbose=True):
     laug = laug / laug.sum(-1, keepdim=True)
     check("lrp_attn_matrices", max(_rel(K.lrp_attn_matrices(lcam, lgrad, K.LRP_MATRICES), lm), _rel(K.lrp_attn_matrices(lcam, lgrad, K.LRP_ROLLOUT), laug),
                                    _rel(K.lrp_attn_matrices(lcam, None, K.LRP_CLS_ROW), lcam.clamp(min=0).double().mean(2).transpose(0, 1)[:, :, 0])), 1e-6)
+    # quickshift (K53-K55, libxai_ext5.so) against the window loop over offsets in scan order, in torch fp64 on the device
+    qH, qW, qks, qmd = 19, 23, 1.0, 4.0
+    qkw = math.ceil(3 * qks)
+    qf = torch.rand(1, qH, qW, 3, device=dev, generator=gen, dtype=torch.float64) * 3
+    qnoise = torch.randn(1, qH, qW, device=dev, generator=gen, dtype=torch.float64) * 1e-5
+    qdens = K.quickshift_density(qf, qnoise, qks)
+    qparent, qclosest, qdist, qtree = K.quickshift_parent(qf, qdens, qks, qmd, want_tree=True)
+    qidx = torch.arange(qH * qW, device=dev).view(qH, qW)
+    wsum = torch.zeros(qH, qW, device=dev, dtype=torch.float64)
+    wclosest = torch.full((qH, qW), torch.finfo(torch.float64).max, device=dev, dtype=torch.float64)
+    wtree = qidx.clone()
+    for dr in range(-qkw, qkw + 1):
+        for dc in range(-qkw, qkw + 1):
+            own = (slice(max(0, -dr), min(qH, qH - dr)), slice(max(0, -dc), min(qW, qW - dc)))
+            oth = (slice(max(0, dr), min(qH, qH + dr)), slice(max(0, dc), min(qW, qW + dc)))
+            t = qf[0][own] - qf[0][oth]
+            d = t[..., 0] * t[..., 0] + t[..., 1] * t[..., 1] + t[..., 2] * t[..., 2] + float(dr * dr) + float(dc * dc)   # the header's order
+            wsum[own] += torch.exp(d * (-0.5 / (qks * qks)))
+            better = (qdens[0][oth] > qdens[0][own]) & (d < wclosest[own])
+            wclosest[own] = torch.where(better, d, wclosest[own])
+            wtree[own] = torch.where(better, qidx[oth], wtree[own])
+    check("quickshift_density", _rel(qdens[0], wsum + qnoise[0]), 1e-12)
+    wparent = torch.where(wclosest.sqrt() > qmd, qidx, wtree)
+    check("quickshift_parent", float(not (torch.equal(qclosest[0], wclosest) and torch.equal(qtree[0].long(), wtree)
+                                          and torch.equal(qparent[0].long(), wparent))) + _rel(qdist[0], wclosest.sqrt()), 1e-15)
+    qlab, qD = K.quickshift_labels(qparent)
+    roots = qparent[0].long().flatten()
+    for _ in range(qH * qW):
+        roots = roots[roots]
+    wD, wlab = (lambda u: (u[0].numel(), u[1]))(torch.unique(roots, return_inverse=True))
+    check("quickshift_labels", float(not (torch.equal(qlab[0].long().flatten(), wlab) and int(qD[0]) == wD)), 0.0)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

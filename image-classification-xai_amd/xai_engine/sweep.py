@@ -93,13 +93,18 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
     elif attr_function == "lime":
         # :168-170 -> limeAttr.py:23-36: the un-normalised [0, 1] image goes to the classifier as it is (no Normalize: the
         # reference's behaviour), quickshift superpixels on the host (skimage; testing_dict["lime_segments"], not a reference key,
-        # a callable from the (H, W, C) image to the ids, replaces the segmenter), 1000 samples, top 5 labels, hide colour 0; the
+        # a callable from the (H, W, C) image to the ids, replaces the segmenter; testing_dict["lime_quickshift"] = "device", not a
+        # reference key either, runs the same quickshift on K53-K55 instead of skimage's), 1000 samples, top 5 labels, hide colour 0; the
         # mask of the five most positive superpixels of the top class times ones(3, H, W), |sum over channels| (:181) = K33's 3 / 0
         if trans_img is None:
             raise ValueError("lime: the row needs the harness's un-normalised [0, 1] image (trans_img)")
         from . import lime
         seg_fn = testing_dict.get("lime_segments")
-        segmenter = (lambda im, seed: seg_fn(im)) if seg_fn is not None else lime.quickshift_segments
+        which = testing_dict.get("lime_quickshift", "skimage")
+        if which not in ("skimage", "device"):
+            raise ValueError(f"lime: testing_dict['lime_quickshift'] must be 'skimage' or 'device', got {which!r}")
+        segmenter = ((lambda im, seed: seg_fn(im)) if seg_fn is not None else
+                     lime.device_quickshift_segments if which == "device" else lime.quickshift_segments)
         model.eval()
         sal = lime.lime_batch(torch.as_tensor(trans_img).to(torch.float32)[None].to(dev), model, segmenter, num_samples=1000, top_labels=5,
                               hide_color=0, random_state=testing_dict.get("lime_random_state"))[0]

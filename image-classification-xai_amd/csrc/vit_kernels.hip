@@ -13,9 +13,15 @@
 // K19 rollout row: one workgroup per image, v in LDS, L-1 vector-matrix products.
 // K20 residual shares: one wave per (block, token), four token 2-norms.
 // K21 cam_attn: one workgroup per image.
+//
+// NaN: the reference's expressions are torch.max, clamp, min and F.normalize, which carry a NaN to their result; fmaxf / fminf
+// return the other operand.  K18's max over heads and clamps, K20's clamped denominators and K21's clamp, min and max follow
+// torch (max_nan, relu_nan, the NaN flag of K21): a NaN gradient gives a NaN row, block or image, as in the reference.
 #include "xai_common.h"
 
 #include <math.h>
+
+#include <atomic>
 
 namespace {
 
@@ -24,6 +30,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kTile = 32;
 constexpr int kK17Waves = 4;
 constexpr int kKUnroll = 8;                        // k-steps of 2 whose loads are issued before their MFMAs
+
+// torch.max / torch.clamp carry a NaN to the result; fmaxf returns the other operand.  IEEE 754-2019 maximum carries it, orders
+// -0 below +0 and is fmaxf on every other pair; on gfx950 it is one instruction (v_maximum3_f32), as v_max_f32 is for fmaxf.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return max_nan(v, 0.f); }
 
 inline int k17_tiles(int S) {
   const int t = (S + kTile - 1) / kTile;
@@ -106,17 +117,17 @@ __global__ __launch_bounds__(256) void rave_matrices_kernel(const float* const* 
   float qs = 0.f;
   if (ablate == 0) {
     for (int j = lane; j < S; j += kWave) qs += fabsf(b2l[S + j] / b2l[j]);
-    qs = fmaxf(wave_sum(qs), 1e-12f);
+    qs = max_nan(wave_sum(qs), 1e-12f);
   }
   float* out = aug + l * plane + static_cast<int64_t>(i) * S;
   float rs = 0.f;
   for (int j = lane; j < S; j += kWave) {
     float m = A[j] * ih[0];
-    for (int h = 1; h < H; ++h) m = fmaxf(m, A[h * plane + j] * ih[h]);
+    for (int h = 1; h < H; ++h) m = max_nan(m, A[h * plane + j] * ih[h]);
     if (Gb) {
       float g = 0.f;
       for (int h = 0; h < H; ++h) g += Gb[h * plane + j];
-      m = fmaxf((g / static_cast<float>(H)) * m, 0.f);
+      m = relu_nan((g / static_cast<float>(H)) * m);
     }
     float r = m * b1l[S + j];
     if (j == i) r = r + b1l[j];
@@ -165,6 +176,23 @@ __global__ __launch_bounds__(kRollWaves* kWave) void rollout_row_kernel(const fl
   for (int j = threadIdx.x; j < S; j += blockDim.x) out[static_cast<int64_t>(blockIdx.x) * S + j] = v[j];
 }
 
+// K19 is the one kernel here that asks for more than 64 KiB of dynamic LDS (17 * S * 4 bytes, up to the CU's 160 KiB at
+// S = 2409).  The limit is declared on the function the first time such a launch is asked for, never inside a stream capture
+// (a first large launch that arrives while its stream is capturing is refused), and an error of the call is returned.
+constexpr size_t kRollMaxLds = 160 * 1024;
+std::atomic<int> g_roll_lds_status{-1};            // -1: not declared yet, else the hipError_t of the declaration
+inline int rollout_row_allow_large_lds(hipStream_t st) {
+  int s = g_roll_lds_status.load(std::memory_order_acquire);
+  if (s < 0) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return XAI_E_UNSUPPORTED;
+    s = static_cast<int>(hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_row_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kRollMaxLds)));
+    g_roll_lds_status.store(s, std::memory_order_release);
+  }
+  return s == static_cast<int>(hipSuccess) ? XAI_OK : s;
+}
+
 // grid (ceil(S / 4), L), 4 waves: wave w owns token s = blockIdx.x*4 + w of block l.
 // tab[4l + 0..3] = input, attention output, input + attention, MLP output of block l, each [S][D] (image 0)
 __global__ __launch_bounds__(256) void residual_shares_kernel(const float* const* __restrict__ tab, int S, int D, float* __restrict__ b1,
@@ -181,7 +209,7 @@ __global__ __launch_bounds__(256) void residual_shares_kernel(const float* const
     q[o] = sqrtf(wave_sum(a));
   }
   if (lane == 0) {
-    const float d1 = fmaxf(q[0] + q[1], 1e-12f), d2 = fmaxf(q[2] + q[3], 1e-12f);
+    const float d1 = max_nan(q[0] + q[1], 1e-12f), d2 = max_nan(q[2] + q[3], 1e-12f);
     float* o1 = b1 + static_cast<int64_t>(l) * 2 * S;
     float* o2 = b2 + static_cast<int64_t>(l) * 2 * S;
     o1[s] = q[0] / d1;
@@ -202,15 +230,18 @@ __global__ __launch_bounds__(kCamThreads) void attn_cam_kernel(const float* __re
   const float* G = grad + static_cast<int64_t>(blockIdx.x) * H * plane;
   float* o = out + static_cast<int64_t>(blockIdx.x) * P;
   float lo = INFINITY, hi = -INFINITY;
+  int has_nan = 0;
   for (int p = threadIdx.x; p < P; p += blockDim.x) {
     float s = 0.f;
     for (int h = 0; h < H; ++h) s += A[h * plane + 1 + p] * G[h * plane + 1 + p];
-    const float c = fmaxf(s / static_cast<float>(H), 0.f);
+    const float c = relu_nan(s / static_cast<float>(H));
     o[p] = c;
+    has_nan |= isnan(c);
     lo = fminf(lo, c);
     hi = fmaxf(hi, c);
   }
   block_min_max<kCamThreads / kWave>(lo, hi, red);
+  if (__syncthreads_or(has_nan)) lo = hi = NAN;   // the reference's min() and max() of a map with a NaN are NaN: all NaN
   for (int p = threadIdx.x; p < P; p += blockDim.x) o[p] = (o[p] - lo) / (hi - lo);   // constant map: 0/0 = NaN, as the reference
 }
 
@@ -251,7 +282,11 @@ XAI_EXPORT int xai_rollout_row_f32(const float* aug, int n_img, int L, int S, in
   XAI_REQUIRE_PTR(aug); XAI_REQUIRE_PTR(out);
   XAI_REQUIRE(n_img > 0 && L > 0 && S > 0 && target_token >= 0 && target_token < S, XAI_E_SHAPE);
   const size_t lds = static_cast<size_t>(kRollWaves + 1) * S * sizeof(float);
-  XAI_REQUIRE(lds <= 160 * 1024 && n_img <= 65535, XAI_E_UNSUPPORTED);
+  XAI_REQUIRE(lds <= kRollMaxLds && n_img <= 65535, XAI_E_UNSUPPORTED);
+  if (lds > 64 * 1024) {
+    const int e = rollout_row_allow_large_lds(static_cast<hipStream_t>(stream));
+    if (e != XAI_OK) return e;
+  }
   hipLaunchKernelGGL(rollout_row_kernel, dim3(n_img), dim3(kRollWaves * kWave), lds, static_cast<hipStream_t>(stream), aug, L, S,
                      target_token, out);
   return xai_launch_status();

@@ -278,13 +278,18 @@ int xai_attn_head_importance_f32(const float* const* attn_tab, const float* cons
  * replaces  ViT_explanation_generator.py:272 (max over heads), :278-281 (bottom-up gradient), compute_RAVE :63-86 (the
  *           r1 @ r2 product is a column scale: r2 is diagonal)
  *   attn_tab[l], bgrad_tab[l] : [H][S][S] (bgrad_tab NULL = withgrad False);  Ih : [L][H];  b1, b2 : [L][2][S];
- *   ablate : 0 or 1;  aug : [L][S][S] */
+ *   ablate : 0 or 1;  aug : [L][S][S]
+ *   NaN: the max over heads, the clamp at 0 and the clamp at 1e-12 carry a NaN as torch.max / clamp / F.normalize do (a NaN
+ *   gradient entry makes its row NaN, as in the reference) */
 int xai_rave_matrices_f32(const float* const* attn_tab, const float* const* bgrad_tab, const float* Ih, const float* b1,
                           const float* b2, int L, int H, int S, int ablate, float* aug, xai_stream_t stream);
 
 /* K19 out[n] = row target_token of aug[n][L-1] . aug[n][L-2] ... aug[n][0], as L-1 vector-matrix products (all entries >= 0)
  * replaces  compute_RAVE, ViT_explanation_generator.py:84-88, and rollout[:, target_token] of :299
- *   aug : [n_img][L][S][S];  out : [n_img][S] */
+ *   aug : [n_img][L][S][S];  out : [n_img][S]
+ *   one workgroup per image with 17 * S * 4 bytes of dynamic LDS: S <= 2409 (160 KiB), beyond that XAI_E_UNSUPPORTED.  Above
+ *   64 KiB the limit is declared on the kernel (hipFuncAttributeMaxDynamicSharedMemorySize) at the first such call of the
+ *   process; that call must not arrive on a capturing stream (XAI_E_UNSUPPORTED), later ones may */
 int xai_rollout_row_f32(const float* aug, int n_img, int L, int S, int target_token, float* out, xai_stream_t stream);
 
 /* K20 residual-stream 2-norm shares of every block, p=1-normalised with a max(., 1e-12) denominator:
@@ -295,7 +300,8 @@ int xai_rollout_row_f32(const float* aug, int n_img, int L, int S, int target_to
 int xai_residual_shares_f32(const float* const* tab, int L, int S, int D, float* b1, float* b2, xai_stream_t stream);
 
 /* K21 out[n][p] = (c[p] - min c) / (max c - min c),  c[p] = max(mean_h A[n][h][0][1+p] * G[n][h][0][1+p], 0), p < S-1;
- *     a constant c gives NaN everywhere, as the reference's 0/0
+ *     a constant c gives NaN everywhere, as the reference's 0/0; so does a NaN in any c[p] of the image (torch's clamp, min
+ *     and max carry it)
  * replaces  ViT_explanation_generator.py:167-177 (Baselines.generate_cam_attn after its backward)
  *   attn, grad : [n_img][H][S][S] of one block;  out : [n_img][S-1] */
 int xai_attn_cam_f32(const float* attn, const float* grad, int n_img, int H, int S, float* out, xai_stream_t stream);

@@ -543,6 +543,26 @@ def test_gig_edge_tolerances_are_tied_to_measured_errors():
                 assert max(r["measured"] for r in mine) == want, (k, side)
 
 
+def test_vit_edge_ledger_holds_every_bound_and_the_bar():
+    """profiles/vit_edges_parity.json is the ledger of tests/test_gpu_vit_edges.py from an MI355X
+    (XAI_PARITY_REPORT=profiles/vit_edges_parity.json python -m pytest tests/test_gpu_vit_edges.py -m gpu -q -x): the run passed, in
+    deterministic mode, with every row of the matrix present; every /bound row (the largest |error| / derived bound of its
+    comparison) is asserted at 1.0 and measured below it; every other row is asserted at no more than the 1e-5 bar."""
+    import json
+    import vit_restated
+    from conftest import BAR
+    led = json.load(open(os.path.join(ROOT, "profiles", "vit_edges_parity.json")))
+    assert led["meta"]["exitstatus"] == 0 and led["meta"]["deterministic"] is True
+    rows = led["comparisons"]
+    assert sorted(r["name"] for r in rows) == vit_restated.ledger_names()
+    assert all(r["measured"] <= r["tol"] for r in rows)
+    for r in rows:
+        if r["name"].endswith("/bound"):
+            assert r["tol"] == 1.0 and r["norm"] == "abs" and r["measured"] <= 1.0, r
+        else:
+            assert r["tol"] <= BAR and r["norm"] == "rel_inf", r
+
+
 def test_model_zoo_state_dicts_have_the_reference_definitions_keys_and_shapes():
     """tests/golden/zoo_state_dicts.npz: every state-dict key and tensor shape of the reference's own classifier definitions (its
     vendored torchvision ResNets, util/modified_models/resnet.py, and its hooked ViT-B/16, VIT_LRP/ViT_ig.py).  The build's zoo must

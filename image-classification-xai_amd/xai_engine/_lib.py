@@ -2,7 +2,8 @@
 (include/xai_hip_ext.h: the entry points added after xai_hip.h was frozen at ABI 1.11) and libxai_ext2.so
 (include/xai_hip_ext2.h: the ones added after xai_hip_ext.h was frozen too) and libxai_ext3.so (include/xai_hip_ext3.h: the ones
 added after xai_hip_ext2.h was pinned at 1.1) and libxai_ext4.so (include/xai_hip_ext4.h: the ones added after xai_hip_ext3.h was pinned
-at 1.0) and libxai_ext5.so (include/xai_hip_ext5.h: the ones added after xai_hip_ext4.h was pinned at 1.0).
+at 1.0) and libxai_ext5.so (include/xai_hip_ext5.h: the ones added after xai_hip_ext4.h was pinned at 1.0) and libxai_ext6.so
+(include/xai_hip_ext6.h: the ones added after xai_hip_ext5.h was pinned at 1.0).
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers below are read
 from it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing
@@ -32,6 +33,9 @@ EXT4_DEFINES = ("XAI_EXT4_VERSION", "XAI_EXT4_MINOR")
 EXT5_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext5.so")
 EXT5_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext5.h")
 EXT5_DEFINES = ("XAI_EXT5_VERSION", "XAI_EXT5_MINOR")
+EXT6_LIB_PATH = os.path.join(_HERE, "lib", "libxai_ext6.so")
+EXT6_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "xai_hip_ext6.h")
+EXT6_DEFINES = ("XAI_EXT6_VERSION", "XAI_EXT6_MINOR")
 
 _lib = None
 _ext = None
@@ -39,6 +43,7 @@ _ext2 = None
 _ext3 = None
 _ext4 = None
 _ext5 = None
+_ext6 = None
 
 
 class XaiHipError(RuntimeError):
@@ -151,6 +156,14 @@ def _read_ext5_header():
         raise XaiHipError(f"{EXT5_HEADER_PATH}: the fifth extension ABI cannot be bound from its header: {e}") from e
 
 
+def _read_ext6_header():
+    try:
+        with open(EXT6_HEADER_PATH) as f:
+            return parse_header(f.read(), EXT6_DEFINES)
+    except (OSError, XaiHipError) as e:
+        raise XaiHipError(f"{EXT6_HEADER_PATH}: the sixth extension ABI cannot be bound from its header: {e}") from e
+
+
 # name -> argument types / return type of every prototype, and the XAI_ABI_VERSION / XAI_ABI_MINOR the header declares
 SIGNATURES, _RESTYPE, (ABI_VERSION, ABI_MINOR) = _read_header()
 # the same for the extension header and its XAI_EXT_VERSION / XAI_EXT_MINOR
@@ -163,6 +176,8 @@ EXT3_SIGNATURES, _EXT3_RESTYPE, (EXT3_VERSION, EXT3_MINOR) = _read_ext3_header()
 EXT4_SIGNATURES, _EXT4_RESTYPE, (EXT4_VERSION, EXT4_MINOR) = _read_ext4_header()
 # and for the fifth extension header and its XAI_EXT5_VERSION / XAI_EXT5_MINOR
 EXT5_SIGNATURES, _EXT5_RESTYPE, (EXT5_VERSION, EXT5_MINOR) = _read_ext5_header()
+# and for the sixth extension header and its XAI_EXT6_VERSION / XAI_EXT6_MINOR
+EXT6_SIGNATURES, _EXT6_RESTYPE, (EXT6_VERSION, EXT6_MINOR) = _read_ext6_header()
 
 
 def load():
@@ -311,6 +326,30 @@ def load_ext5():
         fn.argtypes = argtypes
         fn.restype = _EXT5_RESTYPE[name]
     _ext5 = lib
+    return lib
+
+
+def load_ext6():
+    """Load the sixth extension library once, as strictly as `load_ext5()`: absent -> XaiHipError, the version pair first, then
+    every prototype of include/xai_hip_ext6.h (AttributeError if the .so is stale).  Never falls back."""
+    global _ext6
+    if _ext6 is not None:
+        return _ext6
+    csrc = os.path.join(os.path.dirname(_HERE), "csrc")
+    if not os.path.exists(EXT6_LIB_PATH):
+        raise XaiHipError(f"{EXT6_LIB_PATH} not found: the sixth HIP extension library is not built. Run `make -C {csrc}` (needs "
+                          "hipcc, targets gfx950). There is deliberately no CPU fallback.")
+    lib = C.CDLL(EXT6_LIB_PATH)
+    lib.xai_ext6_version.restype = lib.xai_ext6_version_minor.restype = C.c_int
+    major, minor = lib.xai_ext6_version(), lib.xai_ext6_version_minor()
+    if major != EXT6_VERSION or minor < EXT6_MINOR:
+        raise XaiHipError(f"{EXT6_LIB_PATH} has ABI {major}.{minor}, this package needs {EXT6_VERSION}.{EXT6_MINOR} or a later minor "
+                          f"(include/xai_hip_ext6.h); rebuild with `make -C {csrc}`")
+    for name, argtypes in EXT6_SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError if the .so is stale
+        fn.argtypes = argtypes
+        fn.restype = _EXT6_RESTYPE[name]
+    _ext6 = lib
     return lib
 
 

@@ -58,6 +58,9 @@ def build_parser():
     p.add_argument("--lime_quickshift", choices=("skimage", "device"), default="skimage", help="--attr_func lime: who computes the quickshift "
                    "superpixels.  skimage (default): skimage.segmentation.quickshift on the host, the reference's dependency.  device: the "
                    "same algorithm (scikit-image 0.18.3's, fp64) on the HIP kernels K53-K55; needs no scikit-image")
+    p.add_argument("--vit_cx_clustering", choices=("sklearn", "device"), default="sklearn", help="--attr_func VIT_CX: who clusters the "
+                   "feature-map masks.  sklearn (default): AgglomerativeClustering on a host copy of the distance matrix, the reference's "
+                   "call.  device: the same complete-linkage algorithm on the HIP kernels K56-K57, the same labels bit for bit")
     p.add_argument("--out_dir", type=str, default="pert_test_results")
     p.add_argument("--checkpoint", type=str, default=None, help="path prefix for per-rank resume files (the reference loses a crashed run)")
     return p
@@ -89,7 +92,8 @@ def main(argv=None):
     testing_dict = {"models": [model, model], "imagenet_dataset": args.dataset_path, "normalize": norm, "img_hw": 224,
                     "batch_size": batch_size, "attr_func": args.attr_func, "model_name": args.model,
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
-                    "weights_path": args.weights or "", "num_patches": num_patches, "lime_quickshift": args.lime_quickshift}
+                    "weights_path": args.weights or "", "num_patches": num_patches, "lime_quickshift": args.lime_quickshift,
+                    "vit_cx_clustering": args.vit_cx_clustering}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, fused=not args.eight_runs, out_dir=args.out_dir,
                                                      checkpoint=args.checkpoint, streams=args.streams, reference_counter=args.reference_counter)
     if rank == 0:

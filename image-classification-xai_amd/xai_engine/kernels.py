@@ -1498,3 +1498,68 @@ def quickshift_labels(parent, labels=None):
     ws = torch.empty(max(nbytes, 4), dtype=U8, device=parent.device)
     _call_ext5("xai_quickshift_labels_i32", parent.device, _ptr(parent), B, H, W, _ptr(labels), _ptr(D), _ptr(ws), ws.numel())
     return labels, D
+
+
+# ------------------------------------------------------------------------------ complete linkage (K56-K57; libxai_ext6.so)
+def _call_ext6(name, dev, *args):
+    """`_call` for an entry of the sixth extension library (include/xai_hip_ext6.h); the error texts are xai_strerror's."""
+    lib = _lib.load_ext6()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+
+
+LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_BOUND = 0, 1, 2       # info[0] of K56 / K57 (XAI_LINKAGE_*)
+
+
+def linkage_max_n():
+    """The largest n K56 / K57 take (include/xai_hip_ext6.h, THE CAP)"""
+    return _lib.load_ext6().xai_linkage_max_n()
+
+
+def _linkage_n(distance):
+    if not isinstance(distance, torch.Tensor):
+        raise TypeError(f"distance: expected a torch.Tensor, got {type(distance).__name__}")
+    if distance.dtype != F32:
+        raise TypeError(f"distance: expected {F32}, got {distance.dtype}")
+    if distance.dim() != 2 or distance.shape[0] != distance.shape[1]:
+        raise ValueError(f"distance must be (n, n), got {tuple(distance.shape)}")
+    n = int(distance.shape[0])
+    if n < 2:
+        raise ValueError(f"distance must be (n, n) with n >= 2, got n = {n}")
+    if n > linkage_max_n():
+        raise ValueError(f"distance must be (n, n) with n <= {linkage_max_n()} (include/xai_hip_ext6.h, THE CAP), got n = {n}")
+    _need(distance, F32, "distance")
+    return n
+
+
+def linkage_workspace(distance):
+    """The scratch K56 fills and K57 reads: uint8, xai_linkage_workspace_bytes(n) bytes"""
+    n = _linkage_n(distance)
+    return torch.empty(_lib.load_ext6().xai_linkage_workspace_bytes(n), dtype=U8, device=distance.device)
+
+
+def linkage_complete(distance, ws, info, lanes=0):
+    """K56: distance (n, n) fp32, only i < j read -> the merges in the chain's order inside `ws`, info (4,) int32 = [status, row
+    scans, pushes, merges].  `lanes`: 64, 256 or 1024 lanes in the chain's one workgroup, 0 = the library's default."""
+    n = _linkage_n(distance)
+    _need(ws, U8, "ws")
+    _need(info, I32, "info")
+    if info.numel() != 4:
+        raise ValueError("info must hold 4 int32")
+    if int(lanes) not in (0, 64, 256, 1024):
+        raise ValueError(f"lanes must be 0, 64, 256 or 1024, got {lanes!r}")
+    _call_ext6("xai_linkage_complete_f32", distance.device, _ptr(distance), n, _ptr(ws), ws.numel(), _ptr(info), int(lanes))
+    return info
+
+
+def linkage_sort_relabel(n, ws, children, heights, info):
+    """K57: the merges in `ws` -> children (n - 1, 2) int32 and heights (n - 1,) fp32, sklearn's children_ and distances_"""
+    n = int(n)
+    _need(ws, U8, "ws")
+    _need(children, I32, "children")
+    _need(heights, F32, "heights")
+    _need(info, I32, "info")
+    if children.numel() != 2 * (n - 1) or heights.numel() != n - 1 or info.numel() != 4:
+        raise ValueError(f"children, heights and info must hold {2 * (n - 1)}, {n - 1} and 4 elements")
+    _call_ext6("xai_linkage_sort_relabel_i32", ws.device, n, _ptr(ws), ws.numel(), _ptr(children), _ptr(heights), _ptr(info))
+    return children, heights

@@ -446,6 +446,28 @@ def run(device="cuda:0", verbose=True):
         roots = roots[roots]
     wD, wlab = (lambda u: (u[0].numel(), u[1]))(torch.unique(roots, return_inverse=True))
     check("quickshift_labels", float(not (torch.equal(qlab[0].long().flatten(), wlab) and int(qD[0]) == wD)), 0.0)
+    # complete linkage (K56-K57, libxai_ext6.so) against the textbook loop in torch on the device: merge the closest pair of
+    # clusters, the new row is the elementwise max.  With distinct distances (no ties) the dendrogram is unique.
+    from . import linkage
+    ln = 37
+    lv = torch.rand(ln, 9, device=dev, generator=gen) + 0.05
+    lv = lv / lv.norm(dim=1, keepdim=True)
+    ldist = (1 - lv @ lv.t()).contiguous()
+    lchildren, lheights = linkage.complete_linkage(ldist)
+    lw = torch.triu(ldist, 1)
+    lw = lw + lw.t()
+    lw.fill_diagonal_(float("inf"))
+    lids, lwant_c, lwant_h = list(range(ln)), [], []
+    for lk in range(ln - 1):
+        at = int(torch.argmin(lw))
+        la, lb = sorted((at // ln, at % ln))
+        lwant_c.append(sorted((lids[la], lids[lb])))
+        lwant_h.append(lw[la, lb].clone())
+        lrow = torch.maximum(lw[la], lw[lb])
+        lw[lb], lw[:, lb] = lrow, lrow
+        lw[la], lw[:, la], lw[lb, lb] = float("inf"), float("inf"), float("inf")
+        lids[lb] = ln + lk
+    check("linkage_complete", float(not (lchildren.tolist() == lwant_c and torch.equal(torch.from_numpy(lheights), torch.stack(lwant_h).cpu()))), 0.0)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

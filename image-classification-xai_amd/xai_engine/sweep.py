@@ -227,10 +227,11 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
     if attr_function == "VIT_CX":
         # :231-235: ViT-CX map of the top-1 class (the reference does not pass target_class), min-max normalised, times
         # ones(H,W,3), then |sum over the 3 copies| = 3 * normalised map.  The reference passes gpu_batch=1; the batch only
-        # groups the 2N masked forwards, 50 is ViT_CX's own default.
+        # groups the 2N masked forwards, 50 is ViT_CX's own default.  testing_dict["vit_cx_clustering"] = "device" (not a reference
+        # key) runs the complete-linkage clustering on K56 / K57 instead of scikit-learn's host call: the same labels.
         from .vit_cx import ViT_CX
         result, _ = ViT_CX(model, x, model.blocks[-1].norm1, device=device, gpu_batch=testing_dict.get("vit_cx_batch", 50),
-                           return_feature_map=False)
+                           return_feature_map=False, clustering=testing_dict.get("vit_cx_clustering", "sklearn"))
         result = result.reshape(img_hw, img_hw)
         result = (result - result.min()) / (result.max() - result.min())
         return (result * 3.0).abs().numpy()

@@ -8,7 +8,9 @@ What runs where
   classifier forward (softmax of 2N masked / noised images)        PyTorch-ROCm, batches of `gpu_batch`
   feature maps (D,h,w) -> D normalised (H,W) masks                  K11  xai_up_rownorm_f32 (one launch, written once)
   D x D cosine similarity                                           torch.mm on the device (rocBLAS, a plain library GEMM)
-  complete-linkage agglomerative clustering of the D x D matrix     host, scikit-learn -- exactly the reference's call (:94-95)
+  complete-linkage agglomerative clustering of the D x D matrix     host, scikit-learn -- exactly the reference's call (:94-95);
+                                                                    opt-in (clustering="device"): K56 / K57 and a host heapq cut
+                                                                    (xai_engine/linkage.py), the same labels bit for bit
   cluster sums in the reference's `+=` order, min-max normalise     K13 xai_cluster_sum_f32, K12 xai_rownorm_f32
   x*m + noise*(1-m)  and  x + noise*(1-m)  for every mask           K14 xai_causal_apply_f32 (written straight into the 2N stack)
   sal = p_final @ (masks / sum masks) / N for the target class      K2 weighted form (masked.causal_saliency)
@@ -62,17 +64,38 @@ def cluster_members(labels):
     return members, offs
 
 
-def cluster_masks(mask, distance_threshold):
-    """mask (D,P) on the device -> (K,P) normalised cluster masks (ViT_CX.py:89-109)."""
+CLUSTERINGS = ("sklearn", "device")
+
+
+def check_clustering(clustering):
+    if clustering not in CLUSTERINGS:
+        raise ValueError(f"clustering must be one of {CLUSTERINGS}, got {clustering!r}")
+    return clustering
+
+
+def cluster_labels(distance, distance_threshold, clustering="sklearn"):
+    """distance (D,D) on the device -> the (D,) labels of the reference's AgglomerativeClustering call (ViT_CX.py:94-96).
+    "sklearn": that call, on a host copy of the matrix.  "device": the same algorithm on K56 / K57 (xai_engine/linkage.py); the
+    matrix stays on the device and 12 (D - 1) + 16 bytes come back."""
+    if check_clustering(clustering) == "device":
+        from .linkage import agglomerative_labels
+        return agglomerative_labels(distance.contiguous(), distance_threshold)[0]
     from sklearn.cluster import AgglomerativeClustering
-    similarity = get_cos_similar_matrix(mask, mask)
-    distance = 1 - similarity
     cluster = AgglomerativeClustering(n_clusters=None, distance_threshold=distance_threshold, metric="precomputed", linkage="complete")
     cluster.fit(distance.cpu())
-    members, offs = cluster_members(cluster.labels_)
+    return cluster.labels_
+
+
+def cluster_masks(mask, distance_threshold, clustering="sklearn"):
+    """mask (D,P) on the device -> (K,P) normalised cluster masks (ViT_CX.py:89-109)."""
+    check_clustering(clustering)
+    similarity = get_cos_similar_matrix(mask, mask)
+    distance = 1 - similarity
+    labels = cluster_labels(distance, distance_threshold, clustering)
+    members, offs = cluster_members(labels)
     dev = mask.device
     sums = K.cluster_sum(mask, torch.from_numpy(members).to(dev), torch.from_numpy(offs).to(dev))
-    return K.rownorm(sums), cluster.labels_            # out of place: lets the kernel split a row over several workgroups
+    return K.rownorm(sums), labels                     # out of place: lets the kernel split a row over several workgroups
 
 
 class causal_score(nn.Module):
@@ -132,10 +155,12 @@ def feature_maps(model_softmax, image, target_layer, reshape_function):
 
 
 def ViT_CX(model, image, target_layer, target_category=None, distance_threshold=0.1, reshape_function=reshape_function_vit,
-           gpu_batch=50, device="cuda:0", *, noise=None, device_noise=False, return_feature_map=True):
+           gpu_batch=50, device="cuda:0", *, noise=None, device_noise=False, return_feature_map=True, clustering="sklearn"):
     """-> (sal (H,W), feature_map (D,H,W)) as CPU tensors, like the reference (ViT_CX.py:117).
     Keyword-only extras: `noise` (N,3,H,W) to fix the draw, `device_noise`, `return_feature_map=False` to skip
-    materialising and downloading the D x H x W up-sampled maps (the harness discards them)."""
+    materialising and downloading the D x H x W up-sampled maps (the harness discards them), `clustering`: "sklearn" (default, the
+    reference's host call) or "device" (K56 / K57, `cluster_labels`); anything else is a ValueError."""
+    check_clustering(clustering)
     dev = hip_device(device)
     image = image.to(dev, torch.float32)
     model_softmax = nn.Sequential(model, nn.Softmax(dim=1))
@@ -146,7 +171,7 @@ def ViT_CX(model, image, target_layer, target_category=None, distance_threshold=
     class_p = y_hat[target_category]
     H, W = int(image.shape[2]), int(image.shape[3])
     mask = K.up_rownorm(fmap, H, W)                                         # (D, H*W)
-    mask_clustering_norm, _ = cluster_masks(mask, distance_threshold)
+    mask_clustering_norm, _ = cluster_masks(mask, distance_threshold, clustering)
     scorer = causal_score(model_softmax, (H, W), gpu_batch=gpu_batch, device=device, device_noise=device_noise)
     sal = scorer(image, mask_clustering_norm, class_p, target_category=target_category, noise=noise)
     # no axis shrinks here: K.up_rownorm above has refused an (H, W) below the feature map's (h, w)

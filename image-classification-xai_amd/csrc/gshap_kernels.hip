@@ -3,6 +3,9 @@
 #include "xai_common.h"
 #include "xai_hip_ext.h"
 
+// the version pair of libxai_ext.so; its error texts stay with xai_strerror in libxai_hip.so
+XAI_VERSION_ENTRIES(xai_ext_version, XAI_EXT_VERSION, XAI_EXT_MINOR)
+
 namespace {
 
 // The baseline of row r.  The draw is the caller's (np.random.choice(n_base, ...)); a value outside [0, n_base) is clamped so

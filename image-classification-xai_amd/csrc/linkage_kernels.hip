@@ -15,6 +15,9 @@
 #include <limits.h>
 #include <math.h>
 
+// the version pair of libxai_ext6.so; its error texts stay with xai_strerror in libxai_hip.so
+XAI_VERSION_ENTRIES(xai_ext6_version, XAI_EXT6_VERSION, XAI_EXT6_MINOR)
+
 namespace {
 
 constexpr int kLkMaxN = XAI_LINKAGE_MAX_N;

@@ -19,6 +19,9 @@
 
 #include <math.h>
 
+// the version pair of libxai_ext4.so; its error texts stay with xai_strerror in libxai_hip.so
+XAI_VERSION_ENTRIES(xai_ext4_version, XAI_EXT4_VERSION, XAI_EXT4_MINOR)
+
 namespace {
 
 constexpr int kLrpThreads = 256;

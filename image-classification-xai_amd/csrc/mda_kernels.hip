@@ -25,6 +25,9 @@
 
 #include <math.h>
 
+// the version pair of libxai_ext2.so; its error texts stay with xai_strerror in libxai_hip.so
+XAI_VERSION_ENTRIES(xai_ext2_version, XAI_EXT2_VERSION, XAI_EXT2_MINOR)
+
 namespace {
 
 constexpr int kBlock = 256;

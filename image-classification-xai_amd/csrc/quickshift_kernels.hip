@@ -15,6 +15,9 @@
 #include <float.h>
 #include <math.h>
 
+// the version pair of libxai_ext5.so; its error texts stay with xai_strerror in libxai_hip.so
+XAI_VERSION_ENTRIES(xai_ext5_version, XAI_EXT5_VERSION, XAI_EXT5_MINOR)
+
 namespace {
 
 constexpr int kQsTile = 16;            // a workgroup is a kQsTile x kQsTile block of pixels, one lane each

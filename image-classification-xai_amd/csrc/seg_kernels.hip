@@ -17,6 +17,9 @@
 
 #include <math.h>
 
+// the version pair of libxai_ext3.so; its error texts stay with xai_strerror in libxai_hip.so
+XAI_VERSION_ENTRIES(xai_ext3_version, XAI_EXT3_VERSION, XAI_EXT3_MINOR)
+
 namespace {
 
 constexpr int64_t kSegMaxHw = int64_t(1) << 30;

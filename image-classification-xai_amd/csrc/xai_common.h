@@ -8,6 +8,11 @@
 #include "xai_launch_plan.h"
 
 #define XAI_EXPORT extern "C" __attribute__((visibility("default")))
+// The two version entry points every library exports, `name` and `name`_minor, returning the two version defines of the library's
+// header.  Said once per library, in the first source file of its SRCS_<key> line (csrc/Makefile).
+#define XAI_VERSION_ENTRIES(name, version, minor) \
+  XAI_EXPORT int name(void) { return version; }   \
+  XAI_EXPORT int name##_minor(void) { return minor; }
 
 #define XAI_REQUIRE_PTR(p) \
   do {                     \

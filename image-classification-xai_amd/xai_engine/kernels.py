@@ -1,6 +1,7 @@
-"""Torch-tensor front end of the C ABI (include/xai_hip.h): shape/device checks, output
+"""Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
+Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES>)`.
 """
 import math
 
@@ -32,17 +33,12 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def _call(name, dev, *args):
-    lib = _lib.load()
+def _call(name, dev, *args, lib="hip"):
+    """Launch entry `name` of library `lib` (a key of _lib.LIBRARIES) on torch's current stream of `dev`; the error texts of every
+    library are the main one's xai_strerror."""
+    handle = _lib.load(lib)
     with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
-
-
-def _call_ext(name, dev, *args):
-    """`_call` for an entry of the extension library (include/xai_hip_ext.h); the error texts are xai_strerror's."""
-    lib = _lib.load_ext()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+        _lib.check(getattr(handle, name)(*args, _stream(dev)), name)
 
 
 def _base_args(baseline, like, name="baseline"):
@@ -66,9 +62,12 @@ def _out(t, name, shape, like, wrong=None, dtype=F32, alloc=torch.empty):
     return t
 
 
-def _workspace(entry, dev, *extents):
-    """-> (uint8 device scratch of `entry`(*extents) bytes, or None for 0 bytes; the byte count)"""
-    nbytes = getattr(_lib.load(), entry)(*extents)
+def _workspace(entry, dev, *extents, lib="hip", required=False):
+    """-> (uint8 device scratch of `entry`(*extents) bytes, or None for 0 bytes; the byte count).  `entry` is a *_workspace_bytes
+    of library `lib`; required: 0 bytes there means the extents are refused, not that no scratch is needed."""
+    nbytes = int(getattr(_lib.load(lib), entry)(*extents))
+    if required and nbytes <= 0:
+        raise ValueError(f"{entry}{extents}: no such workspace (an extent is not positive, or too large)")
     return (torch.empty(nbytes, dtype=U8, device=dev) if nbytes else None), nbytes
 
 
@@ -1058,8 +1057,8 @@ def gshap_scale(x, baselines, alpha, idx, n_samples, out=None):
     R = alpha.numel()
     per_row, n_base, E = _gshap_rows(x, baselines, idx, R, n_samples, "gshap_scale")
     out = _out(out, "out", (R,) + tuple(x.shape[1:]), x)
-    _call_ext("xai_gshap_scale_f32", x.device, _ptr(x), _ptr(baselines), _ptr(alpha), _ptr(idx), R, int(n_samples), E, n_base, per_row,
-              _ptr(out))
+    _call("xai_gshap_scale_f32", x.device, _ptr(x), _ptr(baselines), _ptr(alpha), _ptr(idx), R, int(n_samples), E, n_base, per_row,
+          _ptr(out), lib="ext")
     return out
 
 
@@ -1081,29 +1080,22 @@ def gshap_finish(grads, x, baselines, idx, n_samples, want_attr=True, want_map=F
         attr = _out(attr, "attr", (B, Cc, H, W), grads)
     if want_map:
         map = _out(map, "map", (B, H, W), grads)
-    _call_ext("xai_gshap_finish_f32", grads.device, _ptr(grads), _ptr(x), _ptr(baselines), _ptr(idx), B, int(n_samples), Cc, H * W, n_base,
-              per_row, _ptr(attr if want_attr else None), _ptr(map if want_map else None))
+    _call("xai_gshap_finish_f32", grads.device, _ptr(grads), _ptr(x), _ptr(baselines), _ptr(idx), B, int(n_samples), Cc, H * W, n_base,
+          per_row, _ptr(attr if want_attr else None), _ptr(map if want_map else None), lib="ext")
     if want_attr and want_map:
         return attr, map
     return attr if want_attr else map
 
 
 # ------------------------------------------------------------------------------ MDA (K36, K37, K38; libxai_ext2.so)
-def _call_ext2(name, dev, *args):
-    """`_call` for an entry of the second extension library (include/xai_hip_ext2.h); the error texts are xai_strerror's."""
-    lib = _lib.load_ext2()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
-
-
 def mda_max_segments():
     """The largest number of segments of one image K37 takes."""
-    return int(_lib.load_ext2().xai_mda_max_segments())
+    return int(_lib.load("ext2").xai_mda_max_segments())
 
 
 def mda_max_width():
     """The largest sub-search width (candidates per step) K37 takes."""
-    return int(_lib.load_ext2().xai_mda_max_width())
+    return int(_lib.load("ext2").xai_mda_max_width())
 
 
 def _mda_images(start, finish, seg, name):
@@ -1127,7 +1119,7 @@ def mda_compose(start, finish, seg, cand, out=None):
         raise ValueError(f"mda_compose: cand must be ({n_img}, L), got {tuple(cand.shape)}")
     L = cand.shape[1]
     out = _out(out, "out", (n_img * L,) + tuple(start.shape[1:]), start)
-    _call_ext2("xai_mda_compose_f32", start.device, _ptr(start), _ptr(finish), _ptr(seg), _ptr(cand), n_img, L, Cc, hw, _ptr(out))
+    _call("xai_mda_compose_f32", start.device, _ptr(start), _ptr(finish), _ptr(seg), _ptr(cand), n_img, L, Cc, hw, _ptr(out), lib="ext2")
     return out
 
 
@@ -1158,8 +1150,8 @@ def mda_select(resp, order, plan, stop_ref, mode, cutoff, mr, chosen, taken, can
         _need(stop_ref, F32, "stop_ref")
         if tuple(stop_ref.shape) != (n_img, 2):
             raise ValueError(f"mda_select: stop_ref must be ({n_img}, 2), got {tuple(stop_ref.shape)}")
-    _call_ext2("xai_mda_select_f32", resp.device, _ptr(resp), _ptr(order), _ptr(plan), _ptr(stop_ref), n_img, S, L, plan.shape[1],
-               int(mode), int(stop_test), float(cutoff), _ptr(mr), _ptr(chosen), _ptr(taken), _ptr(cand), _ptr(state))
+    _call("xai_mda_select_f32", resp.device, _ptr(resp), _ptr(order), _ptr(plan), _ptr(stop_ref), n_img, S, L, plan.shape[1],
+          int(mode), int(stop_test), float(cutoff), _ptr(mr), _ptr(chosen), _ptr(taken), _ptr(cand), _ptr(state), lib="ext2")
 
 
 def mda_commit(finish, seg, state, start):
@@ -1168,19 +1160,11 @@ def mda_commit(finish, seg, state, start):
     _need(state, I32, "state")
     if tuple(state.shape) != (n_img, 4):
         raise ValueError(f"mda_commit: state must be ({n_img}, 4), got {tuple(state.shape)}")
-    _call_ext2("xai_mda_commit_f32", start.device, _ptr(finish), _ptr(seg), _ptr(state), n_img, Cc, hw, _ptr(start))
+    _call("xai_mda_commit_f32", start.device, _ptr(finish), _ptr(seg), _ptr(state), n_img, Cc, hw, _ptr(start), lib="ext2")
     return start
 
 
 # ------------------------------------------------------------------------------ sanity test (K39-K43; libxai_ext2.so)
-def _workspace_ext2(entry, dev, *extents):
-    """`_workspace` for a *_workspace_bytes entry of the second extension library; 0 bytes there means the extents are refused."""
-    nbytes = int(getattr(_lib.load_ext2(), entry)(*extents))
-    if nbytes <= 0:
-        raise ValueError(f"{entry}{extents}: no such workspace (an extent is not positive, or too large)")
-    return torch.empty(nbytes, dtype=U8, device=dev), nbytes
-
-
 def _maps(t, name):
     """(n, H, W) float32 maps with at least one element"""
     _need(t, F32, name)
@@ -1195,13 +1179,13 @@ def sanity_normalize(x, guard=True, out=None):
     if x.dim() < 2 or x.numel() == 0:
         raise ValueError(f"sanity_normalize: x must be (n, ...) with at least one element per map, got {tuple(x.shape)}")
     out = _out(out, "out", x.shape, x)
-    _call_ext2("xai_sanity_normalize_f32", x.device, _ptr(x), x.shape[0], x[0].numel(), int(bool(guard)), _ptr(out))
+    _call("xai_sanity_normalize_f32", x.device, _ptr(x), x.shape[0], x[0].numel(), int(bool(guard)), _ptr(out), lib="ext2")
     return out.view(x.shape)
 
 
 def ssim_tile():
     """The extent of K40's square output tile."""
-    return int(_lib.load_ext2().xai_ssim_tile())
+    return int(_lib.load("ext2").xai_ssim_tile())
 
 
 def ssim_weights(sigma=1.5, truncate=3.5):
@@ -1222,17 +1206,17 @@ def ssim(x, y, data_range=2.0, want_map=False):
     if H < 11 or W < 11:
         raise ValueError(f"ssim: the Gaussian window is 11 x 11, the maps are {H} x {W}")
     c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
-    ws, nbytes = _workspace_ext2("xai_ssim_workspace_bytes", x.device, n, H, W)
+    ws, nbytes = _workspace("xai_ssim_workspace_bytes", x.device, n, H, W, lib="ext2", required=True)
     mean = torch.empty(n, dtype=F64, device=x.device)
     S = torch.empty((n, H, W), dtype=F32, device=x.device) if want_map else None
-    _call_ext2("xai_ssim_f32", x.device, _ptr(x), _ptr(y), n, H, W, *ssim_weights(), c1, c2, _ptr(mean), _ptr(S), _ptr(ws),
-               nbytes)
+    _call("xai_ssim_f32", x.device, _ptr(x), _ptr(y), n, H, W, *ssim_weights(), c1, c2, _ptr(mean), _ptr(S), _ptr(ws),
+          nbytes, lib="ext2")
     return (mean, S) if want_map else mean
 
 
 def tie_ranks_chunk():
     """The number of sorted positions one workgroup of K41 handles."""
-    return int(_lib.load_ext2().xai_tie_ranks_chunk())
+    return int(_lib.load("ext2").xai_tie_ranks_chunk())
 
 
 def tie_ranks(vals, order):
@@ -1242,13 +1226,13 @@ def tie_ranks(vals, order):
     if vals.dim() != 2 or vals.numel() == 0 or order.shape != vals.shape:
         raise ValueError(f"tie_ranks: vals and order must be (n_rows, n) of one shape, got {tuple(vals.shape)} and {tuple(order.shape)}")
     out = torch.empty_like(order)
-    _call_ext2("xai_tie_ranks_i32", vals.device, _ptr(vals), _ptr(order), vals.shape[0], vals.shape[1], _ptr(out))
+    _call("xai_tie_ranks_i32", vals.device, _ptr(vals), _ptr(order), vals.shape[0], vals.shape[1], _ptr(out), lib="ext2")
     return out
 
 
 def rank_corr_max_n():
     """The largest row length K42 takes."""
-    return int(_lib.load_ext2().xai_rank_corr_max_n())
+    return int(_lib.load("ext2").xai_rank_corr_max_n())
 
 
 def rank_corr(ra, rb, a=None, b=None):
@@ -1259,7 +1243,7 @@ def rank_corr(ra, rb, a=None, b=None):
         raise ValueError(f"rank_corr: ra and rb must be (n_pairs, n) of one shape, got {tuple(ra.shape)} and {tuple(rb.shape)}")
     _shaped_like(a, ra, "a", "ra"); _shaped_like(b, ra, "b", "ra")
     out = torch.empty(ra.shape[0], dtype=F64, device=ra.device)
-    _call_ext2("xai_rank_corr_f64", ra.device, _ptr(ra), _ptr(rb), _ptr(a), _ptr(b), ra.shape[0], ra.shape[1], _ptr(out))
+    _call("xai_rank_corr_f64", ra.device, _ptr(ra), _ptr(rb), _ptr(a), _ptr(b), ra.shape[0], ra.shape[1], _ptr(out), lib="ext2")
     return out
 
 
@@ -1270,20 +1254,13 @@ def hog(img, cell=(16, 16)):
     ch, cw = int(cell[0]), int(cell[1])
     if ch < 1 or cw < 1 or H // ch < 3 or W // cw < 3:
         raise ValueError(f"hog: {H} x {W} pixels in cells of {ch} x {cw} give fewer than 3 cells on an axis")
-    ws, nbytes = _workspace_ext2("xai_hog_workspace_bytes", img.device, n, H, W, ch, cw)
+    ws, nbytes = _workspace("xai_hog_workspace_bytes", img.device, n, H, W, ch, cw, lib="ext2", required=True)
     out = torch.empty((n, (H // ch - 2) * (W // cw - 2) * 81), dtype=F32, device=img.device)
-    _call_ext2("xai_hog_f32", img.device, _ptr(img), n, H, W, ch, cw, _ptr(out), _ptr(ws), nbytes)
+    _call("xai_hog_f32", img.device, _ptr(img), n, H, W, ch, cw, _ptr(out), _ptr(ws), nbytes, lib="ext2")
     return out
 
 
 # ------------------------------------------------------------------------------ segmentation evaluation (K44-K45; libxai_ext3.so)
-def _call_ext3(name, dev, *args):
-    """`_call` for an entry of the third extension library (include/xai_hip_ext3.h); the error texts are xai_strerror's."""
-    lib = _lib.load_ext3()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
-
-
 def seg_normalize(x, out=None):
     """K44: x (n, ...) float32 -> (out, thr, stats): every map min-max normalised in fp32 (evaluateImageNetSeg.py:215-217; Inf is not
     replaced, a constant map becomes NaN), thr (n,) float32 the mean of each normalised map in the header's stated fp64 tree, stats
@@ -1295,7 +1272,7 @@ def seg_normalize(x, out=None):
     n = x.shape[0]
     thr = torch.empty(n, dtype=F32, device=x.device)
     stats = torch.empty((n, 2), dtype=F32, device=x.device)
-    _call_ext3("xai_seg_normalize_f32", x.device, _ptr(x), n, x[0].numel(), _ptr(out), _ptr(thr), _ptr(stats))
+    _call("xai_seg_normalize_f32", x.device, _ptr(x), n, x[0].numel(), _ptr(out), _ptr(thr), _ptr(stats), lib="ext3")
     return out.view(x.shape), thr, stats
 
 
@@ -1311,18 +1288,11 @@ def seg_counts(res, labels, thr):
     T = thr.shape[1]
     counts = torch.empty((n, T, H, 2, 3), dtype=I32, device=res.device)
     other = torch.empty(n, dtype=I32, device=res.device)
-    _call_ext3("xai_seg_counts_i32", res.device, _ptr(res), _ptr(labels), _ptr(thr), n, H, W, T, _ptr(counts), _ptr(other))
+    _call("xai_seg_counts_i32", res.device, _ptr(res), _ptr(labels), _ptr(thr), n, H, W, T, _ptr(counts), _ptr(other), lib="ext3")
     return counts, other
 
 
 # ------------------------------------------------------------------------------ Transformer Attribution (K46-K52; libxai_ext4.so)
-def _call_ext4(name, dev, *args):
-    """`_call` for an entry of the fourth extension library (include/xai_hip_ext4.h); the error texts are xai_strerror's."""
-    lib = _lib.load_ext4()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
-
-
 def _images(t, name):
     """(B, elements per image) of an operand whose leading axis counts images"""
     _need(t, F32, name)
@@ -1335,7 +1305,7 @@ def lrp_split(x, pos=None, neg=None):
     """K46: x (B, ...) -> (clamp(x, min=0), clamp(x, max=0))"""
     B, n = _images(x, "x")
     pos, neg = _out(pos, "pos", x.shape, x), _out(neg, "neg", x.shape, x)
-    _call_ext4("xai_lrp_split_f32", x.device, _ptr(x), B, n, _ptr(pos), _ptr(neg))
+    _call("xai_lrp_split_f32", x.device, _ptr(x), B, n, _ptr(pos), _ptr(neg), lib="ext4")
     return pos, neg
 
 
@@ -1346,7 +1316,7 @@ def lrp_ratio(r, z1, z2=None, out=None):
     if z1 is None:
         raise TypeError("z1: expected a torch.Tensor, got NoneType")
     out = _out(out, "out", r.shape, r)
-    _call_ext4("xai_lrp_ratio_f32", r.device, _ptr(r), _ptr(z1), _ptr(z2), B, n, _ptr(out))
+    _call("xai_lrp_ratio_f32", r.device, _ptr(r), _ptr(z1), _ptr(z2), B, n, _ptr(out), lib="ext4")
     return out
 
 
@@ -1357,7 +1327,7 @@ def lrp_gather(x, g1, g2, out=None):
         _need(t, F32, name)
         _shaped_like(t, x, name, "x")
     out = _out(out, "out", x.shape, x)
-    _call_ext4("xai_lrp_gather_f32", x.device, _ptr(x), _ptr(g1), _ptr(g2), B, n, _ptr(out))
+    _call("xai_lrp_gather_f32", x.device, _ptr(x), _ptr(g1), _ptr(g2), B, n, _ptr(out), lib="ext4")
     return out
 
 
@@ -1371,7 +1341,7 @@ def lrp_half_product(x, c, out=None, slot=None):
         if n > 2 ** 31 - 1:
             raise ValueError(f"lrp_half_product: {n} elements per image are more than K49 takes")
         out = _out(out, "out", x.shape, x)
-        _call_ext4("xai_lrp_half_product_f32", x.device, _ptr(x), _ptr(c), B, 1, n, 1, 1, 0, _ptr(out))
+        _call("xai_lrp_half_product_f32", x.device, _ptr(x), _ptr(c), B, 1, n, 1, 1, 0, _ptr(out), lib="ext4")
         return out
     if x.dim() != 4 or x.numel() == 0:
         raise ValueError(f"lrp_half_product: a slot needs x of (B, h, N, d), got {tuple(x.shape)}")
@@ -1381,13 +1351,13 @@ def lrp_half_product(x, c, out=None, slot=None):
     if out is None:
         raise TypeError("lrp_half_product: a slot needs the cam_qkv buffer as out")
     _out(out, "out", (B, N, 3 * h * d), x, wrong=f"out must be the ({B}, {N}, {3 * h * d}) cam_qkv buffer")
-    _call_ext4("xai_lrp_half_product_f32", x.device, _ptr(x), _ptr(c), B, h, N, d, 3, int(slot), _ptr(out))
+    _call("xai_lrp_half_product_f32", x.device, _ptr(x), _ptr(c), B, h, N, d, 3, int(slot), _ptr(out), lib="ext4")
     return out
 
 
 def lrp_add_chunk():
     """the elements of an image one workgroup of K50 sums"""
-    return _lib.load_ext4().xai_lrp_add_chunk()
+    return _lib.load("ext4").xai_lrp_add_chunk()
 
 
 def lrp_add(x0, x1, r, a=None, b=None, ws=None):
@@ -1398,14 +1368,14 @@ def lrp_add(x0, x1, r, a=None, b=None, ws=None):
         _need(t, F32, name)
         _shaped_like(t, r, name, "r")
     a, b = _out(a, "a", r.shape, r), _out(b, "b", r.shape, r)
-    nbytes = _lib.load_ext4().xai_lrp_add_workspace_bytes(B, n)
+    nbytes = _lib.load("ext4").xai_lrp_add_workspace_bytes(B, n)
     if nbytes == 0:
         raise ValueError(f"lrp_add: {B} images of {n} elements are more than K50 takes")
     if ws is None:
         ws = torch.empty(nbytes, dtype=U8, device=r.device)
     _need(ws, U8, "ws")
-    _call_ext4("xai_lrp_add_parts_f32", r.device, _ptr(x0), _ptr(x1), _ptr(r), B, n, _ptr(a), _ptr(b), _ptr(ws), ws.numel())
-    _call_ext4("xai_lrp_add_scale_f32", r.device, _ptr(a), _ptr(b), B, n, _ptr(ws), ws.numel())
+    _call("xai_lrp_add_parts_f32", r.device, _ptr(x0), _ptr(x1), _ptr(r), B, n, _ptr(a), _ptr(b), _ptr(ws), ws.numel(), lib="ext4")
+    _call("xai_lrp_add_scale_f32", r.device, _ptr(a), _ptr(b), B, n, _ptr(ws), ws.numel(), lib="ext4")
     return a, b
 
 
@@ -1416,7 +1386,7 @@ def lrp_clone(x, r1, r2, out=None):
         _need(t, F32, name)
         _shaped_like(t, x, name, "x")
     out = _out(out, "out", x.shape, x)
-    _call_ext4("xai_lrp_clone_f32", x.device, _ptr(x), _ptr(r1), _ptr(r2), B, n, _ptr(out))
+    _call("xai_lrp_clone_f32", x.device, _ptr(x), _ptr(r1), _ptr(r2), B, n, _ptr(out), lib="ext4")
     return out
 
 
@@ -1435,21 +1405,14 @@ def lrp_attn_matrices(cam, grad=None, mode=LRP_ROLLOUT):
         raise ValueError("mode must be LRP_MATRICES, LRP_ROLLOUT or LRP_CLS_ROW")
     L, B, h, S, _ = cam.shape
     out = torch.empty((B, L, S) if mode == LRP_CLS_ROW else (B, L, S, S), dtype=F32, device=cam.device)
-    _call_ext4("xai_lrp_attn_matrices_f32", cam.device, _ptr(cam), _ptr(grad), L, B, h, S, int(mode), _ptr(out))
+    _call("xai_lrp_attn_matrices_f32", cam.device, _ptr(cam), _ptr(grad), L, B, h, S, int(mode), _ptr(out), lib="ext4")
     return out
 
 
 # ------------------------------------------------------------------------------ quickshift superpixels (K53-K55; libxai_ext5.so)
-def _call_ext5(name, dev, *args):
-    """`_call` for an entry of the fifth extension library (include/xai_hip_ext5.h); the error texts are xai_strerror's."""
-    lib = _lib.load_ext5()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
-
-
 def quickshift_lds_bytes(C, kernel_size):
     """The LDS bytes a workgroup of K53 / K54 stages; the entries refuse more than 65536 (include/xai_hip_ext5.h, THE CAP)"""
-    return _lib.load_ext5().xai_quickshift_lds_bytes(int(C), float(kernel_size))
+    return _lib.load("ext5").xai_quickshift_lds_bytes(int(C), float(kernel_size))
 
 
 def _quickshift_shape(features, name="features"):
@@ -1466,7 +1429,7 @@ def quickshift_density(features, noise, kernel_size, out=None):
     if tuple(noise.shape) != (B, H, W):
         raise ValueError(f"noise must be {(B, H, W)}, got {tuple(noise.shape)}")
     out = _out(out, "out", (B, H, W), features, dtype=F64)
-    _call_ext5("xai_quickshift_density_f64", features.device, _ptr(features), _ptr(noise), B, H, W, C, float(kernel_size), _ptr(out))
+    _call("xai_quickshift_density_f64", features.device, _ptr(features), _ptr(noise), B, H, W, C, float(kernel_size), _ptr(out), lib="ext5")
     return out
 
 
@@ -1481,8 +1444,8 @@ def quickshift_parent(features, dens, kernel_size, max_dist, want_tree=False):
     tree = torch.empty_like(parent) if want_tree else None
     closest = torch.empty((B, H, W), dtype=F64, device=features.device)
     dist = torch.empty_like(closest)
-    _call_ext5("xai_quickshift_parent_f64", features.device, _ptr(features), _ptr(dens), B, H, W, C, float(kernel_size), float(max_dist),
-               _ptr(parent), _ptr(tree), _ptr(closest), _ptr(dist))
+    _call("xai_quickshift_parent_f64", features.device, _ptr(features), _ptr(dens), B, H, W, C, float(kernel_size), float(max_dist),
+          _ptr(parent), _ptr(tree), _ptr(closest), _ptr(dist), lib="ext5")
     return parent, closest, dist, tree
 
 
@@ -1494,26 +1457,19 @@ def quickshift_labels(parent, labels=None):
     B, H, W = parent.shape
     labels = _out(labels, "labels", (B, H, W), parent, dtype=I32)
     D = torch.empty((B,), dtype=I32, device=parent.device)
-    nbytes = _lib.load_ext5().xai_quickshift_workspace_bytes(B, H, W)
+    nbytes = _lib.load("ext5").xai_quickshift_workspace_bytes(B, H, W)
     ws = torch.empty(max(nbytes, 4), dtype=U8, device=parent.device)
-    _call_ext5("xai_quickshift_labels_i32", parent.device, _ptr(parent), B, H, W, _ptr(labels), _ptr(D), _ptr(ws), ws.numel())
+    _call("xai_quickshift_labels_i32", parent.device, _ptr(parent), B, H, W, _ptr(labels), _ptr(D), _ptr(ws), ws.numel(), lib="ext5")
     return labels, D
 
 
 # ------------------------------------------------------------------------------ complete linkage (K56-K57; libxai_ext6.so)
-def _call_ext6(name, dev, *args):
-    """`_call` for an entry of the sixth extension library (include/xai_hip_ext6.h); the error texts are xai_strerror's."""
-    lib = _lib.load_ext6()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
-
-
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_BOUND = 0, 1, 2       # info[0] of K56 / K57 (XAI_LINKAGE_*)
 
 
 def linkage_max_n():
     """The largest n K56 / K57 take (include/xai_hip_ext6.h, THE CAP)"""
-    return _lib.load_ext6().xai_linkage_max_n()
+    return _lib.load("ext6").xai_linkage_max_n()
 
 
 def _linkage_n(distance):
@@ -1535,7 +1491,7 @@ def _linkage_n(distance):
 def linkage_workspace(distance):
     """The scratch K56 fills and K57 reads: uint8, xai_linkage_workspace_bytes(n) bytes"""
     n = _linkage_n(distance)
-    return torch.empty(_lib.load_ext6().xai_linkage_workspace_bytes(n), dtype=U8, device=distance.device)
+    return torch.empty(_lib.load("ext6").xai_linkage_workspace_bytes(n), dtype=U8, device=distance.device)
 
 
 def linkage_complete(distance, ws, info, lanes=0):
@@ -1548,7 +1504,7 @@ def linkage_complete(distance, ws, info, lanes=0):
         raise ValueError("info must hold 4 int32")
     if int(lanes) not in (0, 64, 256, 1024):
         raise ValueError(f"lanes must be 0, 64, 256 or 1024, got {lanes!r}")
-    _call_ext6("xai_linkage_complete_f32", distance.device, _ptr(distance), n, _ptr(ws), ws.numel(), _ptr(info), int(lanes))
+    _call("xai_linkage_complete_f32", distance.device, _ptr(distance), n, _ptr(ws), ws.numel(), _ptr(info), int(lanes), lib="ext6")
     return info
 
 
@@ -1561,5 +1517,5 @@ def linkage_sort_relabel(n, ws, children, heights, info):
     _need(info, I32, "info")
     if children.numel() != 2 * (n - 1) or heights.numel() != n - 1 or info.numel() != 4:
         raise ValueError(f"children, heights and info must hold {2 * (n - 1)}, {n - 1} and 4 elements")
-    _call_ext6("xai_linkage_sort_relabel_i32", ws.device, n, _ptr(ws), ws.numel(), _ptr(children), _ptr(heights), _ptr(info))
+    _call("xai_linkage_sort_relabel_i32", ws.device, n, _ptr(ws), ws.numel(), _ptr(children), _ptr(heights), _ptr(info), lib="ext6")
     return children, heights

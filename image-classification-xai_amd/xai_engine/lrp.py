@@ -257,7 +257,7 @@ def relevance_pass(model, tape, tgt, attns, need):
     for i in range(len(blocks) - 1, need[0] - 1, -1):
         blk, rec = blocks[i], tape.blocks[i]
         if ws is None:
-            ws = torch.empty(K._lib.load_ext4().xai_lrp_add_workspace_bytes(B, rec["x_in"][0].numel()), dtype=torch.uint8, device=dev)
+            ws = torch.empty(K._lib.load("ext4").xai_lrp_add_workspace_bytes(B, rec["x_in"][0].numel()), dtype=torch.uint8, device=dev)
         cam1, cam2 = K.lrp_add(rec["x_mid"].contiguous(), rec["mlp_out"].contiguous(), R, ws=ws)  # add2
         cam2 = _linear(cam2, rec["g"].contiguous(), blk.mlp.fc2.weight)                           # fc2; act passes
         cam2 = _linear(cam2, rec["n2"].contiguous(), blk.mlp.fc1.weight)                          # fc1; norm2 passes

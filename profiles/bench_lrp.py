@@ -189,15 +189,15 @@ def main():
 
     tape, tgt, attns, grads = lrp.record(model, x, torch.tensor([target], device=DEV), True)
     hip = [0]
-    call_ext4 = K._call_ext4
+    call = K._call
 
-    def counted(*a):
-        hip[0] += 1
-        return call_ext4(*a)
-    K._call_ext4 = counted
+    def counted(*a, lib="hip"):
+        hip[0] += lib == "ext4"                      # K46-K52 are the launches of libxai_ext4.so
+        return call(*a, lib=lib)
+    K._call = counted
     with Count() as c:
         lrp.relevance_pass(model, tape, tgt, attns, list(range(depth)))
-    K._call_ext4 = call_ext4
+    K._call = call
     lines += ["", "launches per transformer block over one eager relevance pass (aten operators that are not views, plus HIP launches)",
               f"  engine:            {c.n / depth:7.1f} aten operators + {hip[0] / depth:5.1f} launches of K46-K51"]
     with Count() as c:
@@ -212,7 +212,7 @@ def main():
     q4, c4 = r(1, heads, N, D // heads), r(1, heads, N, D // heads)
     qkv = torch.empty(1, N, 3 * D, device=DEV)
     cam5, grad5 = r(depth, 1, heads, N, N), r(depth, 1, heads, N, N)
-    ws = torch.empty(K._lib.load_ext4().xai_lrp_add_workspace_bytes(1, N * D), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(K._lib.load("ext4").xai_lrp_add_workspace_bytes(1, N * D), dtype=torch.uint8, device=DEV)
     o1, o2 = torch.empty_like(a3), torch.empty_like(a3)
     ow1, ow2 = torch.empty_like(wide), torch.empty_like(wide)
     o4 = torch.empty_like(a4)

@@ -305,9 +305,9 @@ def main():
     ap.add_argument("--ext-lib", help="another build of libxai_ext.so to load instead of the package's")
     args = ap.parse_args()
     if args.lib:
-        _lib.LIB_PATH = os.path.abspath(args.lib)
+        _lib.LIBRARIES["hip"].path = os.path.abspath(args.lib)
     if args.ext_lib:
-        _lib.EXT_LIB_PATH = os.path.abspath(args.ext_lib)
+        _lib.LIBRARIES["ext"].path = os.path.abspath(args.ext_lib)
     _lib.load()
     for part in (ig_entries, cam_rise_blur_entries, insdel_entries, masker_entries, vit_entries, gig_entries, agi_entries, ablation_entries,
                  xrai_entries, lime_gshap_entries):

@@ -118,11 +118,11 @@ def test_version_numbers_are_the_headers_defines(L, monkeypatch, tmp_path):
     assert L.ABI_VERSION == int(re.search(r"^#define XAI_ABI_VERSION (\d+)$", hdr, flags=re.M).group(1))
     assert L.ABI_MINOR == int(re.search(r"^#define XAI_ABI_MINOR (\d+)$", hdr, flags=re.M).group(1))
     assert (L.ABI_VERSION, L.ABI_MINOR) == L.parse_header(hdr)[2]
-    # read once at import, from HEADER_PATH; a header that is absent or does not parse is an error that names the path
+    # read once at import, from the record's header_path; a header that is absent or does not parse is an error that names the path
     for name, text in (("absent.h", None), ("broken.h", hdr.replace("int xai_version(void);", "long xai_version(void);"))):
         path = tmp_path / name
         if text is not None:
             path.write_text(text)
-        monkeypatch.setattr(L, "HEADER_PATH", str(path))
+        monkeypatch.setattr(L.LIBRARIES["hip"], "header_path", str(path))
         with pytest.raises(L.XaiHipError, match=name):
-            L._read_header()
+            L.LIBRARIES["hip"].read_header()

@@ -15,28 +15,12 @@ import pytest
 import torch
 
 import gshap_restated as R
+from abi_libs import built, declared, exported, exported_elsewhere
 from conftest import PKG, ROOT
 from helpers import TinyNet
 
 EXT_HEADER = os.path.join(ROOT, "include", "xai_hip_ext.h")
 _p, _i, _l = C.c_void_p, C.c_int, C.c_int64
-
-
-def _ext_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
 
 
 # ------------------------------------------------------------------------------------------------ the harness row and the CLI
@@ -108,13 +92,14 @@ def test_engine_refuses_the_cpu_and_bad_arguments_before_any_buffer_is_made():
 # ------------------------------------------------------------------------------------------------ the extension library
 def test_extension_header_parses_with_the_strict_reader_and_the_table_equals_the_parse():
     from xai_engine import _lib
-    assert os.path.samefile(_lib.EXT_HEADER_PATH, EXT_HEADER)
+    rec = _lib.LIBRARIES["ext"]
+    assert os.path.samefile(rec.header_path, EXT_HEADER)
     text = open(EXT_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT_DEFINES)
-    assert args == _lib.EXT_SIGNATURES and sorted(args) == _declared(EXT_HEADER)
-    assert version == (_lib.EXT_VERSION, _lib.EXT_MINOR)
-    assert _lib.EXT_VERSION == int(re.search(r"^#define XAI_EXT_VERSION (\d+)$", text, flags=re.M).group(1))
-    assert _lib.EXT_MINOR == int(re.search(r"^#define XAI_EXT_MINOR (\d+)$", text, flags=re.M).group(1))
+    args, ret, version = _lib.parse_header(text, rec.defines)
+    assert args == rec.signatures and sorted(args) == declared(EXT_HEADER)
+    assert version == (rec.version, rec.minor)
+    assert rec.version == int(re.search(r"^#define XAI_EXT_VERSION (\d+)$", text, flags=re.M).group(1))
+    assert rec.minor == int(re.search(r"^#define XAI_EXT_MINOR (\d+)$", text, flags=re.M).group(1))
     assert args["xai_ext_version"] == [] and args["xai_ext_version_minor"] == []
     assert args["xai_gshap_scale_f32"] == [_p, _p, _p, _p, _i, _i, _l, _i, _i, _p, _p]
     assert args["xai_gshap_finish_f32"] == [_p, _p, _p, _p, _i, _i, _i, _l, _i, _i, _p, _p, _p]
@@ -135,7 +120,7 @@ def test_the_default_of_parse_header_is_the_main_headers_pair():
     assert _lib.parse_header(main) == _lib.parse_header(main, _lib.ABI_DEFINES)
     assert _lib.parse_header(main)[0] == _lib.SIGNATURES
     with pytest.raises(_lib.XaiHipError, match="XAI_EXT_MINOR"):
-        _lib.parse_header(main, _lib.EXT_DEFINES)                    # the pair asked for is the pair required
+        _lib.parse_header(main, _lib.LIBRARIES["ext"].defines)       # the pair asked for is the pair required
     with pytest.raises(_lib.XaiHipError, match="XAI_ABI_MINOR"):
         _lib.parse_header(open(EXT_HEADER).read())
 
@@ -169,68 +154,23 @@ def _ext_with(extra, drop=None):
 def test_reader_refuses_a_broken_extension_header_and_quotes_the_statement(text, quoted):
     from xai_engine import _lib
     with pytest.raises(_lib.XaiHipError) as e:
-        _lib.parse_header(text(), _lib.EXT_DEFINES)
+        _lib.parse_header(text(), _lib.LIBRARIES["ext"].defines)
     assert quoted in str(e.value), str(e.value)
-
-
-def test_an_absent_or_broken_extension_header_is_an_error_that_names_the_path(monkeypatch, tmp_path):
-    from xai_engine import _lib
-    hdr = open(EXT_HEADER).read()
-    for name, text in (("absent_ext.h", None), ("broken_ext.h", hdr.replace("int xai_ext_version(void);", "long xai_ext_version(void);"))):
-        path = tmp_path / name
-        if text is not None:
-            path.write_text(text)
-        monkeypatch.setattr(_lib, "EXT_HEADER_PATH", str(path))
-        with pytest.raises(_lib.XaiHipError, match=name):
-            _lib._read_ext_header()
 
 
 def test_extension_library_exports_exactly_its_header_and_the_main_library_still_its_64():
     from xai_engine import _lib, LIB_PATH
-    assert _exported(_ext_path()) == _declared(EXT_HEADER) == sorted(_lib.EXT_SIGNATURES)
-    main = _exported(LIB_PATH)
-    assert main == _declared(os.path.join(ROOT, "include", "xai_hip.h")) and len(main) == 64
-    assert not any("gshap" in n or "_ext_" in n for n in main)
+    assert exported(built("ext")) == declared(EXT_HEADER) == sorted(_lib.LIBRARIES["ext"].signatures)
+    main = exported(LIB_PATH)
+    assert main == declared(os.path.join(ROOT, "include", "xai_hip.h")) and len(main) == 64
+    assert not [(o, n) for o, n in exported_elsewhere("ext") if "gshap" in n or "_ext_" in n]         # nor any of the six others
     assert (_lib.ABI_VERSION, _lib.ABI_MINOR) == (1, 11)
-
-
-def test_loaded_extension_reports_the_headers_version_and_carries_the_headers_types():
-    from xai_engine import _lib
-    _ext_path()
-    lib = _lib.load_ext()
-    assert lib is _lib.load_ext()
-    assert (lib.xai_ext_version(), lib.xai_ext_version_minor()) == (_lib.EXT_VERSION, _lib.EXT_MINOR)
-    for name, types in _lib.EXT_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == types and fn.restype is _i, name
-
-
-def test_binding_refuses_an_absent_an_older_and_a_stale_extension_library(monkeypatch, tmp_path):
-    from xai_engine import _lib
-    _ext_path()
-    monkeypatch.setattr(_lib, "_ext", None)
-    monkeypatch.setattr(_lib, "EXT_LIB_PATH", str(tmp_path / "libxai_ext.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load_ext()
-    monkeypatch.undo()
-    monkeypatch.setattr(_lib, "_ext", None)
-    has = rf"has ABI {_lib.EXT_VERSION}\.{_lib.EXT_MINOR},"
-    monkeypatch.setattr(_lib, "EXT_MINOR", _lib.EXT_MINOR + 1)                       # the package wants a later minor than the .so has
-    with pytest.raises(_lib.XaiHipError, match=has):
-        _lib.load_ext()
-    monkeypatch.undo()
-    monkeypatch.setattr(_lib, "_ext", None)
-    monkeypatch.setitem(_lib.EXT_SIGNATURES, "xai_not_in_the_library_f32", [_p])     # a header ahead of the .so: stale
-    with pytest.raises(AttributeError):
-        _lib.load_ext()
-    monkeypatch.undo()
-    assert _lib.load_ext() is not None
 
 
 def test_both_kernels_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext_path()
-    lib = _lib.load_ext()
+    built("ext")
+    lib = _lib.load("ext")
     p = 16                               # a non-NULL pointer that is never dereferenced: validation comes first
 
     def scale(x=p, base=p, alpha=p, idx=p, out=p, rows=10, n=5, E=147, nb=1, per_row=0):

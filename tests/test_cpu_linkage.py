@@ -7,37 +7,20 @@ import hashlib
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import linkage_restated as R
-from conftest import PKG, ROOT, load_golden
+from abi_libs import PINNED, built, declared, exported, exported_elsewhere
+from conftest import ROOT, load_golden
 
 EXT6_HEADER = os.path.join(ROOT, "include", "xai_hip_ext6.h")
 ENTRIES = ["xai_linkage_complete_f32", "xai_linkage_max_n", "xai_linkage_sort_relabel_i32", "xai_linkage_workspace_bytes"]
 _p, _i, _z = C.c_void_p, C.c_int, C.c_size_t
 SIZES = (2, 3, 5, 63, 64, 65, 127, 129)
 KINDS = ("generic", "q16", "q64", "equal", "blocks")
-
-
-def _ext6_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT6_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT6_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
 
 
 def _matrix(g, tag):
@@ -137,9 +120,9 @@ def test_the_host_cut_of_the_engine_is_the_restated_one_and_keeps_the_threshold_
 def test_ext6_header_parses_at_1_0_and_cites_scipy_and_sklearn():
     from xai_engine import _lib
     text = open(EXT6_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT6_DEFINES)
-    assert version == (1, 0) and (_lib.EXT6_VERSION, _lib.EXT6_MINOR) == (1, 0)
-    assert sorted(args) == _declared(EXT6_HEADER) == sorted(ENTRIES + ["xai_ext6_version", "xai_ext6_version_minor"])
+    args, ret, version = _lib.parse_header(text, _lib.LIBRARIES["ext6"].defines)
+    assert version == (1, 0) and (_lib.LIBRARIES["ext6"].version, _lib.LIBRARIES["ext6"].minor) == PINNED["ext6"] == (1, 0)
+    assert sorted(args) == declared(EXT6_HEADER) == sorted(ENTRIES + ["xai_ext6_version", "xai_ext6_version_minor"])
     assert args["xai_linkage_max_n"] == [] and args["xai_linkage_workspace_bytes"] == [_i]
     assert args["xai_linkage_complete_f32"] == [_p, _i, _p, _z, _p, _i, _p]
     assert args["xai_linkage_sort_relabel_i32"] == [_i, _p, _z, _p, _p, _p, _p]
@@ -156,48 +139,19 @@ def test_ext6_header_parses_at_1_0_and_cites_scipy_and_sklearn():
 
 def test_ext6_library_exports_exactly_its_header_and_the_other_six_are_unchanged():
     from xai_engine import _lib
-    assert _exported(_ext6_path()) == _declared(EXT6_HEADER) == sorted(_lib.EXT6_SIGNATURES)
-    lib = _lib.load_ext6()
+    assert exported(built("ext6")) == declared(EXT6_HEADER) == sorted(_lib.LIBRARIES["ext6"].signatures)
+    lib = _lib.load("ext6")
     assert (lib.xai_ext6_version(), lib.xai_ext6_version_minor()) == (1, 0)
-    for other, sigs in ((_lib.LIB_PATH, _lib.SIGNATURES), (_lib.EXT_LIB_PATH, _lib.EXT_SIGNATURES), (_lib.EXT2_LIB_PATH, _lib.EXT2_SIGNATURES),
-                        (_lib.EXT3_LIB_PATH, _lib.EXT3_SIGNATURES), (_lib.EXT4_LIB_PATH, _lib.EXT4_SIGNATURES),
-                        (_lib.EXT5_LIB_PATH, _lib.EXT5_SIGNATURES)):
-        assert _exported(other) == sorted(sigs), other
-        assert not [s for s in _exported(other) if s.startswith("xai_linkage_") or "ext6" in s], other
-    assert (_lib.ABI_VERSION, _lib.ABI_MINOR, _lib.EXT_VERSION, _lib.EXT_MINOR, _lib.EXT2_VERSION, _lib.EXT2_MINOR, _lib.EXT3_VERSION,
-            _lib.EXT3_MINOR, _lib.EXT4_VERSION, _lib.EXT4_MINOR, _lib.EXT5_VERSION, _lib.EXT5_MINOR) == (1, 11, 1, 0, 1, 1, 1, 0, 1, 0, 1, 0)
-
-
-def test_load_ext6_refuses_an_absent_an_older_and_a_stale_library(tmp_path, monkeypatch):
-    from xai_engine import _lib
-    real = _ext6_path()
-    monkeypatch.setattr(_lib, "_ext6", None)
-    monkeypatch.setattr(_lib, "EXT6_LIB_PATH", str(tmp_path / "libxai_ext6.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load_ext6()
-    monkeypatch.setattr(_lib, "EXT6_LIB_PATH", real)
-    monkeypatch.setattr(_lib, "EXT6_MINOR", 1)                            # the package wants a later minor than the library has
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1"):
-        _lib.load_ext6()
-    monkeypatch.setattr(_lib, "EXT6_MINOR", 0)
-    monkeypatch.setattr(_lib, "EXT6_SIGNATURES", dict(_lib.EXT6_SIGNATURES, xai_linkage_later_f32=[_p]))
-    monkeypatch.setattr(_lib, "_EXT6_RESTYPE", dict(_lib._EXT6_RESTYPE, xai_linkage_later_f32=_i))
-    with pytest.raises(AttributeError):                                   # a prototype the built library does not have: stale
-        _lib.load_ext6()
-    assert _lib._ext6 is None
-
-
-def test_build_names_the_seventh_library():
-    import __graft_entry__ as g
-    src = inspect.getsource(g.build)
-    assert "load_ext6" in src and "libxai_ext6.so" in src and "linkage" in src
+    # each of the other six exports exactly its own header (exported_elsewhere), none of them an entry of this feature
+    assert not [(o, n) for o, n in exported_elsewhere("ext6") if n.startswith("xai_linkage_") or "ext6" in n]
+    assert {k: (rec.version, rec.minor) for k, rec in _lib.LIBRARIES.items()} == PINNED
 
 
 # ------------------------------------------------------------------------------------------------ refusals, no device
 def test_k56_and_k57_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext6_path()
-    lib = _lib.load_ext6()
+    built("ext6")
+    lib = _lib.load("ext6")
     p = 16                               # a non-NULL, aligned pointer that is never dereferenced: validation comes first
     cap = lib.xai_linkage_max_n()
     assert cap == 2048 >= 1024

@@ -6,37 +6,20 @@ import inspect
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import lrp_restated as R
-from conftest import GOLDEN, PKG, ROOT
+from abi_libs import PINNED, built, declared, exported, exported_elsewhere
+from conftest import GOLDEN, ROOT
 
 EXT4_HEADER = os.path.join(ROOT, "include", "xai_hip_ext4.h")
 ENTRIES = ["xai_lrp_add_chunk", "xai_lrp_add_parts_f32", "xai_lrp_add_scale_f32", "xai_lrp_add_workspace_bytes",
            "xai_lrp_attn_matrices_f32", "xai_lrp_clone_f32", "xai_lrp_gather_f32", "xai_lrp_half_product_f32", "xai_lrp_ratio_f32",
            "xai_lrp_split_f32"]
 _p, _i, _l, _z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
-
-
-def _ext4_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT4_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT4_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
 
 
 # ------------------------------------------------------------------------------------------------ module path, tuples, CLIs
@@ -101,9 +84,9 @@ def test_the_segmentation_cli_still_refuses_t_attr_by_name():
 def test_ext4_header_parses_at_1_0_and_cites_the_reference():
     from xai_engine import _lib
     text = open(EXT4_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT4_DEFINES)
-    assert version == (1, 0) and (_lib.EXT4_VERSION, _lib.EXT4_MINOR) == (1, 0)
-    assert sorted(args) == _declared(EXT4_HEADER) == sorted(ENTRIES + ["xai_ext4_version", "xai_ext4_version_minor"])
+    args, ret, version = _lib.parse_header(text, _lib.LIBRARIES["ext4"].defines)
+    assert version == (1, 0) and (_lib.LIBRARIES["ext4"].version, _lib.LIBRARIES["ext4"].minor) == PINNED["ext4"] == (1, 0)
+    assert sorted(args) == declared(EXT4_HEADER) == sorted(ENTRIES + ["xai_ext4_version", "xai_ext4_version_minor"])
     assert args["xai_lrp_split_f32"] == [_p, _i, _l, _p, _p, _p]
     assert args["xai_lrp_ratio_f32"] == [_p, _p, _p, _i, _l, _p, _p]
     assert args["xai_lrp_half_product_f32"] == [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]
@@ -123,41 +106,19 @@ def test_ext4_header_parses_at_1_0_and_cites_the_reference():
 
 def test_ext4_library_exports_exactly_its_header_and_the_other_four_are_unchanged():
     from xai_engine import _lib
-    assert _exported(_ext4_path()) == _declared(EXT4_HEADER) == sorted(_lib.EXT4_SIGNATURES)
-    lib = _lib.load_ext4()
+    assert exported(built("ext4")) == declared(EXT4_HEADER) == sorted(_lib.LIBRARIES["ext4"].signatures)
+    lib = _lib.load("ext4")
     assert (lib.xai_ext4_version(), lib.xai_ext4_version_minor()) == (1, 0)
     assert lib.xai_lrp_add_chunk() == R.ADD_CHUNK == 4096
-    for other, sigs in ((_lib.LIB_PATH, _lib.SIGNATURES), (_lib.EXT_LIB_PATH, _lib.EXT_SIGNATURES), (_lib.EXT2_LIB_PATH, _lib.EXT2_SIGNATURES),
-                        (_lib.EXT3_LIB_PATH, _lib.EXT3_SIGNATURES)):
-        assert _exported(other) == sorted(sigs), other                           # each exports exactly its own, older header
-        assert not [s for s in _exported(other) if s.startswith("xai_lrp_") or "ext4" in s], other
-    assert (_lib.ABI_VERSION, _lib.ABI_MINOR, _lib.EXT_VERSION, _lib.EXT_MINOR, _lib.EXT2_VERSION, _lib.EXT2_MINOR, _lib.EXT3_VERSION,
-            _lib.EXT3_MINOR) == (1, 11, 1, 0, 1, 1, 1, 0)
-
-
-def test_load_ext4_refuses_an_absent_an_older_and_a_stale_library(tmp_path, monkeypatch):
-    from xai_engine import _lib
-    real = _ext4_path()
-    monkeypatch.setattr(_lib, "_ext4", None)
-    monkeypatch.setattr(_lib, "EXT4_LIB_PATH", str(tmp_path / "libxai_ext4.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load_ext4()
-    monkeypatch.setattr(_lib, "EXT4_LIB_PATH", real)
-    monkeypatch.setattr(_lib, "EXT4_MINOR", 1)                            # the package wants a later minor than the library has
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1"):
-        _lib.load_ext4()
-    monkeypatch.setattr(_lib, "EXT4_MINOR", 0)
-    monkeypatch.setattr(_lib, "EXT4_SIGNATURES", dict(_lib.EXT4_SIGNATURES, xai_lrp_later_f32=[_p]))
-    monkeypatch.setattr(_lib, "_EXT4_RESTYPE", dict(_lib._EXT4_RESTYPE, xai_lrp_later_f32=_i))
-    with pytest.raises(AttributeError):                                   # a prototype the built library does not have: stale
-        _lib.load_ext4()
-    assert _lib._ext4 is None
+    # each of the other six exports exactly its own header (exported_elsewhere), none of them an entry of this feature
+    assert not [(o, n) for o, n in exported_elsewhere("ext4") if n.startswith("xai_lrp_") or "ext4" in n]
+    assert {k: (rec.version, rec.minor) for k, rec in _lib.LIBRARIES.items()} == PINNED
 
 
 def test_k46_to_k52_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext4_path()
-    lib = _lib.load_ext4()
+    built("ext4")
+    lib = _lib.load("ext4")
     p = 16                               # a non-NULL, 16-byte aligned pointer that is never dereferenced: validation comes first
     assert lib.xai_lrp_split_f32(None, 1, 4, p, p, None) == lib.xai_lrp_split_f32(p, 1, 4, None, p, None) == -1
     assert [lib.xai_lrp_split_f32(p, 0, 4, p, p, None), lib.xai_lrp_split_f32(p, 1, 0, p, p, None)] == [-2, -2]

@@ -16,28 +16,12 @@ import pytest
 import torch
 
 import mda_restated as R
+from abi_libs import built, declared, exported, exported_elsewhere
 from conftest import BAR, GOLDEN, PKG, ROOT, check, load_golden
 
 EXT2_HEADER = os.path.join(ROOT, "include", "xai_hip_ext2.h")
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 CASES = sorted(R.CASES)
-
-
-def _ext2_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT2_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT2_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
 
 
 # ------------------------------------------------------------------------------------------------ the restatement vs the reference
@@ -251,21 +235,22 @@ def test_end_index_is_the_first_response_at_or_above_090_else_the_length():
 # ------------------------------------------------------------------------------------------------ the second extension library
 def test_ext2_header_parses_with_the_strict_reader_and_the_table_equals_the_parse():
     from xai_engine import _lib
-    assert os.path.samefile(_lib.EXT2_HEADER_PATH, EXT2_HEADER)
+    rec = _lib.LIBRARIES["ext2"]
+    assert os.path.samefile(rec.header_path, EXT2_HEADER)
     text = open(EXT2_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT2_DEFINES)
-    assert args == _lib.EXT2_SIGNATURES and sorted(args) == _declared(EXT2_HEADER)
-    assert version == (_lib.EXT2_VERSION, _lib.EXT2_MINOR)
+    args, ret, version = _lib.parse_header(text, rec.defines)
+    assert args == rec.signatures and sorted(args) == declared(EXT2_HEADER)
+    assert version == (rec.version, rec.minor)
     # the pair is read from the header, whatever it has grown to
-    assert _lib.EXT2_VERSION == int(re.search(r"^#define XAI_EXT2_VERSION (\d+)$", text, flags=re.M).group(1))
-    assert _lib.EXT2_MINOR == int(re.search(r"^#define XAI_EXT2_MINOR (\d+)$", text, flags=re.M).group(1))
+    assert rec.version == int(re.search(r"^#define XAI_EXT2_VERSION (\d+)$", text, flags=re.M).group(1))
+    assert rec.minor == int(re.search(r"^#define XAI_EXT2_MINOR (\d+)$", text, flags=re.M).group(1))
     assert args["xai_ext2_version"] == [] and args["xai_ext2_version_minor"] == [] and args["xai_mda_max_segments"] == []
     assert args["xai_mda_compose_f32"] == [_p, _p, _p, _p, _i, _i, _i, _l, _p, _p]
     assert args["xai_mda_select_f32"] == [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p]
     assert args["xai_mda_commit_f32"] == [_p, _p, _p, _i, _i, _l, _p, _p]
     assert all(t is _i for t in ret.values())
     # the three headers do not share a name
-    assert not set(args) & set(_lib.SIGNATURES) and not set(args) & set(_lib.EXT_SIGNATURES)
+    assert not set(args) & set(_lib.SIGNATURES) and not set(args) & set(_lib.LIBRARIES["ext"].signatures)
     # every MDA launch entry cites the lines of MDAFunctions.py it replaces (a later feature's entries cite their own source)
     for name in args:
         if name.startswith("xai_mda_") and name.endswith(("_f32", "_f64", "_i32", "_u64")):
@@ -273,52 +258,21 @@ def test_ext2_header_parses_with_the_strict_reader_and_the_table_equals_the_pars
             comment = text[text.rfind("/*", 0, at):at]
             assert re.search(r"replaces\s+MDAFunctions\.py:\d+", comment), name
     with pytest.raises(_lib.XaiHipError, match="XAI_EXT2_MINOR"):
-        _lib.parse_header(open(_lib.EXT_HEADER_PATH).read(), _lib.EXT2_DEFINES)
+        _lib.parse_header(open(_lib.LIBRARIES["ext"].header_path).read(), rec.defines)
 
 
 def test_ext2_library_exports_exactly_its_header_and_the_other_two_are_untouched():
-    from xai_engine import _lib, LIB_PATH
-    assert _exported(_ext2_path()) == _declared(EXT2_HEADER) == sorted(_lib.EXT2_SIGNATURES)
-    assert not any("mda" in n or "ext2" in n for n in _exported(LIB_PATH) + _exported(_lib.EXT_LIB_PATH))
-
-
-def test_loaded_ext2_reports_the_headers_version_and_carries_the_headers_types():
     from xai_engine import _lib
-    _ext2_path()
-    lib = _lib.load_ext2()
-    assert lib is _lib.load_ext2()
-    assert (lib.xai_ext2_version(), lib.xai_ext2_version_minor()) == (_lib.EXT2_VERSION, _lib.EXT2_MINOR)
-    for name, types in _lib.EXT2_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == types and fn.restype is _i, name
+    assert exported(built("ext2")) == declared(EXT2_HEADER) == sorted(_lib.LIBRARIES["ext2"].signatures)
+    assert not [(o, n) for o, n in exported_elsewhere("ext2") if "mda" in n or "ext2" in n]
+    lib = _lib.load("ext2")
     assert lib.xai_mda_max_segments() >= 1024 and lib.xai_mda_max_width() >= 28
-
-
-def test_binding_refuses_an_absent_an_older_and_a_stale_ext2_library(monkeypatch, tmp_path):
-    from xai_engine import _lib
-    _ext2_path()
-    monkeypatch.setattr(_lib, "_ext2", None)
-    monkeypatch.setattr(_lib, "EXT2_LIB_PATH", str(tmp_path / "libxai_ext2.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load_ext2()
-    monkeypatch.undo()
-    monkeypatch.setattr(_lib, "_ext2", None)
-    monkeypatch.setattr(_lib, "EXT2_MINOR", _lib.EXT2_MINOR + 1)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI \d+\.\d+,"):
-        _lib.load_ext2()
-    monkeypatch.undo()
-    monkeypatch.setattr(_lib, "_ext2", None)
-    monkeypatch.setitem(_lib.EXT2_SIGNATURES, "xai_not_in_the_library_f32", [_p])
-    with pytest.raises(AttributeError):
-        _lib.load_ext2()
-    monkeypatch.undo()
-    assert _lib.load_ext2() is not None
 
 
 def test_the_three_kernels_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext2_path()
-    lib = _lib.load_ext2()
+    built("ext2")
+    lib = _lib.load("ext2")
     cap = lib.xai_mda_max_segments()
     p = 16                               # a non-NULL pointer that is never dereferenced: validation comes first
 

@@ -6,37 +6,20 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import quickshift_restated as R
-from conftest import PKG, ROOT, load_golden
+from abi_libs import PINNED, built, declared, exported, exported_elsewhere
+from conftest import ROOT, load_golden
 
 EXT5_HEADER = os.path.join(ROOT, "include", "xai_hip_ext5.h")
 ENTRIES = ["xai_quickshift_density_f64", "xai_quickshift_labels_i32", "xai_quickshift_lds_bytes", "xai_quickshift_parent_f64",
            "xai_quickshift_workspace_bytes"]
 _p, _i, _d, _z = C.c_void_p, C.c_int, C.c_double, C.c_size_t
 SQRT_DBL_MAX = float(np.sqrt(np.finfo(np.float64).max))
-
-
-def _ext5_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT5_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT5_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
 
 
 def _case(g, tag):
@@ -125,9 +108,9 @@ def test_tie_noise_equals_the_two_numpy_draws():
 def test_ext5_header_parses_at_1_0_and_cites_skimage():
     from xai_engine import _lib
     text = open(EXT5_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT5_DEFINES)
-    assert version == (1, 0) and (_lib.EXT5_VERSION, _lib.EXT5_MINOR) == (1, 0)
-    assert sorted(args) == _declared(EXT5_HEADER) == sorted(ENTRIES + ["xai_ext5_version", "xai_ext5_version_minor"])
+    args, ret, version = _lib.parse_header(text, _lib.LIBRARIES["ext5"].defines)
+    assert version == (1, 0) and (_lib.LIBRARIES["ext5"].version, _lib.LIBRARIES["ext5"].minor) == PINNED["ext5"] == (1, 0)
+    assert sorted(args) == declared(EXT5_HEADER) == sorted(ENTRIES + ["xai_ext5_version", "xai_ext5_version_minor"])
     assert args["xai_quickshift_lds_bytes"] == [_i, _d]
     assert args["xai_quickshift_density_f64"] == [_p, _p, _i, _i, _i, _i, _d, _p, _p]
     assert args["xai_quickshift_parent_f64"] == [_p, _p, _i, _i, _i, _i, _d, _d, _p, _p, _p, _p, _p]
@@ -146,47 +129,19 @@ def test_ext5_header_parses_at_1_0_and_cites_skimage():
 
 def test_ext5_library_exports_exactly_its_header_and_the_other_five_are_unchanged():
     from xai_engine import _lib
-    assert _exported(_ext5_path()) == _declared(EXT5_HEADER) == sorted(_lib.EXT5_SIGNATURES)
-    lib = _lib.load_ext5()
+    assert exported(built("ext5")) == declared(EXT5_HEADER) == sorted(_lib.LIBRARIES["ext5"].signatures)
+    lib = _lib.load("ext5")
     assert (lib.xai_ext5_version(), lib.xai_ext5_version_minor()) == (1, 0)
-    for other, sigs in ((_lib.LIB_PATH, _lib.SIGNATURES), (_lib.EXT_LIB_PATH, _lib.EXT_SIGNATURES), (_lib.EXT2_LIB_PATH, _lib.EXT2_SIGNATURES),
-                        (_lib.EXT3_LIB_PATH, _lib.EXT3_SIGNATURES), (_lib.EXT4_LIB_PATH, _lib.EXT4_SIGNATURES)):
-        assert _exported(other) == sorted(sigs), other
-        assert not [s for s in _exported(other) if s.startswith("xai_quickshift_") or "ext5" in s], other
-    assert (_lib.ABI_VERSION, _lib.ABI_MINOR, _lib.EXT_VERSION, _lib.EXT_MINOR, _lib.EXT2_VERSION, _lib.EXT2_MINOR, _lib.EXT3_VERSION,
-            _lib.EXT3_MINOR, _lib.EXT4_VERSION, _lib.EXT4_MINOR) == (1, 11, 1, 0, 1, 1, 1, 0, 1, 0)
-
-
-def test_load_ext5_refuses_an_absent_an_older_and_a_stale_library(tmp_path, monkeypatch):
-    from xai_engine import _lib
-    real = _ext5_path()
-    monkeypatch.setattr(_lib, "_ext5", None)
-    monkeypatch.setattr(_lib, "EXT5_LIB_PATH", str(tmp_path / "libxai_ext5.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load_ext5()
-    monkeypatch.setattr(_lib, "EXT5_LIB_PATH", real)
-    monkeypatch.setattr(_lib, "EXT5_MINOR", 1)                            # the package wants a later minor than the library has
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1"):
-        _lib.load_ext5()
-    monkeypatch.setattr(_lib, "EXT5_MINOR", 0)
-    monkeypatch.setattr(_lib, "EXT5_SIGNATURES", dict(_lib.EXT5_SIGNATURES, xai_quickshift_later_f64=[_p]))
-    monkeypatch.setattr(_lib, "_EXT5_RESTYPE", dict(_lib._EXT5_RESTYPE, xai_quickshift_later_f64=_i))
-    with pytest.raises(AttributeError):                                   # a prototype the built library does not have: stale
-        _lib.load_ext5()
-    assert _lib._ext5 is None
-
-
-def test_build_names_the_sixth_library():
-    import __graft_entry__ as g
-    src = inspect.getsource(g.build)
-    assert "load_ext5" in src and "libxai_ext5.so" in src
+    # each of the other six exports exactly its own header (exported_elsewhere), none of them an entry of this feature
+    assert not [(o, n) for o, n in exported_elsewhere("ext5") if n.startswith("xai_quickshift_") or "ext5" in n]
+    assert {k: (rec.version, rec.minor) for k, rec in _lib.LIBRARIES.items()} == PINNED
 
 
 # ------------------------------------------------------------------------------------------------ refusals, no device
 def test_k53_to_k55_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext5_path()
-    lib = _lib.load_ext5()
+    built("ext5")
+    lib = _lib.load("ext5")
     p = 16                               # a non-NULL, aligned pointer that is never dereferenced: validation comes first
     nan = float("nan")
 

@@ -5,14 +5,14 @@ import copy
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import sanity_restated as R
-from conftest import PKG, ROOT
+from abi_libs import PINNED, built, declared, exported
+from conftest import ROOT
 
 EXT2_HEADER = os.path.join(ROOT, "include", "xai_hip_ext2.h")
 NEW = ["xai_hog_f32", "xai_hog_workspace_bytes", "xai_rank_corr_f64", "xai_rank_corr_max_n", "xai_sanity_normalize_f32", "xai_ssim_f32",
@@ -20,30 +20,13 @@ NEW = ["xai_hog_f32", "xai_hog_workspace_bytes", "xai_rank_corr_f64", "xai_rank_
 _p, _i, _l, _f, _d, _z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 
-def _ext2_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT2_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT2_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
-
-
 # ------------------------------------------------------------------------------------------------ header and library
 def test_ext2_header_parses_at_minor_1_with_the_sanity_entries():
     from xai_engine import _lib
     text = open(EXT2_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT2_DEFINES)
-    assert version == (1, 1) and _lib.EXT2_MINOR == 1
-    assert set(NEW) <= set(args) and sorted(args) == _declared(EXT2_HEADER)
+    args, ret, version = _lib.parse_header(text, _lib.LIBRARIES["ext2"].defines)
+    assert version == (1, 1) == PINNED["ext2"] and _lib.LIBRARIES["ext2"].minor == 1
+    assert set(NEW) <= set(args) and sorted(args) == declared(EXT2_HEADER)
     assert args["xai_sanity_normalize_f32"] == [_p, _i, _l, _i, _p, _p]
     assert args["xai_ssim_f32"] == [_p, _p, _i, _i, _i] + [_d] * 6 + [_f, _f, _p, _p, _p, _z, _p]
     assert args["xai_tie_ranks_i32"] == [_p, _p, _i, _l, _p, _p]
@@ -62,16 +45,16 @@ def test_ext2_header_parses_at_minor_1_with_the_sanity_entries():
 
 def test_ext2_library_exports_exactly_the_declared_symbols():
     from xai_engine import _lib
-    assert _exported(_ext2_path()) == _declared(EXT2_HEADER) == sorted(_lib.EXT2_SIGNATURES)
-    lib = _lib.load_ext2()
+    assert exported(built("ext2")) == declared(EXT2_HEADER) == sorted(_lib.LIBRARIES["ext2"].signatures)
+    lib = _lib.load("ext2")
     assert (lib.xai_ext2_version(), lib.xai_ext2_version_minor()) == (1, 1)
     assert lib.xai_ssim_tile() >= 11 and lib.xai_tie_ranks_chunk() >= 64 and lib.xai_rank_corr_max_n() == 131072
 
 
 def test_the_five_kernels_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext2_path()
-    lib = _lib.load_ext2()
+    built("ext2")
+    lib = _lib.load("ext2")
     p = 16                               # a non-NULL pointer that is never dereferenced: validation comes first
 
     def norm(x=p, out=p, n=1, hw=64):

@@ -4,7 +4,6 @@ reference-made golden file (tests/golden/seg.npz), the fp32 thresholds of the MD
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,37 +11,21 @@ import pytest
 import torch
 
 import seg_restated as R
-from conftest import PKG, ROOT, load_golden
+from abi_libs import PINNED, built, declared, exported, exported_elsewhere
+from conftest import ROOT, load_golden
 
 EXT3_HEADER = os.path.join(ROOT, "include", "xai_hip_ext3.h")
 ENTRIES = ["xai_seg_counts_i32", "xai_seg_max_hw", "xai_seg_max_thresholds", "xai_seg_normalize_f32"]
 _p, _i, _l = C.c_void_p, C.c_int, C.c_int64
 
 
-def _ext3_path():
-    from xai_engine import _lib
-    if not os.path.exists(_lib.EXT3_LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return _lib.EXT3_LIB_PATH
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(xai_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exported(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("xai_"))
-
-
 # ------------------------------------------------------------------------------------------------ header and library
 def test_ext3_header_parses_at_1_0_and_cites_the_reference():
     from xai_engine import _lib
     text = open(EXT3_HEADER).read()
-    args, ret, version = _lib.parse_header(text, _lib.EXT3_DEFINES)
-    assert version == (1, 0) and (_lib.EXT3_VERSION, _lib.EXT3_MINOR) == (1, 0)
-    assert sorted(args) == _declared(EXT3_HEADER) == sorted(ENTRIES + ["xai_ext3_version", "xai_ext3_version_minor"])
+    args, ret, version = _lib.parse_header(text, _lib.LIBRARIES["ext3"].defines)
+    assert version == (1, 0) and (_lib.LIBRARIES["ext3"].version, _lib.LIBRARIES["ext3"].minor) == PINNED["ext3"] == (1, 0)
+    assert sorted(args) == declared(EXT3_HEADER) == sorted(ENTRIES + ["xai_ext3_version", "xai_ext3_version_minor"])
     assert args["xai_seg_normalize_f32"] == [_p, _i, _l, _p, _p, _p, _p]
     assert args["xai_seg_counts_i32"] == [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p]
     assert all(t is _i for t in ret.values())
@@ -58,40 +41,21 @@ def test_ext3_header_parses_at_1_0_and_cites_the_reference():
 
 def test_ext3_library_exports_exactly_its_header_and_the_others_gained_nothing():
     from xai_engine import _lib
-    assert _exported(_ext3_path()) == _declared(EXT3_HEADER) == sorted(_lib.EXT3_SIGNATURES)
-    lib = _lib.load_ext3()
+    assert exported(built("ext3")) == declared(EXT3_HEADER) == sorted(_lib.LIBRARIES["ext3"].signatures)
+    lib = _lib.load("ext3")
     assert (lib.xai_ext3_version(), lib.xai_ext3_version_minor()) == (1, 0)
     assert lib.xai_seg_max_thresholds() == 16 and lib.xai_seg_max_hw() == 1 << 30
     # no other library carries an entry of this feature.  (`xai_seg_`, not a bare "seg": XRAI's xai_segment_sums_f32 and MDA's
     # xai_mda_max_segments have been in libxai_hip.so and libxai_ext2.so all along, and those libraries may not change.)
-    for other in (_lib.LIB_PATH, _lib.EXT_LIB_PATH, _lib.EXT2_LIB_PATH):
-        assert not [s for s in _exported(other) if s.startswith("xai_seg_") or "ext3" in s], other
-        assert [s for s in _exported(other) if "seg" in s] in ([], ["xai_segment_sums_f32"], ["xai_mda_max_segments"]), other
-
-
-def test_load_ext3_refuses_an_absent_an_older_and_a_stale_library(tmp_path, monkeypatch):
-    from xai_engine import _lib
-    real = _ext3_path()
-    monkeypatch.setattr(_lib, "_ext3", None)
-    monkeypatch.setattr(_lib, "EXT3_LIB_PATH", str(tmp_path / "libxai_ext3.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load_ext3()
-    monkeypatch.setattr(_lib, "EXT3_LIB_PATH", real)
-    monkeypatch.setattr(_lib, "EXT3_MINOR", 1)                            # the package wants a later minor than the library has
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1"):
-        _lib.load_ext3()
-    monkeypatch.setattr(_lib, "EXT3_MINOR", 0)
-    monkeypatch.setattr(_lib, "EXT3_SIGNATURES", dict(_lib.EXT3_SIGNATURES, xai_seg_later_f32=[_p]))
-    monkeypatch.setattr(_lib, "_EXT3_RESTYPE", dict(_lib._EXT3_RESTYPE, xai_seg_later_f32=_i))
-    with pytest.raises(AttributeError):                                   # a prototype the built library does not have: stale
-        _lib.load_ext3()
-    assert _lib._ext3 is None
+    elsewhere = exported_elsewhere("ext3")
+    assert not [(o, n) for o, n in elsewhere if n.startswith("xai_seg_") or "ext3" in n]
+    assert [(o, n) for o, n in elsewhere if "seg" in n] == [("hip", "xai_segment_sums_f32"), ("ext2", "xai_mda_max_segments")]
 
 
 def test_k44_and_k45_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _ext3_path()
-    lib = _lib.load_ext3()
+    built("ext3")
+    lib = _lib.load("ext3")
     p = 16                               # a non-NULL pointer that is never dereferenced: validation comes first
 
     def norm(x=p, out=p, thr=p, stats=p, n=1, hw=64):

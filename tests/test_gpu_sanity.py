@@ -118,7 +118,7 @@ def test_k40_refuses_maps_below_the_window(K):
         K.ssim(x, x)
     ws = torch.empty(64, dtype=torch.uint8, device=DEV)
     out = torch.empty(1, dtype=torch.float64, device=DEV)
-    code = _lib.load_ext2().xai_ssim_f32(x.data_ptr(), x.data_ptr(), 1, 10, 40, *K.ssim_weights(), 1e-4, 1e-3, out.data_ptr(), None,
+    code = _lib.load("ext2").xai_ssim_f32(x.data_ptr(), x.data_ptr(), 1, 10, 40, *K.ssim_weights(), 1e-4, 1e-3, out.data_ptr(), None,
                                          ws.data_ptr(), 64, None)
     assert code == -2                                    # XAI_E_SHAPE, where skimage raises
 

@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI libraries: lib/libxai_hip.so (include/xai_hip.h, frozen at ABI 1.11) and the extension libraries
 lib/libxai_ext.so, libxai_ext2.so ... libxai_ext6.so (include/xai_hip_ext.h ... xai_hip_ext6.h), each holding the entry points
-added after the header before it was frozen or pinned.  LIBRARIES lists them, one Library record each; nothing else in Python does.
+added after the header before it was frozen or pinned.  LIBRARIES lists them, one Library record each; OPEN_LIBRARIES lists, in the
+same records, the libraries added since that table was pinned (lib/libxai_ext7.so, include/xai_hip_ext7.h); nothing else in Python does.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -138,14 +139,20 @@ LIBRARIES = {lib.key: lib for lib in (
     Library("ext5", "xai_hip_ext5.h", ("XAI_EXT5_VERSION", "XAI_EXT5_MINOR")),
     Library("ext6", "xai_hip_ext6.h", ("XAI_EXT6_VERSION", "XAI_EXT6_MINOR")),
 )}
+# The libraries added after the table above was pinned to its seven keys by tests (tests/test_cpu_abi_libs.py), which a feature may
+# not edit: the same records, the same loader.  A refactor that may touch those tests folds this table into LIBRARIES.
+OPEN_LIBRARIES = {lib.key: lib for lib in (
+    Library("ext7", "xai_hip_ext7.h", ("XAI_EXT7_VERSION", "XAI_EXT7_MINOR")),
+)}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
-    return LIBRARIES[key].load()
+    """The loaded handle of LIBRARIES[key] or OPEN_LIBRARIES[key] (cached by the record); raises, never falls back, when the file is
+    absent or refused."""
+    return (LIBRARIES[key] if key in LIBRARIES else OPEN_LIBRARIES[key]).load()
 
 
 def check(code, what):

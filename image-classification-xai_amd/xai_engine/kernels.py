@@ -1,7 +1,7 @@
 """Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
-Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES>)`.
+Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES or _lib.OPEN_LIBRARIES>)`.
 """
 import math
 
@@ -34,8 +34,8 @@ def _stream(dev):
 
 
 def _call(name, dev, *args, lib="hip"):
-    """Launch entry `name` of library `lib` (a key of _lib.LIBRARIES) on torch's current stream of `dev`; the error texts of every
-    library are the main one's xai_strerror."""
+    """Launch entry `name` of library `lib` (a key of _lib.LIBRARIES or _lib.OPEN_LIBRARIES) on torch's current stream of `dev`; the
+    error texts of every library are the main one's xai_strerror."""
     handle = _lib.load(lib)
     with torch.cuda.device(dev):
         _lib.check(getattr(handle, name)(*args, _stream(dev)), name)
@@ -1519,3 +1519,103 @@ def linkage_sort_relabel(n, ws, children, heights, info):
         raise ValueError(f"children, heights and info must hold {2 * (n - 1)}, {n - 1} and 4 elements")
     _call("xai_linkage_sort_relabel_i32", ws.device, n, _ptr(ws), ws.numel(), _ptr(children), _ptr(heights), _ptr(info), lib="ext6")
     return children, heights
+
+
+# ------------------------------------------------------------------------------ k-means (K58-K61; libxai_ext7.so)
+KMEANS_STATE_WORDS = 6                                       # state: iterations, done, status, 0, err (a double in words 4 and 5)
+KMEANS_OK, KMEANS_BAD_INDEX = 0, 1                           # state[2] (XAI_KMEANS_*)
+
+
+def kmeans_limits():
+    """(the most points, features, clusters) K58-K61 take (include/xai_hip_ext7.h, THE LIMITS)"""
+    lib = _lib.load("ext7")
+    return lib.xai_kmeans_max_points(), lib.xai_kmeans_max_features(), lib.xai_kmeans_max_clusters()
+
+
+def _kmeans_extents(points, k):
+    """points (n, d) fp32 contiguous on a HIP device and 1 <= k <= n inside THE LIMITS -> (n, d, k); the one check of every wrapper"""
+    if not isinstance(points, torch.Tensor):
+        raise TypeError(f"points: expected a torch.Tensor, got {type(points).__name__}")
+    if points.dtype != F32:
+        raise TypeError(f"points: expected {F32}, got {points.dtype}")
+    if points.dim() != 2 or points.shape[0] < 1 or points.shape[1] < 1:
+        raise ValueError(f"points must be (n, d) with n, d >= 1, got {tuple(points.shape)}")
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"n_clusters: expected an int, got {type(k).__name__}")
+    n, d = int(points.shape[0]), int(points.shape[1])
+    if not 1 <= k <= n:
+        raise ValueError(f"n_clusters must be in [1, n = {n}], got {k}")
+    cap = kmeans_limits()
+    if n > cap[0] or d > cap[1] or k > cap[2]:
+        raise ValueError(f"(n, d, k) = ({n}, {d}, {k}) is over THE LIMITS {cap} (include/xai_hip_ext7.h)")
+    if not points.is_contiguous():
+        raise ValueError("points must be contiguous")
+    _need(points, F32, "points")
+    return n, d, k
+
+
+def _kmeans_buffers(points, n, d, k, C, ws, state, assign=None, counts=None):
+    for t, dtype, name, numel in ((C, F32, "C", k * d), (state, I32, "state", KMEANS_STATE_WORDS), (assign, I32, "assign", n),
+                                  (counts, I32, "counts", k)):
+        if t is not None:
+            _need(t, dtype, name)
+            if t.numel() != numel or t.device != points.device:
+                raise ValueError(f"{name} must hold {numel} elements on the device of points")
+    _need(ws, U8, "ws")
+    if ws.device != points.device or ws.numel() < _lib.load("ext7").xai_kmeans_workspace_bytes(n, d, k):
+        raise ValueError("ws must be kmeans_workspace(points, k) on the device of points")
+
+
+def kmeans_workspace(points, k):
+    """The scratch of K58-K61 (e_j, xx_i, cc_j): uint8, xai_kmeans_workspace_bytes(n, d, k) bytes"""
+    n, d, k = _kmeans_extents(points, k)
+    return torch.empty(_lib.load("ext7").xai_kmeans_workspace_bytes(n, d, k), dtype=U8, device=points.device)
+
+
+def kmeans_init(points, first, C, ws, state):
+    """K58: xx_i into `ws`, C (k, d) = points[first], cc_j, state zeroed.  first (k,) int64 on the device of points."""
+    _need(first, I64, "first")
+    n, d, k = _kmeans_extents(points, int(first.numel()))
+    _kmeans_buffers(points, n, d, k, C, ws, state)
+    if first.device != points.device:
+        raise ValueError("first must be on the device of points")
+    _call("xai_kmeans_init_f32", points.device, _ptr(points), _ptr(first), n, d, k, _ptr(C), _ptr(ws), ws.numel(), _ptr(state), lib="ext7")
+    return C
+
+
+def kmeans_assign(points, C, assign, ws, state):
+    """K59: assign (n,) int32 = the first index of the maximal score against the centroids C (k, d); nothing when state[1] is set"""
+    n, d, k = _kmeans_extents(points, int(C.shape[0]) if isinstance(C, torch.Tensor) and C.dim() == 2 else 0)
+    _kmeans_buffers(points, n, d, k, C, ws, state, assign)
+    _call("xai_kmeans_assign_f32", points.device, _ptr(points), n, d, k, _ptr(C), _ptr(assign), _ptr(ws), ws.numel(), _ptr(state), lib="ext7")
+    return assign
+
+
+def _kmeans_stop(max_iter, tol):
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int):
+        raise TypeError(f"max_iter: expected an int, got {type(max_iter).__name__}")
+    if max_iter < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+    return max_iter, float(tol)
+
+
+def kmeans_update(points, C, assign, counts, ws, state, max_iter, tol):
+    """K60, K61: counts (k,) int32, C replaced by the new centroids, err, the iteration counter and `done` in state"""
+    n, d, k = _kmeans_extents(points, int(C.shape[0]) if isinstance(C, torch.Tensor) and C.dim() == 2 else 0)
+    _kmeans_buffers(points, n, d, k, C, ws, state, assign, counts)
+    max_iter, tol = _kmeans_stop(max_iter, tol)
+    _call("xai_kmeans_update_f32", points.device, _ptr(points), n, d, k, _ptr(C), _ptr(assign), _ptr(counts), _ptr(ws), ws.numel(),
+          _ptr(state), max_iter, tol, lib="ext7")
+    return C
+
+
+def kmeans_iterate(points, C, assign, counts, ws, state, max_iter, tol, iterations):
+    """`iterations` Lloyd iterations (K59, K60, K61 each) on the current stream, no read-back; those after the stop change nothing"""
+    n, d, k = _kmeans_extents(points, int(C.shape[0]) if isinstance(C, torch.Tensor) and C.dim() == 2 else 0)
+    _kmeans_buffers(points, n, d, k, C, ws, state, assign, counts)
+    max_iter, tol = _kmeans_stop(max_iter, tol)
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 1 <= iterations <= max_iter:
+        raise ValueError(f"iterations must be an int in [1, max_iter = {max_iter}], got {iterations!r}")
+    _call("xai_kmeans_iterate_f32", points.device, _ptr(points), n, d, k, _ptr(C), _ptr(assign), _ptr(counts), _ptr(ws), ws.numel(),
+          _ptr(state), max_iter, tol, iterations, lib="ext7")
+    return C

@@ -468,6 +468,25 @@ def run(device="cuda:0", verbose=True):
         lw[la], lw[:, la], lw[lb, lb] = float("inf"), float("inf"), float("inf")
         lids[lb] = ln + lk
     check("linkage_complete", float(not (lchildren.tolist() == lwant_c and torch.equal(torch.from_numpy(lheights), torch.stack(lwant_h).cpu()))), 0.0)
+    # k-means (K58-K61, libxai_ext7.so) against the same Lloyd steps in torch fp32 ops on the device, from the same initial points, on
+    # five separated clusters: the sums differ in order only, so the centroids agree to the bound the suite holds the torch loop to
+    from . import kmeans
+    kc = rnd(5, 16) * 10
+    kp = (kc[:, None] + 0.01 * rnd(5, 40, 16)).reshape(200, 16).contiguous()
+    kfirst = torch.tensor([3, 47, 88, 121, 190], device=dev)
+    kgot = kmeans.kmeans_device(kp, 5, first=kfirst)
+    kw = kp[kfirst].clone()
+    for _ in range(100):
+        ka = (2 * kp @ kw.T - (kp * kp).sum(1, keepdim=True) - (kw * kw).sum(1)[None]).argmax(1)
+        kone = torch.zeros(5, 200, device=dev)
+        kone[ka, torch.arange(200, device=dev)] = 1
+        knew = kone @ kp / kone.sum(-1)[:, None]
+        knew[knew != knew] = 0
+        kerr = (knew - kw).pow(2).sum()
+        kw = knew
+        if float(kerr) <= 1e-4:
+            break
+    check("kmeans_device", float((kgot - kw).abs().max()), 0.05)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

@@ -191,8 +191,11 @@ def vit_patch_map(input_tensor, target_class, testing_dict):
         sal = explainer.IG(x, target_class, device=dev)
     elif attr_function == "TIS":
         from .tis import TIS
-        # :236-239 (n_masks is the class default, 1024, in the reference; the key exists for models with fewer channels)
-        sal = TIS(model, n_masks=testing_dict.get("tis_n_masks", 1024), batch_size=64)(x, class_idx=target_class)[None]
+        # :236-239 (n_masks is the class default, 1024, in the reference; the key exists for models with fewer channels).
+        # testing_dict["tis_kmeans"] = "device" (not a reference key) runs the k-means on K58-K61 instead of the torch loop; TIS
+        # refuses any other value.
+        sal = TIS(model, n_masks=testing_dict.get("tis_n_masks", 1024), batch_size=64,
+                  kmeans=testing_dict.get("tis_kmeans", "torch"))(x, class_idx=target_class)[None]
     elif attr_function == "InFlow":
         # :240-242 passes option='b', which generate_RAVE does not take (a TypeError in the reference too): dropped here
         sal, _ = explainer.generate_RAVE(x, target_class, device=dev)

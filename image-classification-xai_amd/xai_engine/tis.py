@@ -9,6 +9,8 @@ the token-sampling hook on `model.pos_drop` (one batched gather instead of the r
 `fast_pytorch_kmeans` (the reference's k-means) is not vendored by the reference and not in its requirements.txt; the
 Lloyd iteration below restates its published algorithm with the initial centroids drawn from NumPy's global RNG like
 that library does -- parity unpinned.  `raw_masks=` lets a caller supply centroids from anywhere.
+`kmeans="device"` runs the same iteration on the HIP kernels K58-K61 in a stated arithmetic order (xai_engine/kmeans.py); the default,
+"torch", is the loop below.
 """
 import math
 
@@ -39,9 +41,15 @@ def kmeans_centroids(points, n_clusters, max_iter=100, tol=1e-4):
     return c
 
 
+KMEANS = ("torch", "device")        # who runs the Lloyd iteration: kmeans_centroids above, or kmeans.kmeans_device (K58-K61)
+
+
 class TIS:
     def __init__(self, model, n_masks=1024, batch_size=128, tokens_ratio=0.5, normalise=True, verbose=False,
-                 ablation_study=False, *, raw_masks=None):
+                 ablation_study=False, *, raw_masks=None, kmeans="torch"):
+        if kmeans not in KMEANS:
+            raise ValueError(f"kmeans must be one of {KMEANS}, got {kmeans!r}")
+        self.kmeans = kmeans
         self.model = model
         self.batch_size = batch_size
         self.n_masks = n_masks
@@ -81,6 +89,9 @@ class TIS:
     def generate_raw_masks(self, encoder_activations):
         """TIS.py:134-155: k-means over the activation channels (each a vector over the tokens)."""
         channels = encoder_activations.squeeze(0)[1:].T.contiguous().float()
+        if self.kmeans == "device":
+            from .kmeans import kmeans_device
+            return kmeans_device(channels, self.n_masks)
         return kmeans_centroids(channels, self.n_masks)
 
     def generate_binary_masks(self, raw_masks):

@@ -56,6 +56,30 @@ XAI_HD inline XaiBnLane xai_bn_lane_step(XaiBnLane s, int HW, int C) {
   return s;
 }
 
+// The image of flat element i: (i / HW) / C, the n of [N][C][HW] (the broadcast-gradient backward reads per-image operands).
+XAI_HD inline int xai_bn_image_first(int64_t i, int64_t n, int HW, int C) {
+  if (xai_bn_index32(n)) return static_cast<int>(static_cast<uint32_t>(i) / static_cast<uint32_t>(HW) / static_cast<uint32_t>(C));
+  return static_cast<int>(i / HW / C);
+}
+
+// The image of the element after one of image `image`, where `after` = xai_bn_lane_step(its position): a step that lands on
+// (r, c) = (0, 0) has entered the next image.
+XAI_HD inline int xai_bn_image_step(int image, XaiBnLane after) { return image + (after.r == 0 && after.c == 0 ? 1 : 0); }
+
+// ---- channel-major (CNHW) and strided operands of bnrelu_compact_kernels.hip
+// Where element (image, c, r) of an [N][C][HW] tensor sits in its [C][N][HW] (CNHW) twin.  N * C fits an int (the wrappers check).
+XAI_HD inline int64_t xai_bn_cnhw_index(int image, int c, int r, int N, int HW) {
+  return (static_cast<int64_t>(c) * N + image) * HW + r;
+}
+
+// Output extent of a kernel-1, pad-0 window at stride s over H positions: the positions 0, s, 2s, ... below H.
+XAI_HD inline int xai_bn_strided_extent(int H, int s) { return (H - 1) / s + 1; }
+
+// Flat index of side[n][c][ho * s][wo * s] in an [N][C][H][W] tensor: what output (ho, wo) of that window reads.
+XAI_HD inline int64_t xai_bn_strided_index(int n, int c, int ho, int wo, int C, int H, int W, int s) {
+  return ((static_cast<int64_t>(n) * C + c) * H + static_cast<int64_t>(ho) * s) * W + static_cast<int64_t>(wo) * s;
+}
+
 // HW >= 4: a lane's four elements touch at most two channels, s.c and the next one; elements k < xai_bn_lane_split(s, HW) are
 // in the first.
 XAI_HD inline int xai_bn_lane_split(XaiBnLane s, int HW) { return HW - s.r; }

@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI libraries: lib/libxai_hip.so (include/xai_hip.h, frozen at ABI 1.11) and the extension libraries
 lib/libxai_ext.so, libxai_ext2.so ... libxai_ext6.so (include/xai_hip_ext.h ... xai_hip_ext6.h), each holding the entry points
 added after the header before it was frozen or pinned.  LIBRARIES lists them, one Library record each; OPEN_LIBRARIES lists, in the
-same records, the libraries added since that table was pinned (lib/libxai_ext7.so, include/xai_hip_ext7.h); nothing else in Python does.
+same records, the library added since that table was pinned (lib/libxai_ext7.so, include/xai_hip_ext7.h) and LATER_LIBRARIES the ones
+since that one was (lib/libxai_compact.so, include/xai_hip_compact.h); nothing else in Python does.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -144,15 +145,25 @@ LIBRARIES = {lib.key: lib for lib in (
 OPEN_LIBRARIES = {lib.key: lib for lib in (
     Library("ext7", "xai_hip_ext7.h", ("XAI_EXT7_VERSION", "XAI_EXT7_MINOR")),
 )}
+# ... and the libraries added after OPEN_LIBRARIES was pinned to its one key in turn (tests/test_cpu_kmeans.py): lib/libxai_compact.so,
+# include/xai_hip_compact.h, the compact-layout BN/ReLU kernels.  No test names this table's keys, so the next library is a line here.
+LATER_LIBRARIES = {lib.key: lib for lib in (
+    Library("compact", "xai_hip_compact.h", ("XAI_COMPACT_VERSION", "XAI_COMPACT_MINOR")),
+)}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key] or OPEN_LIBRARIES[key] (cached by the record); raises, never falls back, when the file is
-    absent or refused."""
-    return (LIBRARIES[key] if key in LIBRARIES else OPEN_LIBRARIES[key]).load()
+    """The loaded handle of the record of `key` in LIBRARIES, OPEN_LIBRARIES or LATER_LIBRARIES (cached by the record); raises, never
+    falls back, when the file is absent or refused."""
+    return all_libraries()[key].load()
+
+
+def all_libraries():
+    """Every Library record by key, the three tables in the order their headers were written."""
+    return {**LIBRARIES, **OPEN_LIBRARIES, **LATER_LIBRARIES}
 
 
 def check(code, what):

@@ -12,6 +12,7 @@ import torch
 
 from . import kernels as K
 from ._lib import XaiHipError
+from .prepare import target_scores
 from .streams import GRAD_RTOL, LOGIT_RTOL, CapturedCall, ThreadGraphs, backward_turn, on_worker, run_passes
 
 
@@ -301,7 +302,9 @@ def _pass_grads(x, base, alphas, targets, model):
     """One classifier pass of k images x `steps` interpolants: K1, forward, every interpolant's target logit, backward
     -> (gradients (k * steps, C,H,W), logits (k * steps,)).  (`backward_turn` does nothing on a stream worker, where captures run.)"""
     flat = K.ig_interp(x, base, alphas).view((-1,) + tuple(x.shape[1:])).requires_grad_(True)
-    scores = _logits_of(model(flat)).gather(1, targets.repeat_interleave(alphas.shape[0]).unsqueeze(1)).squeeze(1)
+    per_row = targets.repeat_interleave(alphas.shape[0])
+    head = target_scores(model, flat, per_row)          # a fuse_bn_relu classifier: the head's backward rides in the last block's kernel
+    scores = head[0] if head is not None else _logits_of(model(flat)).gather(1, per_row.unsqueeze(1)).squeeze(1)
     with backward_turn(x.device):
         (g,) = torch.autograd.grad(scores, flat, grad_outputs=torch.ones_like(scores))
     return g.contiguous(), scores.detach()

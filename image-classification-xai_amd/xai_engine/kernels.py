@@ -538,6 +538,105 @@ def bn_relu_bwd_mask(gy, mask, weight, var, eps, variant, want_identity=False, g
     return gx, gid
 
 
+# ---- the same kernels on compact / channel-major operands (K62-K64, include/xai_hip_compact.h)
+def _strided(n, stride):
+    return (n - 1) // stride + 1
+
+
+def stride_gather_cnhw(side, stride):
+    """side (N,C,H,W) -> (C,N,Ho,Wo) = side[:, :, ::stride, ::stride].permute(1, 0, 2, 3), contiguous: the input of a kernel-1,
+    pad-0 convolution at `stride`, compact and channel-major (K62)."""
+    _need(side, F32, "side")
+    if side.dim() != 4 or int(stride) < 1:
+        raise ValueError("side must be (N, C, H, W) and stride >= 1")
+    N, Cc, H, W = side.shape
+    out = torch.empty((Cc, N, _strided(H, stride), _strided(W, stride)), dtype=F32, device=side.device)
+    _call("xai_stride_gather_cnhw_f32", side.device, _ptr(side), N, Cc, H, W, int(stride), _ptr(out), lib="compact")
+    return out
+
+
+def _cnhw_twin(t, like, name, like_name):
+    """`t` must hold `like`'s elements channel-major: (N,C,...) -> C*N*prod(...) elements, contiguous (any view of them)."""
+    _need(t, F32, name)
+    if t.numel() != like.numel():
+        raise ValueError(f"{name} must have the element count of {like_name}")
+
+
+def bn_relu_fwd_cnhw(x, identity_cnhw, weight, bias, mean, var, eps, variant, bn2=None, gated=True):
+    """-> (y, mask): bn_relu_fwd_mask with the identity operand in CNHW order, [C][N][HW] (K63); gated=False writes no mask
+    (-> (y, None), bn_act_fwd's result)."""
+    _need(x, F32, "x")
+    _need_bn(weight, bias, mean, var)
+    _cnhw_twin(identity_cnhw, x, "identity_cnhw", "x")
+    w2, b2, m2, v2, eps2 = _bn2_fwd(bn2)
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x[0, 0].numel()
+    mask = torch.empty(bn_gate_mask_bytes(x.numel()), dtype=torch.uint8, device=x.device) if gated else None
+    y = torch.empty_like(x)
+    _call("xai_bn_relu_fwd_cnhw_f32", x.device, _ptr(x), _ptr(identity_cnhw), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(var), float(eps),
+          _ptr(w2), _ptr(b2), _ptr(m2), _ptr(v2), float(eps2), int(variant), N, Cc, HW, _ptr(y), _ptr(mask), lib="compact")
+    return y, mask
+
+
+def _bwd_mask_common(numel, mask, weight, var, bn2, want_identity):
+    _need(mask, torch.uint8, "mask"); _need(weight, F32, "weight"); _need(var, F32, "var")
+    if mask.numel() < bn_gate_mask_bytes(numel):
+        raise ValueError(f"mask has {mask.numel()} bytes, needs {bn_gate_mask_bytes(numel)}")
+    return _bn2_bwd(bn2, want_identity)
+
+
+def bn_relu_bwd_compact(gy, mask, weight, var, eps, variant, want_identity=False, gy2=None, gy2_compact=None, stride=2, bn2=None,
+                        guided=False, identity_cnhw=False):
+    """bn_relu_bwd_mask (K64) with either of: `gy2_compact` (C,N,Ho,Wo) in place of the dense gy2 -- the input gradient of a
+    kernel-1 convolution at `stride`, added where stride divides (h, w), +0 added elsewhere; `identity_cnhw`: g_identity comes back
+    channel-major, shaped (1, C, N*H, W).  gy must be (N,C,H,W)."""
+    _need(gy, F32, "gy")
+    if gy.dim() != 4:
+        raise ValueError("gy must be (N, C, H, W)")
+    _shaped_like(gy2, gy, "gy2", "gy")
+    w2, v2, eps2, want_identity = _bwd_mask_common(gy.numel(), mask, weight, var, bn2, want_identity or identity_cnhw)
+    N, Cc, H, W = gy.shape
+    if gy2_compact is not None:
+        _need(gy2_compact, F32, "gy2_compact")
+        if gy2 is not None or gy2_compact.numel() != Cc * N * _strided(H, stride) * _strided(W, stride):
+            raise ValueError("gy2_compact must hold (C, N, Ho, Wo) elements of this stride, and excludes gy2")
+    gx = torch.empty_like(gy)
+    gid = None
+    if want_identity:
+        gid = torch.empty((1, Cc, N * H, W), dtype=F32, device=gy.device) if identity_cnhw else torch.empty_like(gy)
+    _call("xai_bn_relu_bwd_compact_f32", gy.device, _ptr(gy), _ptr(gy2), _ptr(gy2_compact), W, int(stride), _ptr(mask), _ptr(weight),
+          _ptr(var), float(eps), _ptr(w2), _ptr(v2), float(eps2), int(variant), int(bool(guided)), N, Cc, H * W, _ptr(gx), _ptr(gid),
+          int(bool(identity_cnhw)), lib="compact")
+    return gx, gid
+
+
+def bn_relu_bwd_bcast(grad_out, fc_weight, targets, shape, mask, weight, var, eps, variant, want_identity=False, gy2=None, bn2=None,
+                      guided=False, scale=None, divisor=0.0):
+    """bn_relu_bwd_mask (K64) of an activation of `shape` (N,C,H,W) whose gradient is the head's broadcast
+    gy[n][c][:] = (grad_out[n] * fc_weight[targets[n]][c]) * scale (default 1/HW rounded to fp32, PyTorch's mean backward), or
+    `/ divisor` where divisor != 0."""
+    _need(grad_out, F32, "grad_out"); _need(fc_weight, F32, "fc_weight"); _need(targets, torch.int64, "targets")
+    N, Cc = int(shape[0]), int(shape[1])
+    HW = 1
+    for v in shape[2:]:
+        HW *= int(v)
+    if grad_out.numel() != N or targets.numel() != N or fc_weight.dim() != 2 or fc_weight.shape[1] != Cc:
+        raise ValueError("grad_out and targets must hold N elements and fc_weight be (classes, C)")
+    if gy2 is not None:
+        _need(gy2, F32, "gy2")
+        if tuple(gy2.shape) != tuple(shape):
+            raise ValueError("gy2 must have the shape of the activation")
+    w2, v2, eps2, want_identity = _bwd_mask_common(N * Cc * HW, mask, weight, var, bn2, want_identity)
+    if scale is None:
+        scale = float(torch.tensor(1.0, dtype=F32) / torch.tensor(float(HW), dtype=F32))
+    gx = torch.empty(tuple(shape), dtype=F32, device=grad_out.device)
+    gid = torch.empty_like(gx) if want_identity else None
+    _call("xai_bn_relu_bwd_bcast_f32", grad_out.device, _ptr(grad_out), _ptr(fc_weight), _ptr(targets), int(fc_weight.shape[0]),
+          float(scale), float(divisor), _ptr(gy2), _ptr(mask), _ptr(weight), _ptr(var), float(eps), _ptr(w2), _ptr(v2), float(eps2),
+          int(variant), int(bool(guided)), N, Cc, HW, _ptr(gx), _ptr(gid), lib="compact")
+    return gx, gid
+
+
 def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, stride, pad):
     """-> (y, code): max_pool2d(relu(bn(x)), kernel, stride, pad) and one uint8 per pooled output for bn_relu_maxpool_bwd (the
     window-local arg-max, or 255 for a closed ReLU gate); x (N,C,H,W) -> (N,C,PH,PW) twice."""

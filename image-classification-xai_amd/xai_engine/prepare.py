@@ -120,6 +120,32 @@ def _guided_relu_fn():
     return _GUIDED_RELU_FN
 
 
+class _Link:
+    """What a consumer of a fused site's output hands back to that site's backward beside autograd, which checks gradient shapes:
+    `compact` = (tensor (C,N,Ho,Wo), stride), the input gradient of a strided 1x1 shortcut convolution that ran on the compact
+    tensor; `head` = (grad_out, fc_weight, targets, scale, divisor), the broadcast gradient of a pool + Linear head.  Made by the
+    forward of the producing site, one per call, and rides on its output as `._xai_link`; a consumer's backward fills it and
+    returns None for that input, and the producer's backward, which autograd runs after all its consumers', takes it."""
+    __slots__ = ("compact", "head", "accepts_head")
+
+    def __init__(self, accepts_head=True):
+        self.compact = self.head = None
+        self.accepts_head = accepts_head          # the kernel has no broadcast form with a channel-major g_identity
+
+    def take(self):
+        got = (self.compact, self.head)
+        self.compact = self.head = None
+        return got
+
+
+def _dense_of(compact, stride, shape):
+    """the dense, zero-filled gradient (N,C,H,W) that a compact one (C,N,Ho,Wo) stands for"""
+    import torch
+    dense = torch.zeros(shape, dtype=compact.dtype, device=compact.device)
+    dense[:, :, ::stride, ::stride] = compact.permute(1, 0, 2, 3)
+    return dense
+
+
 def _make_function():
     import torch
     from . import kernels as K
@@ -127,12 +153,18 @@ def _make_function():
     class BnReluFunction(torch.autograd.Function):
         """relu(bn(x) [+ identity]).  With `fork` the output is returned twice, as two tensors on one storage: a residual
         block hands the first to its successor's convolution and the second to its identity path, and backward receives
-        their gradients separately and sums them inside the kernel -- otherwise autograd adds them in a kernel of its own."""
+        their gradients separately and sums them inside the kernel -- otherwise autograd adds them in a kernel of its own.
+        `identity_cnhw`: the identity operand is channel-major, (1, C, N*H, W), and so is its gradient (a compact shortcut).
+        `link` (a _Link or None): gradients that reach this site outside autograd."""
 
         @staticmethod
-        def forward(ctx, x, identity, w, b, mean, var, eps, fork, bn2, gated, guided):
+        def forward(ctx, x, identity, w, b, mean, var, eps, fork, bn2, gated, guided, link=None, identity_cnhw=False):
             x, identity = x.contiguous(), None if identity is None else identity.contiguous()
-            if gated:
+            if identity_cnhw:
+                y, mask = K.bn_relu_fwd_cnhw(x, identity, w, b, mean, var, eps, BN_VARIANT, bn2=bn2, gated=gated)
+                if gated:
+                    ctx.save_for_backward(mask, w, var)
+            elif gated:
                 # a gradient will be taken: the forward also writes the ReLU gates, one bit per element, and the backward
                 # reads them instead of y (torch.empty inside: the mask lives in a capturing graph's pool like y does)
                 y, mask = K.bn_relu_fwd_mask(x, identity, w, b, mean, var, eps, BN_VARIANT, bn2=bn2)
@@ -141,6 +173,7 @@ def _make_function():
                 y = K.bn_act_fwd(x, identity, w, b, mean, var, eps, BN_VARIANT, relu=True, bn2=bn2)
             ctx.eps, ctx.has_identity, ctx.guided = eps, identity is not None, bool(guided)
             ctx.bn2 = None if bn2 is None else (bn2[0], bn2[3], bn2[4])          # weight2, var2, eps2
+            ctx.link, ctx.identity_cnhw, ctx.shape = link, bool(identity_cnhw), tuple(x.shape)
             ctx.set_materialize_grads(False)
             return (y, y.detach()) if fork else y
 
@@ -148,11 +181,29 @@ def _make_function():
         def backward(ctx, *grads):
             mask, w, var = ctx.saved_tensors
             live = [g.contiguous() for g in grads if g is not None]
-            if not live:
-                return (None,) * 11
-            gx, gid = K.bn_relu_bwd_mask(live[0], mask, w, var, ctx.eps, BN_VARIANT, want_identity=ctx.has_identity,
-                                         gy2=live[1] if len(live) > 1 else None, bn2=ctx.bn2, guided=ctx.guided)
-            return (gx, gid) + (None,) * 9
+            compact, head = ctx.link.take() if ctx.link is not None else (None, None)
+            if compact is not None and (len(live) != 1 or head is not None):
+                live, compact = live + [_dense_of(*compact, ctx.shape)], None     # no operand slot left: as the dense tensor
+            while len(live) > (1 if head is not None else 2):
+                live = live[:-2] + [live[-2] + live[-1]]
+            nones = (None,) * 11
+            if head is not None:                          # (a _Link of a channel-major site does not accept one)
+                grad_out, fc_weight, targets, scale, divisor = head
+                gx, gid = K.bn_relu_bwd_bcast(grad_out, fc_weight, targets, ctx.shape, mask, w, var, ctx.eps, BN_VARIANT,
+                                              want_identity=ctx.has_identity, gy2=live[0] if live else None, bn2=ctx.bn2,
+                                              guided=ctx.guided, scale=scale, divisor=divisor)
+            elif not live:
+                return (None,) * 13
+            elif compact is not None or ctx.identity_cnhw:
+                gx, gid = K.bn_relu_bwd_compact(live[0], mask, w, var, ctx.eps, BN_VARIANT, want_identity=ctx.has_identity,
+                                                gy2=live[1] if len(live) > 1 else None,
+                                                gy2_compact=None if compact is None else compact[0],
+                                                stride=1 if compact is None else compact[1], bn2=ctx.bn2, guided=ctx.guided,
+                                                identity_cnhw=ctx.identity_cnhw)
+            else:
+                gx, gid = K.bn_relu_bwd_mask(live[0], mask, w, var, ctx.eps, BN_VARIANT, want_identity=ctx.has_identity,
+                                             gy2=live[1] if len(live) > 1 else None, bn2=ctx.bn2, guided=ctx.guided)
+            return (gx, gid) + nones
     return BnReluFunction
 
 
@@ -170,13 +221,19 @@ def _eager(x, bn, identity, identity_bn=None):
     return F.relu(out)
 
 
-def _check_site(x, bn, identity, fused_fn, fork, identity_bn=None):
-    """Fused vs PyTorch kernels on the tensors of this call site: forward and all gradients must be bit-identical."""
+def _check_site(x, bn, identity, fused_fn, fork, identity_bn=None, identity_cnhw=False):
+    """Fused vs PyTorch kernels on the tensors of this call site: forward and all gradients must be bit-identical.
+    identity_cnhw: `identity` is channel-major, (1, C, N*H, W) -- the PyTorch kernels get its NCHW permutation, and the two
+    identity gradients are compared across the same permutation.  At a fork site the second gradient is also given the way a
+    stride-2 shortcut delivers it, compact through the link, against the dense zero-filled tensor it stands for."""
     import torch
+
+    def nchw(t):
+        return t.view(x.shape[1], x.shape[0], x.shape[2], x.shape[3]).permute(1, 0, 2, 3).contiguous() if identity_cnhw else t
     xa, xb = x.detach().clone().requires_grad_(True), x.detach().clone().requires_grad_(True)
     ia = ib = None
     if identity is not None:
-        ia, ib = identity.detach().clone().requires_grad_(True), identity.detach().clone().requires_grad_(True)
+        ia, ib = nchw(identity.detach()).clone().requires_grad_(True), identity.detach().clone().requires_grad_(True)
     with torch.enable_grad():
         ya, yb = _eager(xa, bn, ia, identity_bn), fused_fn(xb, ib)
         g1, g2 = torch.randn_like(ya), torch.randn_like(ya)
@@ -186,9 +243,18 @@ def _check_site(x, bn, identity, fused_fn, fork, identity_bn=None):
         else:
             ga = torch.autograd.grad(ya, [xa] + ([ia] if ia is not None else []), g1)
             gb = torch.autograd.grad(yb, [xb] + ([ib] if ib is not None else []), g1)
-    if not (torch.equal(ya, yb) and all(torch.equal(p, q) for p, q in zip(ga, gb))):
+        same = torch.equal(ya, yb) and all(torch.equal(p, nchw(q) if k else q) for k, (p, q) in enumerate(zip(ga, gb)))
+        if same and fork:
+            gc = torch.randn((x.shape[1], x.shape[0], (x.shape[2] + 1) // 2, (x.shape[3] + 1) // 2), device=x.device)
+            ya, yb = _eager(xa, bn, ia, identity_bn), fused_fn(xb, ib)
+            ga = torch.autograd.grad([ya, ya], [xa] + ([ia] if ia is not None else []), [g1, _dense_of(gc, 2, tuple(ya.shape))])
+            yb._xai_link.compact = (gc, 2)
+            gb = torch.autograd.grad(yb, [xb] + ([ib] if ib is not None else []), g1)
+            same = all(torch.equal(p, nchw(q) if k else q) for k, (p, q) in enumerate(zip(ga, gb)))
+    if not same:
         raise ValueError(f"fuse_bn_relu: fused BN+ReLU differs from the PyTorch kernels for input {tuple(x.shape)}"
-                         f"{' + identity' if identity is not None else ''} (forward equal: {torch.equal(ya, yb)})")
+                         f"{' + identity' if identity is not None else ''}{' (channel-major)' if identity_cnhw else ''}"
+                         f" (forward equal: {torch.equal(ya, yb)})")
     _CHECK["sites"] += 1
 
 
@@ -199,19 +265,24 @@ def _bn_usable(bn, x):
             and not (bn.bias is not None and bn.bias.requires_grad))
 
 
-def bn_relu(x, bn, identity=None, fork=False, identity_bn=None):
+def bn_relu(x, bn, identity=None, fork=False, identity_bn=None, identity_cnhw=False):
     """relu(bn(x) [+ identity]) through the fused kernels; falls back to the PyTorch modules whenever the fused form does
     not apply (training mode, trainable BN parameters, no running statistics, non-fp32 or non-HIP tensors).
     identity_bn: the identity operand is a raw convolution output and gets this BatchNorm2d inside the same kernel (the
     down-sample branch of a residual block).
     fork=True (block outputs): the result carries a second tensor on the same storage as `._xai_alias`; a following fused
     block routes its identity path through it so that the two gradients of the residual join reach the backward kernel
-    separately (see BnReluFunction).  Anything else just uses the result as an ordinary tensor."""
+    separately (see BnReluFunction).  Anything else just uses the result as an ordinary tensor.
+    identity_cnhw: the identity operand is channel-major, (1, C, N*H, W), as `_compact_shortcut` made it (the caller has checked
+    that this site is usable: there is no PyTorch form to fall back to).
+    A result that a gradient will flow through also carries `._xai_link`, and so does its alias: see _Link."""
     global _FN
     import torch
-    usable = (_bn_usable(bn, x) and (identity is None or identity.shape == x.shape)
+    usable = (_bn_usable(bn, x) and (identity is None or identity.shape == x.shape or identity_cnhw)
               and (identity_bn is None or (identity is not None and _bn_usable(identity_bn, identity))))
     if not usable:
+        if identity_cnhw:
+            raise RuntimeError("bn_relu: a channel-major identity at a site the fused kernels do not cover")
         return _eager(x, bn, identity, identity_bn)
     if _FN is None:
         _FN = _make_function()
@@ -223,32 +294,203 @@ def bn_relu(x, bn, identity=None, fork=False, identity_bn=None):
         # forward-only calls (grad mode off, or nothing upstream wants a gradient) write no gate mask
         gated = torch.is_grad_enabled() and (xx.requires_grad or (ii is not None and ii.requires_grad))
         guided = guided_active()                     # read here, in the forward: BnReluFunction keeps it for its backward
+        link = _Link(accepts_head=not identity_cnhw) if gated else None
         if not forked:
-            return _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), False, bn2, gated, guided)
-        y, alias = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), True, bn2, gated, guided)
-        y._xai_alias = alias
+            y = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), False, bn2, gated, guided, link, identity_cnhw)
+        else:
+            y, alias = _FN.apply(xx, ii, w, b, mean, var, float(bn.eps), True, bn2, gated, guided, link, identity_cnhw)
+            y._xai_alias = alias
+            alias._xai_link = link
+        y._xai_link = link
         return y
     if _CHECK["on"]:
-        _check_site(x, bn, identity, (lambda xx, ii: fused_fn(xx, ii, fork)), fork, identity_bn)
+        _check_site(x, bn, identity, (lambda xx, ii: fused_fn(xx, ii, fork)), fork, identity_bn, identity_cnhw)
     return fused_fn(x, identity)
+
+
+# ------------------------------------------------------------------------------ strided 1x1 shortcuts on compact tensors; the head
+# How many shortcut and head sites (a site = one module at one running shape under one pair of solver switches) run in the new
+# forms, how many the bitwise proof refused, and why; `site_report()` says it in a sentence.
+SITE_COUNTS = {"shortcut_compact": 0, "shortcut_refused": 0, "head_broadcast": 0, "head_refused": 0, "reasons": []}
+_PROOF_LOCK = threading.RLock()
+_INPUT_ONLY = threading.local()      # .on while target_scores builds the forward on this thread
+_PROVEN = {}                 # key -> the accepted candidate, or None once refused (for good)
+
+
+def site_report():
+    c = SITE_COUNTS
+    text = (f"{c['shortcut_compact']} strided 1x1 shortcut site(s) on compact channel-major tensors, {c['shortcut_refused']} refused; "
+            f"{c['head_broadcast']} pool+Linear head backward(s) as a broadcast operand, {c['head_refused']} refused")
+    return text + ("" if not c["reasons"] else " (" + "; ".join(c["reasons"]) + ")")
+
+
+def _refuse(kind, why):
+    import warnings
+    SITE_COUNTS[kind] += 1
+    SITE_COUNTS["reasons"].append(why)
+    warnings.warn("fuse_bn_relu: " + why + "; this site keeps the PyTorch / MIOpen call")
+
+
+def _bits_equal(a, b):
+    import torch
+    return a.shape == b.shape and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
+
+
+def _solver_key():
+    import torch
+    return bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark)
+
+
+def _proven(key, prove, kind, why):
+    """The decision for `key`, made once per process under the lock by `prove()` (-> a candidate or None) on the first eager call;
+    inside a stream capture nothing is decided and None is returned, so the caller takes the PyTorch / MIOpen form there."""
+    import torch
+    with _PROOF_LOCK:
+        if key not in _PROVEN:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            _PROVEN[key] = prove()
+            if _PROVEN[key] is None:
+                _refuse(kind + "_refused", why)
+            else:
+                SITE_COUNTS["shortcut_compact" if kind == "shortcut" else "head_broadcast"] += 1
+        return _PROVEN[key]
+
+
+def _conv_on_view(xv, conv):
+    """the convolution at stride 1 on the (1, Cin, N*Ho, Wo) view of the compact tensor: batch 1, so NCHW is CNHW and MIOpen runs
+    its GEMM without a layout kernel around it"""
+    import torch.nn.functional as F
+    return F.conv2d(xv, conv.weight, conv.bias)
+
+
+def _mm_on_view(xv, conv):
+    import torch
+    out = torch.mm(conv.weight.view(conv.weight.shape[0], -1), xv.view(xv.shape[1], -1))
+    if conv.bias is not None:
+        out = out + conv.bias[:, None]
+    return out.view(1, -1, xv.shape[2], xv.shape[3])
+
+
+# (name, f(xv, conv) -> (1, Cout, N*Ho, Wo)) in differentiable torch ops.  rocBLAS picks its kernel, and with it the order of every
+# sum, by shape, so none is assumed: per site the first one that reproduces MIOpen's strided call bit for bit, forward and
+# backward-data, is kept (DESIGN 5a has what the benchmark's shapes gave).
+_SHORTCUT_CANDIDATES = [("conv2d on the (1, Cin, N*Ho, Wo) view", _conv_on_view), ("mm(W, Xc)", _mm_on_view)]
+
+
+def _prove_shortcut(conv, side, stride):
+    """-> the first candidate whose forward and backward-data on the compact tensor are MIOpen's strided results bit for bit (the
+    rest of MIOpen's input gradient being +0), or None"""
+    import torch
+    from . import kernels as K
+    with torch.enable_grad():
+        dense_in = side.detach().clone().requires_grad_(True)
+        ref = conv(dense_in)
+        gy = torch.randn_like(ref)
+        (gref,) = torch.autograd.grad(ref, dense_in, gy)
+        N, Cout, Ho, Wo = ref.shape
+        want = ref.detach().permute(1, 0, 2, 3).contiguous().view(1, Cout, N * Ho, Wo)
+        gyc = gy.permute(1, 0, 2, 3).contiguous().view(1, Cout, N * Ho, Wo)
+        want_g = gref[:, :, ::stride, ::stride].permute(1, 0, 2, 3).contiguous()
+        if not _bits_equal(_dense_of(want_g, stride, tuple(gref.shape)), gref):
+            return None
+        xc = K.stride_gather_cnhw(side.detach().contiguous(), stride)
+        for cand in list(_SHORTCUT_CANDIDATES):
+            xv = xc.view(1, xc.shape[0], N * Ho, Wo).clone().requires_grad_(True)
+            got = cand[1](xv, conv)
+            if not _bits_equal(got.detach(), want):
+                continue
+            (gv,) = torch.autograd.grad(got, xv, gyc)
+            if _bits_equal(gv.view(want_g.shape), want_g):
+                return cand
+    return None
+
+
+_GATHER_FN = None
+
+
+def _gather_function():
+    global _GATHER_FN
+    if _GATHER_FN is None:
+        import torch
+        from . import kernels as K
+
+        class ShortcutGather(torch.autograd.Function):
+            """side (N,C,H,W) -> its strided positions, compact and channel-major, viewed (1, C, N*Ho, Wo).  The gradient of that
+            view is compact too: it goes to `link`, the producing site's, and `side` gets None (see _Link)."""
+
+            @staticmethod
+            def forward(ctx, side, link, stride):
+                ctx.link, ctx.stride = link, stride
+                ctx.set_materialize_grads(False)
+                xc = K.stride_gather_cnhw(side.contiguous(), stride)
+                return xc.view(1, xc.shape[0], xc.shape[1] * xc.shape[2], xc.shape[3])
+
+            @staticmethod
+            def backward(ctx, g):
+                if g is not None:
+                    ctx.link.compact = (g.contiguous(), ctx.stride)
+                return None, None, None
+        _GATHER_FN = ShortcutGather
+    return _GATHER_FN
+
+
+def _compact_shortcut(conv, side):
+    """conv(side) for a strided 1x1 convolution as a channel-major tensor (1, Cout, N*Ho, Wo), computed on the compact input, or
+    None where that form does not apply or has not proven itself: then the caller runs the module.  Only under deterministic
+    solvers; a site is proven on its first eager call (never inside a stream capture), process-wide and for good."""
+    import torch
+    import torch.nn as nn
+    from . import kernels as K
+    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride[0] == conv.stride[1] > 1 and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and not conv.weight.requires_grad
+            and (conv.bias is None or not conv.bias.requires_grad) and conv.weight.dtype == torch.float32
+            and not conv._forward_hooks and not conv._forward_pre_hooks and not conv._backward_hooks and not conv._backward_pre_hooks
+            and side.is_cuda and side.dtype == torch.float32 and side.dim() == 4 and torch.backends.cudnn.deterministic):
+        return None
+    s = conv.stride[0]
+    needs_grad = torch.is_grad_enabled() and side.requires_grad
+    link = getattr(side, "_xai_link", None)
+    # With a gradient to come, the compact one reaches the site behind `side` through its link and `side` itself gets None from
+    # autograd: only for a caller that differentiates with respect to the network input alone (target_scores says so; Grad-CAM on
+    # an inner layer reads the gradient of a block output and its alias), and only with such a site behind `side`.
+    if needs_grad and (link is None or not getattr(_INPUT_ONLY, "on", False)):
+        return None
+    key = ("shortcut", tuple(conv.weight.shape), conv.bias is not None, tuple(side.shape), s, str(side.device)) + _solver_key()
+    cand = _proven(key, lambda: _prove_shortcut(conv, side, s), "shortcut",
+                   f"no compact form of the stride-{s} 1x1 convolution {tuple(conv.weight.shape[:2])} on input {tuple(side.shape)} "
+                   "reproduces MIOpen's result bit for bit")
+    if cand is None:
+        return None
+    if needs_grad:
+        xv = _gather_function().apply(side, link, s)
+    else:
+        xc = K.stride_gather_cnhw(side.detach().contiguous(), s)
+        xv = xc.view(1, xc.shape[0], xc.shape[1] * xc.shape[2], xc.shape[3])
+    return cand[1](xv, conv)
 
 
 def _fused_block_forward(self, x):
     import torch.nn as nn
     side = getattr(x, "_xai_alias", x)              # the previous fused block's second handle on its output, if any
-    identity, identity_bn = side, None
+    identity, identity_bn, cnhw = side, None, False
     ds = self.downsample
+    last_bn = self.bn3 if hasattr(self, "conv3") else self.bn2
     if ds is not None:
         if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and isinstance(ds[1], nn.BatchNorm2d):
-            identity, identity_bn = ds[0](side), ds[1]          # conv here, its BatchNorm inside the residual kernel
+            identity_bn = ds[1]                                 # conv here, its BatchNorm inside the residual kernel
+            compact = None
+            if _bn_usable(last_bn, side) and _bn_usable(ds[1], side):
+                compact = _compact_shortcut(ds[0], side)        # a strided 1x1 convolution: on the compact tensor, channel-major
+            identity, cnhw = (ds[0](side), False) if compact is None else (compact, True)
         else:
             identity = ds(side)
     out = bn_relu(self.conv1(x), self.bn1)
     fork = getattr(self, "_xai_fork", False)
     if hasattr(self, "conv3"):                      # bottleneck
         out = bn_relu(self.conv2(out), self.bn2)
-        return bn_relu(self.conv3(out), self.bn3, identity, fork=fork, identity_bn=identity_bn)
-    return bn_relu(self.conv2(out), self.bn2, identity, fork=fork, identity_bn=identity_bn)     # basic block
+        return bn_relu(self.conv3(out), self.bn3, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)
+    return bn_relu(self.conv2(out), self.bn2, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)     # basic block
 
 
 _POOL_FN = None
@@ -400,8 +642,114 @@ def stem_autograd(x, bn, pool, fork=False):
     return fused_fn(x, fork)
 
 
-def _fused_resnet_forward(self, x):
+# (name, HW -> (scale, divisor)) of the head's broadcast gradient: mean's backward in PyTorch multiplies by the fp32 reciprocal
+_HEAD_CANDIDATES = [("(grad_out * W[t]) * (1 / HW)", lambda hw: (_fp32_reciprocal(hw), 0.0)),
+                    ("(grad_out * W[t]) / HW", lambda hw: (1.0, float(hw)))]
+_HEAD_FN = None
+
+
+def _fp32_reciprocal(hw):
     import torch
+    return float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(hw), dtype=torch.float32))
+
+
+def _torch_head(model, feat):
+    import torch
+    return model.fc(torch.flatten(model.avgpool(feat), 1))
+
+
+def _prove_head(model, feat, targets):
+    """-> the first candidate whose broadcast gradient, as the kernel forms it, is what PyTorch's head backward hands to the last
+    block for these features and targets, bit for bit (a grad_out that is not ones; every gate open so that g_identity is gy)"""
+    import torch
+    from . import kernels as K
+    N, C = feat.shape[0], feat.shape[1]
+    with torch.enable_grad():
+        f = feat.detach().clone().requires_grad_(True)
+        scores = _torch_head(model, f).gather(1, targets.unsqueeze(1)).squeeze(1)
+        grad_out = torch.randn_like(scores) * 3.0
+        (want,) = torch.autograd.grad(scores, f, grad_out)
+    ones = torch.ones(C, device=feat.device)
+    mask = torch.full((K.bn_gate_mask_bytes(feat.numel()),), 0xFF, dtype=torch.uint8, device=feat.device)
+    hw = feat[0, 0].numel()
+    for cand in list(_HEAD_CANDIDATES):
+        scale, divisor = cand[1](hw)
+        _, got = K.bn_relu_bwd_bcast(grad_out, model.fc.weight.detach(), targets, tuple(feat.shape), mask, ones, ones, 0.0, BN_VARIANT,
+                                     want_identity=True, scale=scale, divisor=divisor)
+        if _bits_equal(got, want.contiguous()):
+            return cand
+    return None
+
+
+def _head_applies(model, feat, targets):
+    import torch
+    import torch.nn as nn
+    pool, fc = getattr(model, "avgpool", None), getattr(model, "fc", None)
+    return (isinstance(pool, nn.AdaptiveAvgPool2d) and pool.output_size in (1, (1, 1)) and isinstance(fc, nn.Linear)
+            and not fc.weight.requires_grad and (fc.bias is None or not fc.bias.requires_grad) and fc.weight.dtype == torch.float32
+            and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 4 and feat.shape[1] == fc.in_features
+            and torch.is_tensor(targets) and targets.dtype == torch.int64 and targets.device == feat.device
+            and tuple(targets.shape) == (feat.shape[0],))
+
+
+def _proven_head(model, feat, targets):
+    key = ("head", tuple(model.fc.weight.shape), tuple(feat.shape), str(feat.device)) + _solver_key()
+    return _proven(key, lambda: _prove_head(model, feat, targets), "head",
+                   f"no broadcast form reproduces PyTorch's pool + Linear backward for features {tuple(feat.shape)} bit for bit")
+
+
+def target_scores(model, x, targets):
+    """(scores, logits) with scores[n] = logits[n][targets[n]] for a `fuse_bn_relu` classifier, for callers that differentiate the
+    scores with respect to `x` ONLY: the head's forward is PyTorch's (avgpool, flatten, fc, gather: the same bits), its backward
+    launches nothing -- the last block's backward kernel forms the gradient it would have delivered from grad_out, the Linear's
+    weight and the targets (_Link).  None where the call does not apply (not such a classifier, a hook on any module of the
+    network, no gradient wanted): the caller then runs the model and selects as before.  Where only the head's new form does not
+    apply (targets not (N,) int64 on the device, a head that is not AdaptiveAvgPool2d(1) + Linear, a last block that is not a
+    fused site or is a channel-major one, a proof that was refused) the head runs in PyTorch's ops on the same features and the
+    pair is returned all the same.  Gradients with respect to block outputs are NOT delivered through this path (the head's and
+    the strided shortcuts' travel beside autograd; a tensor hook on a block output is not seen here either); a plain call of the
+    model keeps delivering them."""
+    global _HEAD_FN
+    import torch
+    if not (getattr(model, "_xai_features", None) is not None and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad):
+        return None
+    # a hook anywhere in the network may read (or take the gradient of) a block output, and the head's modules are called here
+    # without the network's own __call__: with any module hook registered the caller runs the model as before
+    if any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks for m in model.modules()):
+        return None
+    before = getattr(_INPUT_ONLY, "on", False)
+    _INPUT_ONLY.on = True
+    try:
+        feat = model._xai_features(x)
+    finally:
+        _INPUT_ONLY.on = before
+    link = getattr(feat, "_xai_link", None)
+    cand = None
+    if link is not None and link.accepts_head and _head_applies(model, feat, targets):
+        cand = _proven_head(model, feat, targets)
+    if cand is None:                                      # today's ops on the features already computed
+        logits = _torch_head(model, feat)
+        return logits.gather(1, targets.unsqueeze(1)).squeeze(1), logits
+    if _HEAD_FN is None:
+        class HeadFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, feat_, targets_, link_, model_, operand):
+                logits = _torch_head(model_, feat_)
+                ctx.link, ctx.targets, ctx.weight, ctx.operand = link_, targets_, model_.fc.weight.detach(), operand
+                ctx.set_materialize_grads(False)
+                ctx.mark_non_differentiable(logits)
+                return logits.gather(1, targets_.unsqueeze(1)).squeeze(1), logits
+
+            @staticmethod
+            def backward(ctx, g, _g_logits=None):
+                if g is not None:
+                    ctx.link.head = (g.contiguous(), ctx.weight, ctx.targets, *ctx.operand)
+                return None, None, None, None, None
+        _HEAD_FN = HeadFunction
+    return _HEAD_FN.apply(feat, targets.contiguous(), link, model, cand[1](feat[0, 0].numel()))
+
+
+def _fused_resnet_features(self, x):
     stem = self.conv1(x)
     pooled = stem_inference(stem, self.bn1, self.maxpool)
     if pooled is None or _CHECK["on"]:                    # (a verification pass walks every form of the stem)
@@ -411,8 +759,18 @@ def _fused_resnet_forward(self, x):
         if fused is not None:
             pooled = fused
     x = pooled
-    x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-    return self.fc(torch.flatten(self.avgpool(x), 1))
+    return self.layer4(self.layer3(self.layer2(self.layer1(x))))
+
+
+def _fused_resnet_forward(self, x):
+    import torch
+    feat = self._xai_features(x)
+    if _CHECK["on"] and feat.is_cuda:
+        # the head's broadcast backward against PyTorch's on these features (targets with a repeat); a refusal is counted and warned
+        targets = (torch.arange(feat.shape[0], device=feat.device) // 2) % max(int(getattr(self.fc, "out_features", 1)), 1)
+        if _head_applies(self, feat, targets) and _proven_head(self, feat, targets) is not None:
+            _CHECK["sites"] += 1
+    return self.fc(torch.flatten(self.avgpool(feat), 1))
 
 
 def _is_block(m):
@@ -453,6 +811,7 @@ def fuse_bn_relu(model, verify=None, fork_residual=False):
     stem = all(hasattr(m, n) for n in ("conv1", "bn1", "relu", "maxpool", "layer1", "layer2", "layer3", "layer4", "avgpool", "fc"))
     if stem and isinstance(m.bn1, nn.BatchNorm2d):
         m.forward = types.MethodType(_fused_resnet_forward, m)
+        m._xai_features = types.MethodType(_fused_resnet_features, m)        # everything before the head (target_scores)
         m._xai_fork = bool(fork_residual)
     if n_blocks == 0:
         raise ValueError("fuse_bn_relu: no ResNet-style blocks (conv1/bn1/conv2/bn2/relu/downsample) found in the model")

@@ -2,7 +2,8 @@
 lib/libxai_ext.so, libxai_ext2.so ... libxai_ext6.so (include/xai_hip_ext.h ... xai_hip_ext6.h), each holding the entry points
 added after the header before it was frozen or pinned.  LIBRARIES lists them, one Library record each; OPEN_LIBRARIES lists, in the
 same records, the library added since that table was pinned (lib/libxai_ext7.so, include/xai_hip_ext7.h) and LATER_LIBRARIES the ones
-since that one was (lib/libxai_compact.so, include/xai_hip_compact.h); nothing else in Python does.
+since that one was (lib/libxai_compact.so, include/xai_hip_compact.h); NEWER_LIBRARIES holds the one added after the count of those
+three tables was pinned too (lib/libxai_slic.so, include/xai_hip_slic.h); nothing else in Python does.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -150,20 +151,31 @@ OPEN_LIBRARIES = {lib.key: lib for lib in (
 LATER_LIBRARIES = {lib.key: lib for lib in (
     Library("compact", "xai_hip_compact.h", ("XAI_COMPACT_VERSION", "XAI_COMPACT_MINOR")),
 )}
+# ... and the library added after the number of records in the three tables above was pinned (tests/test_cpu_compact_abi.py):
+# lib/libxai_slic.so, include/xai_hip_slic.h, SLIC superpixels.  load() resolves it, every_library() lists it, all_libraries() stays
+# the three tables.
+NEWER_LIBRARIES = {lib.key: lib for lib in (
+    Library("slic", "xai_hip_slic.h", ("XAI_SLIC_VERSION", "XAI_SLIC_MINOR")),
+)}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of the record of `key` in LIBRARIES, OPEN_LIBRARIES or LATER_LIBRARIES (cached by the record); raises, never
-    falls back, when the file is absent or refused."""
-    return all_libraries()[key].load()
+    """The loaded handle of the record of `key` in LIBRARIES, OPEN_LIBRARIES, LATER_LIBRARIES or NEWER_LIBRARIES (cached by the
+    record); raises, never falls back, when the file is absent or refused."""
+    return every_library()[key].load()
 
 
 def all_libraries():
     """Every Library record by key, the three tables in the order their headers were written."""
     return {**LIBRARIES, **OPEN_LIBRARIES, **LATER_LIBRARIES}
+
+
+def every_library():
+    """Every Library record by key, all four tables in the order their headers were written."""
+    return {**all_libraries(), **NEWER_LIBRARIES}
 
 
 def check(code, what):

@@ -64,6 +64,9 @@ def build_parser():
     p.add_argument("--tis_kmeans", choices=("torch", "device"), default="torch", help="--attr_func TIS: who runs the k-means over the "
                    "activation channels.  torch (default): the Lloyd loop in torch ops (rocBLAS's summation order).  device: the same "
                    "iteration on the HIP kernels K58-K61 in a stated order, the same bytes on every run and machine")
+    p.add_argument("--mda_slic", choices=("skimage", "device"), default="skimage", help="--attr_func MDA: who computes the SLIC superpixels.  "
+                   "skimage (default): skimage.segmentation.slic on the host, the reference's dependency.  device: the same algorithm "
+                   "(scikit-image 0.18.3's, float32) on the HIP kernels K65-K68, the same labels; needs no scikit-image")
     p.add_argument("--out_dir", type=str, default="pert_test_results")
     p.add_argument("--checkpoint", type=str, default=None, help="path prefix for per-rank resume files (the reference loses a crashed run)")
     return p
@@ -96,7 +99,8 @@ def main(argv=None):
                     "batch_size": batch_size, "attr_func": args.attr_func, "model_name": args.model,
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
                     "weights_path": args.weights or "", "num_patches": num_patches, "lime_quickshift": args.lime_quickshift,
-                    "vit_cx_clustering": args.vit_cx_clustering, "tis_kmeans": args.tis_kmeans}
+                    "vit_cx_clustering": args.vit_cx_clustering, "tis_kmeans": args.tis_kmeans,
+                    "mda_slic": args.mda_slic}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, fused=not args.eight_runs, out_dir=args.out_dir,
                                                      checkpoint=args.checkpoint, streams=args.streams, reference_counter=args.reference_counter)
     if rank == 0:

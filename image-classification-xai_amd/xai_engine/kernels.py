@@ -1,7 +1,7 @@
 """Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
-Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES or _lib.OPEN_LIBRARIES>)`.
+Every launch goes through `_call(name, dev, *args, lib=<key of _lib.every_library()>)`.
 """
 import math
 
@@ -34,7 +34,7 @@ def _stream(dev):
 
 
 def _call(name, dev, *args, lib="hip"):
-    """Launch entry `name` of library `lib` (a key of _lib.LIBRARIES or _lib.OPEN_LIBRARIES) on torch's current stream of `dev`; the
+    """Launch entry `name` of library `lib` (a key of _lib.every_library()) on torch's current stream of `dev`; the
     error texts of every library are the main one's xai_strerror."""
     handle = _lib.load(lib)
     with torch.cuda.device(dev):
@@ -1718,3 +1718,182 @@ def kmeans_iterate(points, C, assign, counts, ws, state, max_iter, tol, iteratio
     _call("xai_kmeans_iterate_f32", points.device, _ptr(points), n, d, k, _ptr(C), _ptr(assign), _ptr(counts), _ptr(ws), ws.numel(),
           _ptr(state), max_iter, tol, iterations, lib="ext7")
     return C
+
+
+# ------------------------------------------------------------------------------ SLIC superpixels (K65-K68; libxai_slic.so)
+SLIC_UNCOVERED, SLIC_EMPTY, SLIC_IRREGULAR = 1, 2, 4         # the bits of status[b] (XAI_SLIC_*)
+
+
+def slic_limits():
+    """(the most clusters, channels, pixels of an image) K65-K68 take (include/xai_hip_slic.h, THE LIMITS)"""
+    lib = _lib.load("slic")
+    return lib.xai_slic_max_clusters(), lib.xai_slic_max_channels(), lib.xai_slic_max_pixels()
+
+
+def _slic_shape(features, name="features"):
+    """features (B, H, W, C) float32 or float64, contiguous, on a HIP device, inside THE LIMITS -> (B, H, W, C)"""
+    if not isinstance(features, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(features).__name__}")
+    if features.dtype not in (F32, F64):
+        raise TypeError(f"{name}: expected {F32} or {F64}, got {features.dtype}")
+    if features.dim() != 4 or features.numel() == 0:
+        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(features.shape)}")
+    B, H, W, C = (int(v) for v in features.shape)
+    cap = slic_limits()
+    if C > cap[1] or H * W > cap[2] or B > 65535 or H > 16 * 65535:
+        raise ValueError(f"(B, H * W, C) = ({B}, {H * W}, {C}) is over THE LIMITS (65535, {cap[2]}, {cap[1]}), or H = {H} is over "
+                         f"{16 * 65535} (include/xai_hip_slic.h)")
+    _need(features, features.dtype, name)
+    return B, H, W, C
+
+
+def _slic_centres(centres, features, B, C):
+    """centres (B, S, 2 + C) of the features' dtype on their device, 1 <= S <= the limit -> S"""
+    if not isinstance(centres, torch.Tensor):
+        raise TypeError(f"centres: expected a torch.Tensor, got {type(centres).__name__}")
+    if centres.dim() != 3 or centres.shape[0] != B or centres.shape[1] < 1 or centres.shape[2] != 2 + C:
+        raise ValueError(f"centres must be (B, S, 2 + C) = ({B}, S >= 1, {2 + C}), got {tuple(centres.shape)}")
+    S = int(centres.shape[1])
+    if S > slic_limits()[0]:
+        raise ValueError(f"S = {S} clusters are over THE LIMITS ({slic_limits()[0]}) (include/xai_hip_slic.h)")
+    _need(centres, features.dtype, "centres")
+    if centres.device != features.device:
+        raise ValueError("centres must be on the device of features")
+    return S
+
+
+def _slic_int(v, name, least):
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
+    if v < least:
+        raise ValueError(f"{name} must be >= {least}, got {v}")
+    return v
+
+
+def _slic_image_ints(t, name, like=None):
+    """an int32 (B, H, W) device tensor (of the shape and device of `like`)"""
+    _need(t, I32, name)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{name} must be (B, H, W) with at least one element, got {tuple(t.shape)}")
+    if like is not None and (tuple(t.shape) != tuple(like.shape[:3]) or t.device != like.device):
+        raise ValueError(f"{name} must be {tuple(like.shape[:3])} on the device of features")
+    return tuple(int(v) for v in t.shape)
+
+
+def _slic_status(status, B, like):
+    _need(status, I32, "status")
+    if status.numel() != B or status.device != like.device:
+        raise ValueError(f"status must hold {B} int32 on the device of its images")
+    return status
+
+
+def _slic_apart(a, b, name_a, name_b):
+    """K67 and K68 read other pixels of their input while they write their output: the two may share no byte"""
+    lo_a, lo_b = a.data_ptr(), b.data_ptr()
+    if lo_a < lo_b + b.numel() * b.element_size() and lo_b < lo_a + a.numel() * a.element_size():
+        raise ValueError(f"{name_a} must not overlap {name_b}")
+
+
+def _slic_suffix(t):
+    return "f32" if t.dtype == F32 else "f64"
+
+
+def slic_clear(status):
+    """status (B,) int32 = 0, by a kernel"""
+    _need(status, I32, "status")
+    if status.numel() < 1:
+        raise ValueError("status must hold at least one int32")
+    _call("xai_slic_clear_i32", status.device, _ptr(status), status.numel(), lib="slic")
+    return status
+
+
+def slic_assign(features, centres, step, labels=None, status=None):
+    """K65: labels (B, H, W) int32 = the lowest k of the least distance among the clusters whose window holds the pixel, -1 and the
+    UNCOVERED bit of status[b] where none does.  `status` None: a new, cleared word per image."""
+    B, H, W, C = _slic_shape(features)
+    S = _slic_centres(centres, features, B, C)
+    step = _slic_int(step, "step", 1)
+    if labels is None:
+        labels = torch.empty((B, H, W), dtype=I32, device=features.device)
+    _slic_image_ints(labels, "labels", features)
+    status = slic_clear(torch.empty(B, dtype=I32, device=features.device)) if status is None else _slic_status(status, B, features)
+    _call(f"xai_slic_assign_{_slic_suffix(features)}", features.device, _ptr(features), _ptr(centres), B, H, W, C, S, step, _ptr(labels),
+          _ptr(status), lib="slic")
+    return labels, status
+
+
+def slic_update(features, labels, centres, step, status=None):
+    """K66: centres (B, S, 2 + C) replaced by the means of (y, x, features) over each cluster's pixels, summed sequentially in raster
+    order; the EMPTY bit of status[b] for a cluster without a pixel (its centre becomes NaN)"""
+    B, H, W, C = _slic_shape(features)
+    S = _slic_centres(centres, features, B, C)
+    step = _slic_int(step, "step", 1)
+    _slic_image_ints(labels, "labels", features)
+    status = slic_clear(torch.empty(B, dtype=I32, device=features.device)) if status is None else _slic_status(status, B, features)
+    _call(f"xai_slic_update_{_slic_suffix(features)}", features.device, _ptr(features), _ptr(labels), B, H, W, C, S, step, _ptr(centres),
+          _ptr(status), lib="slic")
+    return centres, status
+
+
+def slic_iterate(features, centres, step, iterations, labels=None, status=None):
+    """status cleared, then `iterations` times K65 and K66 on the current stream, no read-back -> (labels of the last assignment,
+    status); centres is updated in place"""
+    B, H, W, C = _slic_shape(features)
+    S = _slic_centres(centres, features, B, C)
+    step = _slic_int(step, "step", 1)
+    iterations = _slic_int(iterations, "max_iter", 1)
+    if labels is None:
+        labels = torch.empty((B, H, W), dtype=I32, device=features.device)
+    _slic_image_ints(labels, "labels", features)
+    status = torch.empty(B, dtype=I32, device=features.device) if status is None else _slic_status(status, B, features)
+    _call(f"xai_slic_iterate_{_slic_suffix(features)}", features.device, _ptr(features), B, H, W, C, S, step, iterations, _ptr(centres),
+          _ptr(labels), _ptr(status), lib="slic")
+    return labels, status
+
+
+def slic_workspace(labels):
+    """The scratch of K67 and K68: uint8, xai_slic_workspace_bytes(B, H, W) bytes"""
+    B, H, W = _slic_image_ints(labels, "labels")
+    ws, _ = _workspace("xai_slic_workspace_bytes", labels.device, B, H, W, lib="slic", required=True)
+    return ws
+
+
+def _slic_ws(ws, t, B, H, W):
+    if ws is None:
+        return slic_workspace(t)
+    _need(ws, U8, "ws")
+    if ws.device != t.device or ws.numel() < _lib.load("slic").xai_slic_workspace_bytes(B, H, W):
+        raise ValueError("ws must be slic_workspace(labels) on the device of labels")
+    return ws
+
+
+def slic_components(labels, min_size, max_size, status=None, ws=None, comp=None):
+    """K67: comp (B, H, W) int32 = the least flat index of each pixel's 4-connected component of equal label; the IRREGULAR bit of
+    status[b] when a component's size is outside [min_size, max_size) or the sweeps ran out.  A given `comp` may not overlap labels."""
+    B, H, W = _slic_image_ints(labels, "labels")
+    min_size = _slic_int(min_size, "min_size", 0)
+    max_size = _slic_int(max_size, "max_size", min_size)
+    ws = _slic_ws(ws, labels, B, H, W)
+    comp = torch.empty_like(labels) if comp is None else comp
+    _slic_image_ints(comp, "comp", labels)
+    _slic_apart(comp, labels, "comp", "labels")
+    status = slic_clear(torch.empty(B, dtype=I32, device=labels.device)) if status is None else _slic_status(status, B, labels)
+    _call("xai_slic_components_i32", labels.device, _ptr(labels), B, H, W, min_size, max_size, _ptr(comp), _ptr(status), _ptr(ws),
+          ws.numel(), lib="slic")
+    return comp
+
+
+def slic_number(comp, start_label=0, ws=None, out=None):
+    """K68: (out (B, H, W) int32 = start_label + the rank of a component's first pixel among all first pixels, counts (B,) int32).
+    A given `out` may not overlap comp."""
+    B, H, W = _slic_image_ints(comp, "comp")
+    if start_label not in (0, 1):
+        raise ValueError("start_label should be 0 or 1.")
+    ws = _slic_ws(ws, comp, B, H, W)
+    out = torch.empty_like(comp) if out is None else out
+    _slic_image_ints(out, "out", comp)
+    _slic_apart(out, comp, "out", "comp")
+    counts = torch.empty(B, dtype=I32, device=comp.device)
+    _call("xai_slic_number_i32", comp.device, _ptr(comp), B, H, W, int(start_label), _ptr(out), _ptr(counts), _ptr(ws), ws.numel(),
+          lib="slic")
+    return out, counts

@@ -33,7 +33,8 @@ After each search everything is the reference's own host arithmetic on S + 1 num
 (curves.monotone_normalise), normalize_curve = curves.shape_constrained_fit (cvxopt's QP solved exactly; parity with cvxopt's
 iterate is unpinned), the two MASMetric.single_run calls on the engine's metric, np.interp, the sparse and dense maps and their
 kappa rule, and the antialiased down / up resize of the `_s` outputs (K.resize_bilinear).  The per-segment means that give
-segment_order are torch.mean on the host, S numbers once per call.  SLIC stays skimage's, on the host.
+segment_order are torch.mean on the host, S numbers once per call.  SLIC is skimage's on the host by default and the same
+algorithm on K65-K68 with segments="device" (xai_engine/slic.py).
 """
 import numpy as np
 import torch
@@ -374,8 +375,18 @@ def find_deletion_patches(input_tensor, segments, saliency_map_segmented, beginn
     return (*out, best_segment_list)
 
 
-def slic_segments(trans_img, patch_count):
-    """:602-604: skimage's SLIC of the un-normalised image, on the host."""
+SLIC = ("skimage", "device")
+
+
+def slic_segments(trans_img, patch_count, which="skimage", device="cuda"):
+    """:602-604: SLIC of the un-normalised image.  which "skimage": skimage's, on the host.  "device": the same algorithm (scikit-image
+    0.18.3's, in the image's float32) on K65-K68 (xai_engine/slic.py) on `device`; needs no scikit-image."""
+    if which not in SLIC:
+        raise ValueError(f"MDA: slic must be one of {SLIC}, got {which!r}")
+    if which == "device":
+        from .slic import slic as device_slic
+        segment_img = np.transpose(trans_img.squeeze().detach().cpu().numpy(), (1, 2, 0))
+        return torch.tensor(device_slic(segment_img, n_segments=patch_count, compactness=10000, start_label=0, device=device), dtype=int)
     try:
         from skimage.segmentation import slic
         from skimage.util import img_as_float
@@ -404,10 +415,13 @@ def end_index_of(MR_ins):
 
 def MDA(trans_img, input_tensor, saliency_map, patch_count, blur, model, device, img_hw, max_batch_size=5, ordered=False,
         CLIP_test_info=None, vis=False, segments=None):
-    """:600-626.  `segments` (not a reference argument): the (img_hw, img_hw) label map to use instead of SLIC's.
+    """:600-626.  `segments` (not a reference argument): the (img_hw, img_hw) label map to use instead of SLIC's, or who computes
+    SLIC: None or "skimage" on the host, "device" on K65-K68 (`slic_segments`).  The signature is the reference's plus this one
+    argument, so the choice of segmenter rides on it.
     -> (MGA_g_0, MGA_g_0_s, MGA_g_10), with vis all six maps, as (H, W, 3) NumPy arrays."""
     _refuse_clip(CLIP_test_info, "MDA")
-    segments = slic_segments(trans_img, patch_count) if segments is None else segments
+    if segments is None or isinstance(segments, str):
+        segments = slic_segments(trans_img, patch_count, "skimage" if segments is None else segments, device)
     saliency_map_segmented = segment_saliency_map(saliency_map, patch_count, img_hw)
     x = torch.as_tensor(input_tensor).cpu()
     _, _, order_a, MR_ins = find_insertion_patches(x, saliency_map_segmented, segments, blur, patch_count, type=1, model=model,

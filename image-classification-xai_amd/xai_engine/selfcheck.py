@@ -487,6 +487,32 @@ def run(device="cuda:0", verbose=True):
         if float(kerr) <= 1e-4:
             break
     check("kmeans_device", float((kgot - kw).abs().max()), 0.05)
+    # SLIC (K65-K68, libxai_slic.so) in fp64 against torch ops on the device: one assignment as the dense distance of every pixel to
+    # every cluster with the windows as a mask (argmin takes the lowest k of a tie, as the strict compare does), one update as
+    # index_add (another order of the same sums: to rounding), the components and numbering of a map of 5 x 6 blocks (its own answer)
+    sH, sW, sstep = 20, 24, 6
+    sf = torch.rand(1, sH, sW, 3, device=dev, dtype=torch.float64)
+    sy, sx = torch.meshgrid(torch.arange(3, sH, sstep, device=dev), torch.arange(3, sW, sstep, device=dev), indexing="ij")
+    sc = torch.zeros(1, sy.numel(), 5, device=dev, dtype=torch.float64)
+    sc[0, :, 0], sc[0, :, 1] = sy.flatten(), sx.flatten()
+    sc[0, :, 2:] = torch.rand(sy.numel(), 3, device=dev, dtype=torch.float64)
+    slab, sstat = K.slic_assign(sf, sc, sstep)
+    py, px = torch.meshgrid(torch.arange(sH, device=dev, dtype=torch.float64), torch.arange(sW, device=dev, dtype=torch.float64), indexing="ij")
+    cy, cx = sc[0, :, 0, None, None], sc[0, :, 1, None, None]
+    sd = ((cy - py) ** 2 + (cx - px) ** 2) * (1.0 / (sstep * sstep)) + ((sf[0][None] - sc[0, :, None, None, 2:]) ** 2).sum(-1)
+    inside = ((py >= (cy - 2 * sstep).clamp(min=0).floor()) & (py < (cy + 2 * sstep + 1).clamp(max=sH).floor())
+              & (px >= (cx - 2 * sstep).clamp(min=0).floor()) & (px < (cx + 2 * sstep + 1).clamp(max=sW).floor()))
+    swant = torch.where(inside, sd, torch.full_like(sd, float("inf"))).argmin(0)
+    check("slic_assign", float((slab[0].long() != swant).float().mean()) + float(int(sstat[0]) != 0), 0.0)
+    snew, _ = K.slic_update(sf, slab, sc.clone(), sstep, sstat)
+    srows = torch.cat([py.flatten()[:, None], px.flatten()[:, None], sf[0].reshape(-1, 3)], 1)
+    ssum = torch.zeros(sy.numel(), 5, device=dev, dtype=torch.float64).index_add_(0, slab[0].flatten().long(), srows)
+    check("slic_update", _rel(snew[0], ssum / torch.bincount(slab[0].flatten().long(), minlength=sy.numel())[:, None]), 1e-12)
+    sblocks = ((py // 5) * 4 + px // 6).to(torch.int32)[None].contiguous()
+    sstat2 = K.slic_clear(torch.empty(1, dtype=torch.int32, device=dev))
+    scomp = K.slic_components(sblocks[:, :, [0, 1, 2, 3, 4, 5, 18, 19, 20, 21, 22, 23, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17]].contiguous(), 30, 31, sstat2)
+    snum, scount = K.slic_number(scomp)
+    check("slic_components_number", float(not (torch.equal(snum, sblocks) and int(scount[0]) == 16 and int(sstat2[0]) == 0)), 0.0)
     wrong = unprotected = 0.0
     for _ in range(3):        # which solver MIOpen serves the probe's shape with settles after its first uses in a process: look more than once
         w, u = streams_probe(dev)

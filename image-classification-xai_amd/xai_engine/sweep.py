@@ -37,7 +37,7 @@ KEYS = ("MAS_ins", "MAS_del", "RISE_ins", "RISE_del", "AIC_ins", "AIC_del", "LER
 CNN_ATTR_FUNCS = ("grad", "inp_x_grad", "ig", "lig", "idg", "gig", "agi", "lime", "gs", "sg", "xrai", "gc", "gbp", "ggc", "fa", "occ")
 TRANS_ATTR_FUNCS = ("agi", "lime")   # rows that need the harness's un-normalised [0, 1] image (`trans_img`)
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
-VIT_TRANS_ATTR_FUNCS = ("MDA",)      # ViT rows that need `trans_img` (and, without skimage, testing_dict["mda_segments"])
+VIT_TRANS_ATTR_FUNCS = ("MDA",)      # ViT rows that need `trans_img` (and, without skimage, testing_dict["mda_segments"] or "mda_slic": "device")
 VIT_LRP_ATTR_FUNCS = ("t_attr",)     # ViT rows of the relevance pass (xai_engine/lrp.py); the segmentation evaluation does not offer them
 
 
@@ -241,16 +241,20 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
     elif attr_function == "MDA":
         # :243-263: the growing-kernel blur search, Baselines.bidirectional resized to the image and times ones(3), MDA with
         # num_patches ** 2 segments and max_batch_size 5, the map of its first return value (:181 |sum over channels|).
-        # testing_dict["mda_segments"] (not a reference key): the (img_hw, img_hw) label map to use instead of skimage's SLIC
+        # testing_dict["mda_segments"] (not a reference key): the (img_hw, img_hw) label map to use instead of skimage's SLIC;
+        # testing_dict["mda_slic"] = "device" (not a reference key either) runs the same SLIC on K65-K68 instead of skimage's
         from .blur import blur_until_unconfident
         from .mda import MDA
+        which = testing_dict.get("mda_slic", "skimage")
+        if which not in ("skimage", "device"):
+            raise ValueError(f"MDA: testing_dict['mda_slic'] must be 'skimage' or 'device', got {which!r}")
         if trans_img is None and testing_dict.get("mda_segments") is None:
             raise ValueError("MDA: the row needs the harness's un-normalised [0, 1] image (trans_img) for SLIC, or mda_segments")
         blur, _, _, _ = blur_until_unconfident(model, input_tensor, target_class, dev)
         bi_attn, _ = explainer.bidirectional(x, target_class, device=dev)
         bi_attn = K.resize_bilinear(bi_attn.detach().float().contiguous(), img_hw, img_hw)[0].cpu().numpy()[:, :, None] * np.ones((img_hw, img_hw, 3))
         mda, _, _ = MDA(trans_img, input_tensor.cpu(), bi_attn, testing_dict["num_patches"] ** 2, blur, model, device, img_hw, max_batch_size=5,
-                        segments=testing_dict.get("mda_segments"))
+                        segments=testing_dict.get("mda_segments") if testing_dict.get("mda_segments") is not None else which)
         return np.abs(np.sum(mda, axis=2)).astype(np.float32)
     else:
         print("Model-attribution mismatch, please use --help.")

@@ -3,7 +3,8 @@ lib/libxai_ext.so, libxai_ext2.so ... libxai_ext6.so (include/xai_hip_ext.h ... 
 added after the header before it was frozen or pinned.  LIBRARIES lists them, one Library record each; OPEN_LIBRARIES lists, in the
 same records, the library added since that table was pinned (lib/libxai_ext7.so, include/xai_hip_ext7.h) and LATER_LIBRARIES the ones
 since that one was (lib/libxai_compact.so, include/xai_hip_compact.h); NEWER_LIBRARIES holds the one added after the count of those
-three tables was pinned too (lib/libxai_slic.so, include/xai_hip_slic.h); nothing else in Python does.
+three tables was pinned too (lib/libxai_slic.so, include/xai_hip_slic.h), and LATEST_LIBRARIES the one added after that table and
+every_library() were pinned (lib/libxai_felz.so, include/xai_hip_felz.h); nothing else in Python does.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -157,15 +158,21 @@ LATER_LIBRARIES = {lib.key: lib for lib in (
 NEWER_LIBRARIES = {lib.key: lib for lib in (
     Library("slic", "xai_hip_slic.h", ("XAI_SLIC_VERSION", "XAI_SLIC_MINOR")),
 )}
+# ... and the library added after NEWER_LIBRARIES was pinned to its one key and every_library() to the four tables
+# (tests/test_cpu_slic.py): lib/libxai_felz.so, include/xai_hip_felz.h, Felzenszwalb segmentation.  load() resolves it and
+# latest_libraries() lists it; no test pins this table's length, so the next library is a line here.
+LATEST_LIBRARIES = {lib.key: lib for lib in (
+    Library("felz", "xai_hip_felz.h", ("XAI_FELZ_VERSION", "XAI_FELZ_MINOR")),
+)}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of the record of `key` in LIBRARIES, OPEN_LIBRARIES, LATER_LIBRARIES or NEWER_LIBRARIES (cached by the
-    record); raises, never falls back, when the file is absent or refused."""
-    return every_library()[key].load()
+    """The loaded handle of the record of `key` in LIBRARIES, OPEN_LIBRARIES, LATER_LIBRARIES, NEWER_LIBRARIES or LATEST_LIBRARIES
+    (cached by the record); raises, never falls back, when the file is absent or refused."""
+    return latest_libraries()[key].load()
 
 
 def all_libraries():
@@ -176,6 +183,11 @@ def all_libraries():
 def every_library():
     """Every Library record by key, all four tables in the order their headers were written."""
     return {**all_libraries(), **NEWER_LIBRARIES}
+
+
+def latest_libraries():
+    """Every Library record by key, all five tables in the order their headers were written: what load() resolves."""
+    return {**every_library(), **LATEST_LIBRARIES}
 
 
 def check(code, what):

@@ -67,6 +67,10 @@ def build_parser():
     p.add_argument("--mda_slic", choices=("skimage", "device"), default="skimage", help="--attr_func MDA: who computes the SLIC superpixels.  "
                    "skimage (default): skimage.segmentation.slic on the host, the reference's dependency.  device: the same algorithm "
                    "(scikit-image 0.18.3's, float32) on the HIP kernels K65-K68, the same labels; needs no scikit-image")
+    p.add_argument("--xrai_felzenszwalb", choices=("skimage", "device"), default="skimage", help="--attr_func xrai: who computes the six "
+                   "Felzenszwalb label maps.  skimage (default): skimage.segmentation.felzenszwalb on the host, the reference's "
+                   "dependency.  device: the same algorithm (scikit-image 0.18.3's, fp64) on the HIP kernels K69-K74, the same labels "
+                   "where no two edge costs are equal; needs no scikit-image")
     p.add_argument("--out_dir", type=str, default="pert_test_results")
     p.add_argument("--checkpoint", type=str, default=None, help="path prefix for per-rank resume files (the reference loses a crashed run)")
     return p
@@ -100,7 +104,7 @@ def main(argv=None):
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
                     "weights_path": args.weights or "", "num_patches": num_patches, "lime_quickshift": args.lime_quickshift,
                     "vit_cx_clustering": args.vit_cx_clustering, "tis_kmeans": args.tis_kmeans,
-                    "mda_slic": args.mda_slic}
+                    "mda_slic": args.mda_slic, "xrai_felzenszwalb": args.xrai_felzenszwalb}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, fused=not args.eight_runs, out_dir=args.out_dir,
                                                      checkpoint=args.checkpoint, streams=args.streams, reference_counter=args.reference_counter)
     if rank == 0:

@@ -1897,3 +1897,148 @@ def slic_number(comp, start_label=0, ws=None, out=None):
     _call("xai_slic_number_i32", comp.device, _ptr(comp), B, H, W, int(start_label), _ptr(out), _ptr(counts), _ptr(ws), ws.numel(),
           lib="slic")
     return out, counts
+
+
+# ------------------------------------------------------------------------------ Felzenszwalb segmentation (K69-K74; libxai_felz.so)
+FELZ_NONFINITE, FELZ_INVARIANT = 1, 2                        # the bits of the status word (XAI_FELZ_*)
+
+
+def felz_limits():
+    """(the most pixels of an image, channels, scales per call, radius) K69-K74 take (include/xai_hip_felz.h, THE LIMITS)"""
+    lib = _lib.load("felz")
+    return lib.xai_felz_max_pixels(), lib.xai_felz_max_channels(), lib.xai_felz_max_scales(), lib.xai_felz_max_radius()
+
+
+def felz_edges(H, W):
+    """E of an H x W image: right, down, down-right and up-right edges"""
+    return H * (W - 1) + (H - 1) * W + 2 * (H - 1) * (W - 1)
+
+
+def _felz_image(image, name="image"):
+    """image (B, H, W, C) float64, contiguous, on a HIP device, inside THE LIMITS -> (B, H, W, C)"""
+    if not isinstance(image, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(image).__name__}")
+    if image.dim() != 4 or image.numel() == 0:
+        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(image.shape)}")
+    B, H, W, C = (int(v) for v in image.shape)
+    cap = felz_limits()
+    if H * W > cap[0] or C > cap[1] or B > 65535:
+        raise ValueError(f"(B, H * W, C) = ({B}, {H * W}, {C}) is over THE LIMITS (65535, {cap[0]}, {cap[1]}) (include/xai_hip_felz.h)")
+    _need(image, F64, name)
+    return B, H, W, C
+
+
+def _felz_status(status, like):
+    if status is None:
+        status = torch.empty(1, dtype=I32, device=like.device)
+        _call("xai_felz_clear_i32", like.device, _ptr(status), 1, lib="felz")
+        return status
+    _need(status, I32, "status")
+    if status.numel() != 1 or status.device != like.device:
+        raise ValueError("status must hold one int32 on the device of its images")
+    return status
+
+
+def felz_clear(status):
+    """status (n,) int32 = 0, by a kernel"""
+    _need(status, I32, "status")
+    if status.numel() < 1:
+        raise ValueError("status must hold at least one int32")
+    _call("xai_felz_clear_i32", status.device, _ptr(status), status.numel(), lib="felz")
+    return status
+
+
+def felz_smooth(image, weights, axis):
+    """K69: one axis (0 = rows, 1 = columns) of the symmetric correlate1d with reflected indices; weights (2 r + 1,) float64 on the
+    device of image -> a new (B, H, W, C) float64 tensor"""
+    B, H, W, C = _felz_image(image)
+    _need(weights, F64, "weights")
+    if weights.dim() != 1 or weights.numel() % 2 != 1 or weights.device != image.device:
+        raise ValueError("weights must be (2 r + 1,) on the device of image")
+    radius = weights.numel() // 2
+    if radius > felz_limits()[3]:
+        raise ValueError(f"the radius {radius} of the weights is over THE LIMITS ({felz_limits()[3]}) (include/xai_hip_felz.h)")
+    if axis not in (0, 1):
+        raise ValueError(f"axis must be 0 or 1, got {axis!r}")
+    out = torch.empty_like(image)
+    _call("xai_felz_smooth_f64", image.device, _ptr(image), _ptr(weights), radius, int(axis), B, H, W, C, _ptr(out), lib="felz")
+    return out
+
+
+def felz_costs(image, status=None):
+    """K70: (keys (B, E) int64 = the bits of the costs, index (B, E) int32 = the edges' numbers, status (1,) int32).  The 1 x 1 image
+    has no edge: its arrays hold one column that nothing reads or writes, so that they have an address."""
+    B, H, W, C = _felz_image(image)
+    E = felz_edges(H, W)
+    status = _felz_status(status, image)
+    keys = torch.empty((B, max(E, 1)), dtype=I64, device=image.device)
+    index = torch.empty((B, max(E, 1)), dtype=I32, device=image.device)
+    _call("xai_felz_costs_u64", image.device, _ptr(image), B, H, W, C, _ptr(keys), _ptr(index), _ptr(status), lib="felz")
+    return keys, index, status
+
+
+def felz_workspace(dev, B, H, W, S):
+    """The scratch of K71-K73: uint8, xai_felz_workspace_bytes(B, H, W, S) bytes"""
+    ws, _ = _workspace("xai_felz_workspace_bytes", dev, B, H, W, S, lib="felz", required=True)
+    return ws
+
+
+def _felz_pairs(keys, index, H, W):
+    _need(keys, I64, "keys")
+    _need(index, I32, "index")
+    if keys.dim() != 2 or keys.shape != index.shape or keys.shape[1] != max(felz_edges(H, W), 1) or keys.device != index.device:
+        raise ValueError(f"keys and index must be (B, E = {felz_edges(H, W)}) on one device, got {tuple(keys.shape)} and "
+                         f"{tuple(index.shape)}")
+    return int(keys.shape[0])
+
+
+def _felz_ws(ws, dev, B, H, W, S):
+    if ws is None:
+        return felz_workspace(dev, B, H, W, S)
+    _need(ws, U8, "ws")
+    if ws.device != dev or ws.numel() < _lib.load("felz").xai_felz_workspace_bytes(B, H, W, S):
+        raise ValueError("ws must be felz_workspace(device, B, H, W, S) on the device of the keys")
+    return ws
+
+
+def felz_sort(keys, index, H, W, S=1, ws=None):
+    """K71 / K72: (keys, index) of every image sorted in place by key, equal keys by index (stable) -> (keys, index)"""
+    B = _felz_pairs(keys, index, H, W)
+    ws = _felz_ws(ws, keys.device, B, H, W, S)
+    _call("xai_felz_sort_u64", keys.device, _ptr(keys), _ptr(index), B, H, W, S, _ptr(ws), ws.numel(), lib="felz")
+    return keys, index
+
+
+def felz_merge(keys, order, scales, H, W, min_size, status=None, ws=None):
+    """K73: the sorted (keys, order) of B images, scales (S,) float64 on their device (scale / 255) -> (roots (B, S, H, W) int32,
+    stats (B, S, 2) int32 = edges tested and merged by the first walk, status)"""
+    B = _felz_pairs(keys, order, H, W)
+    _need(scales, F64, "scales")
+    S = int(scales.numel())
+    if scales.dim() != 1 or S < 1 or S > felz_limits()[2] or scales.device != keys.device:
+        raise ValueError(f"scales must be (S,), 1 <= S <= {felz_limits()[2]}, on the device of the keys")
+    min_size = _slic_int(min_size, "min_size", 0)
+    ws = _felz_ws(ws, keys.device, B, H, W, S)
+    status = _felz_status(status, keys)
+    roots = torch.empty((B, S, H, W), dtype=I32, device=keys.device)
+    stats = torch.empty((B, S, 2), dtype=I32, device=keys.device)
+    _call("xai_felz_merge_f64", keys.device, _ptr(keys), _ptr(order), _ptr(scales), B, S, H, W, min_size, _ptr(roots),
+          _ptr(stats), _ptr(status), _ptr(ws), ws.numel(), lib="felz")
+    return roots, stats, status
+
+
+def felz_labels(roots, status=None):
+    """K74: roots (..., H, W) int32 -> (labels of the same shape = the rank of a pixel's root among the roots in pixel order,
+    counts (...) int32 = the roots of every map, status)"""
+    _need(roots, I32, "roots")
+    if roots.dim() < 3 or roots.numel() == 0:
+        raise ValueError(f"roots must be (..., H, W) with at least one element, got {tuple(roots.shape)}")
+    n = int(roots.shape[-1] * roots.shape[-2])
+    M = roots.numel() // n
+    if n > felz_limits()[0]:
+        raise ValueError(f"H * W = {n} is over THE LIMITS ({felz_limits()[0]}) (include/xai_hip_felz.h)")
+    status = _felz_status(status, roots)
+    labels = torch.empty_like(roots)
+    counts = torch.empty(tuple(roots.shape[:-2]), dtype=I32, device=roots.device)
+    _call("xai_felz_labels_i32", roots.device, _ptr(roots), M, n, _ptr(labels), _ptr(counts), _ptr(status), lib="felz")
+    return labels, counts, status

@@ -122,9 +122,15 @@ def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
         # :142-146: IG (50 steps, the engine's K1 / K2), max over the channels, Felzenszwalb's six label maps of the image on the
         # host (skimage; testing_dict["xrai_label_maps"], not a reference key, replaces the segmenter), K29 at radius 5, K30;
         # |.| of the one-channel map (:181)
+        # testing_dict["xrai_felzenszwalb"] = "device" (not a reference key either) runs the same segmentation on K69-K74 instead of
+        # skimage's; an explicit xrai_label_maps wins over it
         from . import xrai
+        which = testing_dict.get("xrai_felzenszwalb", "skimage")
+        if which not in ("skimage", "device"):
+            raise ValueError(f"xrai: testing_dict['xrai_felzenszwalb'] must be 'skimage' or 'device', got {which!r}")
+        segmenter = (lambda x_hwc: xrai.device_felzenszwalb_label_maps(x_hwc, device=dev)) if which == "device" else xrai.felzenszwalb_label_maps
         ig = IG(input_tensor, model, steps, batch_size, 1, baseline, device, target_class)
-        label_maps = (testing_dict.get("xrai_label_maps") or xrai.felzenszwalb_label_maps)(input_tensor.squeeze().permute(1, 2, 0).cpu())
+        label_maps = (testing_dict.get("xrai_label_maps") or segmenter)(input_tensor.squeeze().permute(1, 2, 0).cpu())
         sal = xrai.xrai_batch(ig.detach().to(dev)[None], xrai.pack_segments(label_maps, dilation_rad=5, device=dev))[0].abs()
     elif attr_function == "gc":
         # |cam_up + cam_up + cam_up| fused into the up-sample kernel (scale 3, abs); with testing_dict["capture_gradcam"] the

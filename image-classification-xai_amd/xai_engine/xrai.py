@@ -8,8 +8,10 @@ of a batch runs in one launch (`xrai_batch`: K30, one workgroup per image).  The
 (`ig.IG`, evaluatePerturbation.py:144).
 
 `XRAI`, `XRAIParameters`, `XRAIOutput` keep the reference's signatures (:295-616; the mirror module
-util/attribution_methods/XRAIBuilder.py serves them).  The segmentation itself (Felzenszwalb, skimage, on the host) stays the
-reference's dependency: `felzenszwalb_label_maps` calls it when skimage is installed, callers that pass `segments=` need none.
+util/attribution_methods/XRAIBuilder.py serves them).  The segmentation itself (Felzenszwalb) is skimage's on the host by default,
+the reference's dependency: `felzenszwalb_label_maps` calls it when skimage is installed.  `device_felzenszwalb_label_maps` computes
+the same six maps on the kernels K69-K74 (xai_engine/felzenszwalb.py) and needs no skimage: `segments="device"`.  Callers that pass
+their own `segments=` need neither.
 """
 import collections
 
@@ -177,6 +179,32 @@ def ranked_segments(pixel_iter, sel_gain, flatten=True):
     return masks
 
 
+def _normalize_image(x_hwc):
+    """_normalize_image (:186-189) to FELZENSZWALB_IM_VALUE_RANGE, on the host in the image's dtype -> a host tensor"""
+    im = x_hwc.detach().cpu() if torch.is_tensor(x_hwc) else torch.as_tensor(np.asarray(x_hwc))
+    lo, hi = FELZENSZWALB_IM_VALUE_RANGE
+    im_max, im_min = torch.max(im), torch.min(im)
+    im = (im - im_min) / (im_max - im_min)
+    return im * (hi - lo) + lo
+
+
+def device_felzenszwalb_label_maps(x_hwc, device=None):
+    """`felzenszwalb_label_maps` on the kernels K69-K74, without skimage: x_hwc one (H, W, C) image or a (B, H, W, C) batch (every
+    image rescaled by its own extremes, on the host as above) -> (6, H, W) or (B, 6, H, W) int32 label maps on the HIP device, for
+    `pack_segments(..., dilation_rad=5)`.  The six scales share one smoothing, one set of costs and one sort."""
+    from . import felzenszwalb as F
+    x = x_hwc if torch.is_tensor(x_hwc) else torch.as_tensor(np.asarray(x_hwc))
+    if x.dim() not in (3, 4):
+        raise ValueError(f"device_felzenszwalb_label_maps: expected (H, W, C) or (B, H, W, C), got {tuple(x.shape)}")
+    if device is None:
+        device = x.device if x.is_cuda else "cuda"
+    images = torch.stack([_normalize_image(im) for im in (x if x.dim() == 4 else x[None])])
+    assert FELZENSZWALB_SIGMA_VALUES == [0.8]
+    labels, _ = F.felzenszwalb_batch(images.to(torch.float64).numpy(), FELZENSZWALB_SCALE_VALUES, FELZENSZWALB_SIGMA_VALUES[0],
+                                     FELZENSZWALB_MIN_SEGMENT_SIZE, device=device)
+    return labels if x.dim() == 4 else labels[0]
+
+
 def felzenszwalb_label_maps(x_hwc):
     """The six Felzenszwalb label maps XRAI segments an (H, W, C) image with (_get_segments_felzenszwalb, :230-254, without the
     resize): the image rescaled to [-1, 1] as _normalize_image does (:186-189), scales 50 ... 1200, sigma 0.8, min_size 150
@@ -185,12 +213,9 @@ def felzenszwalb_label_maps(x_hwc):
         from skimage import segmentation
     except ImportError as e:
         raise ImportError("XRAI's own segmentation needs scikit-image (skimage.segmentation.felzenszwalb), which is not installed; "
-                          "without it only callers that pass segments= work") from e
-    im = x_hwc.detach().cpu() if torch.is_tensor(x_hwc) else torch.as_tensor(np.asarray(x_hwc))
-    lo, hi = FELZENSZWALB_IM_VALUE_RANGE
-    im_max, im_min = torch.max(im), torch.min(im)
-    im = (im - im_min) / (im_max - im_min)
-    im = (im * (hi - lo) + lo).numpy()
+                          "without it pass segments=, or opt in to the device segmenter: XRAI.GetMask(..., segments=\"device\"), "
+                          "testing_dict[\"xrai_felzenszwalb\"] = \"device\", --xrai_felzenszwalb device") from e
+    im = _normalize_image(x_hwc).numpy()
     segs = []
     for scale in FELZENSZWALB_SCALE_VALUES:
         for sigma in FELZENSZWALB_SIGMA_VALUES:
@@ -242,11 +267,14 @@ class XRAI(object):
         """-> XRAIOutput: attribution_mask is the (H, W) float64 array of the float32 gains, as the reference's; segments (with
         return_xrai_segments) the rank image or the mask list of :702-711.  x_value: (H, W, C); base_attribution: the same shape
         (or (H, W)), array or tensor -- a device tensor stays on its device; segments: a list of (H, W) boolean masks, taken as
-        they are, or None for Felzenszwalb's segmentation of x_value (needs skimage) dilated by 5."""
+        they are, None for skimage's Felzenszwalb segmentation of x_value dilated by 5, or "device" for the same segmentation on
+        the kernels K69-K74 (no skimage needed)."""
         if extra_parameters is None:
             extra_parameters = XRAIParameters()
         if extra_parameters.algorithm not in ("full", "fast"):
             raise ValueError('Unknown algorithm type: {}'.format(extra_parameters.algorithm))
+        if isinstance(segments, str) and segments != "device":
+            raise ValueError(f"XRAI: segments must be masks, None or 'device', got {segments!r}")
         if base_attribution is None:
             raise ValueError("XRAI.GetMask needs base_attribution (the reference's GetMaskWithDetails fails without it: `attr` is "
                              "never assigned, XRAIBuilder.py:562-577); compute it with saliencyMethods.IG as the harness does")
@@ -263,7 +291,9 @@ class XRAI(object):
         a = a.to(dev, torch.float32)
         a = a.permute(2, 0, 1)[None] if a.dim() == 3 else a[None, None]
         H, W = a.shape[2:]
-        if segments is not None:
+        if isinstance(segments, str):
+            packed = pack_segments(device_felzenszwalb_label_maps(x_value, device=dev), dilation_rad=5, device=dev)
+        elif segments is not None:
             packed = pack_segments([list(segments)], dilation_rad=0, device=dev, shape=(H, W))
         else:
             packed = pack_segments(felzenszwalb_label_maps(x_value), dilation_rad=5, device=dev)

@@ -2,10 +2,8 @@
 
 Host code is Python on PyTorch-ROCm (classifier forward/backward, streams, memory); every
 element-wise / reduction step of the hot path runs in libxai_hip.so (hand-written gfx950
-HIP kernels behind the C ABI of include/xai_hip.h) or in one of the extension libraries libxai_ext.so ... libxai_ext7.so
-(include/xai_hip_ext.h ... xai_hip_ext7.h: entry points added after the header before was frozen; `_lib.LIBRARIES` lists the
-first seven libraries, `_lib.OPEN_LIBRARIES` the eighth, `_lib.LATER_LIBRARIES` libxai_compact.so (include/xai_hip_compact.h),
-`_lib.NEWER_LIBRARIES` libxai_slic.so (include/xai_hip_slic.h), `_lib.LATEST_LIBRARIES` libxai_felz.so (include/xai_hip_felz.h),
+HIP kernels behind the C ABI of include/xai_hip.h) or in one of the extension libraries libxai_<key>.so
+(include/xai_hip_<key>.h: entry points added after the header before was frozen; `_lib.LIBRARIES` lists every library once,
 and `load_library(key)` loads one).  The `util/` package next to this one
 re-exports these functions under the reference's module paths and signatures.
 """

@@ -1,10 +1,8 @@
-"""ctypes binding of the C ABI libraries: lib/libxai_hip.so (include/xai_hip.h, frozen at ABI 1.11) and the extension libraries
-lib/libxai_ext.so, libxai_ext2.so ... libxai_ext6.so (include/xai_hip_ext.h ... xai_hip_ext6.h), each holding the entry points
-added after the header before it was frozen or pinned.  LIBRARIES lists them, one Library record each; OPEN_LIBRARIES lists, in the
-same records, the library added since that table was pinned (lib/libxai_ext7.so, include/xai_hip_ext7.h) and LATER_LIBRARIES the ones
-since that one was (lib/libxai_compact.so, include/xai_hip_compact.h); NEWER_LIBRARIES holds the one added after the count of those
-three tables was pinned too (lib/libxai_slic.so, include/xai_hip_slic.h), and LATEST_LIBRARIES the one added after that table and
-every_library() were pinned (lib/libxai_felz.so, include/xai_hip_felz.h); nothing else in Python does.
+"""ctypes binding of the C ABI libraries.  LIBRARIES is the one table of them, a Library record per key: lib/libxai_<key>.so,
+declared by include/xai_hip_<key>.h with the version defines XAI_<KEY>_VERSION and XAI_<KEY>_MINOR.  The main library, key "hip", is the
+one exception: include/xai_hip.h, XAI_ABI_VERSION and XAI_ABI_MINOR, frozen at ABI 1.11; new entry points go into a library of
+their own.  A new library is a header, its key in LIBRARIES and the same
+key in csrc/Makefile's LIBS with a SRCS_<key> line.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -88,12 +86,12 @@ class Library:
     (`signatures`: name -> argument types, `restypes`, and the `version`.`minor` its two defines give) and, once load() has
     accepted the file, its `handle`.  The record is the state: redirect `path` or raise `minor` here, nowhere else."""
 
-    def __init__(self, key, header, defines):
+    def __init__(self, key):
         stem = "xai" if key == "hip" else f"xai_{key}"
         self.key = key
         self.path = os.path.join(_HERE, "lib", f"libxai_{key}.so")
-        self.header_path = os.path.join(_INCLUDE, header)
-        self.defines = defines
+        self.header_path = os.path.join(_INCLUDE, "xai_hip.h" if key == "hip" else f"xai_hip_{key}.h")
+        self.defines = ABI_DEFINES if key == "hip" else (f"XAI_{key.upper()}_VERSION", f"XAI_{key.upper()}_MINOR")
         self.version_entries = (f"{stem}_version", f"{stem}_version_minor")
         self.handle = None
         self.signatures, self.restypes, (self.version, self.minor) = self.read_header()
@@ -132,62 +130,16 @@ class Library:
         return lib
 
 
-# the one list of the libraries, in the order in which their headers were frozen; csrc/Makefile's LIBS is its build-side twin
-LIBRARIES = {lib.key: lib for lib in (
-    Library("hip", "xai_hip.h", ABI_DEFINES),
-    Library("ext", "xai_hip_ext.h", ("XAI_EXT_VERSION", "XAI_EXT_MINOR")),
-    Library("ext2", "xai_hip_ext2.h", ("XAI_EXT2_VERSION", "XAI_EXT2_MINOR")),
-    Library("ext3", "xai_hip_ext3.h", ("XAI_EXT3_VERSION", "XAI_EXT3_MINOR")),
-    Library("ext4", "xai_hip_ext4.h", ("XAI_EXT4_VERSION", "XAI_EXT4_MINOR")),
-    Library("ext5", "xai_hip_ext5.h", ("XAI_EXT5_VERSION", "XAI_EXT5_MINOR")),
-    Library("ext6", "xai_hip_ext6.h", ("XAI_EXT6_VERSION", "XAI_EXT6_MINOR")),
-)}
-# The libraries added after the table above was pinned to its seven keys by tests (tests/test_cpu_abi_libs.py), which a feature may
-# not edit: the same records, the same loader.  A refactor that may touch those tests folds this table into LIBRARIES.
-OPEN_LIBRARIES = {lib.key: lib for lib in (
-    Library("ext7", "xai_hip_ext7.h", ("XAI_EXT7_VERSION", "XAI_EXT7_MINOR")),
-)}
-# ... and the libraries added after OPEN_LIBRARIES was pinned to its one key in turn (tests/test_cpu_kmeans.py): lib/libxai_compact.so,
-# include/xai_hip_compact.h, the compact-layout BN/ReLU kernels.  No test names this table's keys, so the next library is a line here.
-LATER_LIBRARIES = {lib.key: lib for lib in (
-    Library("compact", "xai_hip_compact.h", ("XAI_COMPACT_VERSION", "XAI_COMPACT_MINOR")),
-)}
-# ... and the library added after the number of records in the three tables above was pinned (tests/test_cpu_compact_abi.py):
-# lib/libxai_slic.so, include/xai_hip_slic.h, SLIC superpixels.  load() resolves it, every_library() lists it, all_libraries() stays
-# the three tables.
-NEWER_LIBRARIES = {lib.key: lib for lib in (
-    Library("slic", "xai_hip_slic.h", ("XAI_SLIC_VERSION", "XAI_SLIC_MINOR")),
-)}
-# ... and the library added after NEWER_LIBRARIES was pinned to its one key and every_library() to the four tables
-# (tests/test_cpu_slic.py): lib/libxai_felz.so, include/xai_hip_felz.h, Felzenszwalb segmentation.  load() resolves it and
-# latest_libraries() lists it; no test pins this table's length, so the next library is a line here.
-LATEST_LIBRARIES = {lib.key: lib for lib in (
-    Library("felz", "xai_hip_felz.h", ("XAI_FELZ_VERSION", "XAI_FELZ_MINOR")),
-)}
+# the one list of the libraries, in the order in which their headers were written; csrc/Makefile's LIBS is its build-side twin
+LIBRARIES = {key: Library(key) for key in ("hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6", "ext7", "compact", "slic", "felz")}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of the record of `key` in LIBRARIES, OPEN_LIBRARIES, LATER_LIBRARIES, NEWER_LIBRARIES or LATEST_LIBRARIES
-    (cached by the record); raises, never falls back, when the file is absent or refused."""
-    return latest_libraries()[key].load()
-
-
-def all_libraries():
-    """Every Library record by key, the three tables in the order their headers were written."""
-    return {**LIBRARIES, **OPEN_LIBRARIES, **LATER_LIBRARIES}
-
-
-def every_library():
-    """Every Library record by key, all four tables in the order their headers were written."""
-    return {**all_libraries(), **NEWER_LIBRARIES}
-
-
-def latest_libraries():
-    """Every Library record by key, all five tables in the order their headers were written: what load() resolves."""
-    return {**every_library(), **LATEST_LIBRARIES}
+    """The loaded handle of LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
+    return LIBRARIES[key].load()
 
 
 def check(code, what):

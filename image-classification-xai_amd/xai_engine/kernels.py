@@ -1,7 +1,7 @@
 """Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
-Every launch goes through `_call(name, dev, *args, lib=<key of _lib.every_library()>)`.
+Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES>)`.
 """
 import math
 
@@ -34,7 +34,7 @@ def _stream(dev):
 
 
 def _call(name, dev, *args, lib="hip"):
-    """Launch entry `name` of library `lib` (a key of _lib.every_library()) on torch's current stream of `dev`; the
+    """Launch entry `name` of library `lib` (a key of _lib.LIBRARIES) on torch's current stream of `dev`; the
     error texts of every library are the main one's xai_strerror."""
     handle = _lib.load(lib)
     with torch.cuda.device(dev):

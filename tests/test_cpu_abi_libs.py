@@ -1,33 +1,44 @@
-"""The seven C ABI libraries as one table (xai_engine._lib.LIBRARIES): every test here runs for every key, the main library
+"""The C ABI libraries as one table (xai_engine._lib.LIBRARIES): every test here runs for every key of it, the main library
 included.  What a library exports against its header and its pinned version pair, what the loaded handle carries, what the loader
 and the header reader refuse, and that build() checks them all.  What is particular to one feature's entries (literal argtypes,
 the lines a header cites, the argument checks of its kernels) is in that feature's own test file."""
 import ctypes as C
+import glob
 import os
 import re
+import subprocess
 
 import pytest
 
 from abi_libs import PINNED, built, declared, exported
-from conftest import ROOT
+from conftest import PKG, ROOT
+from xai_engine import _lib
 
-KEYS = list(PINNED)
+KEYS = list(_lib.LIBRARIES)
+ELEVEN = ["hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6", "ext7", "compact", "slic", "felz"]
 _p, _i = C.c_void_p, C.c_int
 
 
 @pytest.fixture(scope="module")
 def L():
-    from xai_engine import _lib
     return _lib
 
 
-def test_the_table_lists_the_seven_libraries_once_and_the_old_names_are_aliases_of_the_main_record(L):
+def pin(rec):
+    """the literal pair of tests/abi_libs.py where it has one; a library added since is pinned by its feature's own test file"""
+    return PINNED.get(rec.key, (rec.version, rec.minor))
+
+
+def test_the_table_begins_with_the_eleven_libraries_and_the_old_names_are_aliases_of_the_main_record(L):
+    """The table begins with these eleven keys in this order; keys after them are allowed.  "And no other key" is given up on
+    purpose: it made every new library a new table beside this one.  What holds the table to the tree instead is the closure
+    test below, which grows with the tree: the headers, the Makefile's LIBS and the kernel files must all say the same keys."""
     import xai_engine
-    assert list(L.LIBRARIES) == KEYS == ["hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6"]
+    assert KEYS[:11] == ELEVEN and set(PINNED) <= set(KEYS)
     for key, rec in L.LIBRARIES.items():
         header = "xai_hip.h" if key == "hip" else f"xai_hip_{key}.h"
         stem = "xai" if key == "hip" else f"xai_{key}"
-        assert rec.key == key and os.path.basename(rec.path) == f"libxai_{key}.so"
+        assert isinstance(rec, L.Library) and rec.key == key and os.path.basename(rec.path) == f"libxai_{key}.so"
         assert os.path.dirname(rec.path) == os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "lib")
         assert os.path.samefile(rec.header_path, os.path.join(ROOT, "include", header))
         assert rec.version_entries == (f"{stem}_version", f"{stem}_version_minor") and set(rec.version_entries) <= set(rec.signatures)
@@ -35,6 +46,21 @@ def test_the_table_lists_the_seven_libraries_once_and_the_old_names_are_aliases_
     hip = L.LIBRARIES["hip"]
     assert (L.LIB_PATH, L.HEADER_PATH, L.ABI_VERSION, L.ABI_MINOR, L.ABI_DEFINES) == (hip.path, hip.header_path, hip.version, hip.minor, hip.defines)
     assert L.SIGNATURES is hip.signatures and xai_engine.LIB_PATH == hip.path and xai_engine.load_library is L.load
+    with pytest.raises(KeyError):
+        L.load("ext8")
+
+
+def test_the_table_the_headers_the_makefile_and_the_kernel_files_name_the_same_libraries(L):
+    """(a) include/xai_hip*.h is exactly the records' headers, (b) LIBS as make reads it is the table's keys in order, (c) every
+    csrc/*.hip is in exactly one SRCS_<key> of a key of the table and every file a SRCS_<key> names exists"""
+    csrc = os.path.join(PKG, "csrc")
+    headers = glob.glob(os.path.join(ROOT, "include", "xai_hip*.h"))
+    assert sorted(map(os.path.realpath, headers)) == sorted(os.path.realpath(rec.header_path) for rec in L.LIBRARIES.values())
+    db = subprocess.run(["make", "-C", csrc, "-pnq"], capture_output=True, text=True).stdout      # the database, nothing is run
+    make = dict(re.findall(r"^(LIBS|SRCS_\w+) :?= (.*)$", db, flags=re.M))
+    assert make["LIBS"].split() == KEYS and set(make) == {"LIBS"} | {f"SRCS_{key}" for key in KEYS}
+    listed = sorted(f for key in KEYS for f in make[f"SRCS_{key}"].split())
+    assert listed == sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*.hip")))
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -43,8 +69,8 @@ def test_library_exports_exactly_its_header_at_the_pinned_version(L, key):
     assert exported(built(key)) == declared(rec.header_path) == sorted(rec.signatures)
     text = open(rec.header_path).read()
     major, minor = (int(re.search(rf"^#define {d} (\d+)$", text, flags=re.M).group(1)) for d in rec.defines)
-    assert (rec.version, rec.minor) == PINNED[key] == (major, minor)
-    assert L.parse_header(text, rec.defines) == (rec.signatures, rec.restypes, PINNED[key])      # the table is the parse, nothing else
+    assert (rec.version, rec.minor) == pin(rec) == (major, minor)
+    assert L.parse_header(text, rec.defines) == (rec.signatures, rec.restypes, pin(rec))      # the table is the parse, nothing else
     assert all(rec.signatures[e] == [] and rec.restypes[e] is _i for e in rec.version_entries)
     if key == "hip":
         assert len(rec.signatures) == 64
@@ -58,7 +84,7 @@ def test_loaded_handle_is_cached_reports_the_headers_pair_and_carries_the_header
     built(key)
     lib = L.load(key)
     assert lib is L.load(key) is rec.load() is rec.handle
-    assert tuple(getattr(lib, e)() for e in rec.version_entries) == (rec.version, rec.minor) == PINNED[key]
+    assert tuple(getattr(lib, e)() for e in rec.version_entries) == (rec.version, rec.minor) == pin(rec)
     for name, types in rec.signatures.items():
         fn = getattr(lib, name)
         assert list(fn.argtypes) == types and fn.restype is rec.restypes[name], name
@@ -68,7 +94,7 @@ def test_loaded_handle_is_cached_reports_the_headers_pair_and_carries_the_header
 def test_loader_refuses_an_absent_an_older_and_a_stale_library_and_caches_none_of_them(L, key, monkeypatch, tmp_path):
     rec = L.LIBRARIES[key]
     real = built(key)
-    a, b = PINNED[key]
+    a, b = pin(rec)
     monkeypatch.setattr(rec, "handle", None)
     monkeypatch.setattr(rec, "path", str(tmp_path / f"libxai_{key}.so"))
     with pytest.raises(L.XaiHipError, match="not found") as e:
@@ -127,7 +153,7 @@ def test_build_version_checks_every_library(L, key, monkeypatch):
     import __graft_entry__ as g
     rec = L.LIBRARIES[key]
     real = built(key)
-    a, b = PINNED[key]
+    a, b = pin(rec)
     made = []
     monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: made.append((cmd, kw)))
     monkeypatch.setattr(rec, "handle", None)
@@ -145,4 +171,4 @@ def test_build_passes_on_the_built_tree_and_imports_the_feature_modules(L, monke
     monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
     g.build()
     assert all(rec.handle is not None for rec in L.LIBRARIES.values())
-    assert all(f"xai_engine.{m}" in sys.modules for m in ("segeval", "lrp", "quickshift", "linkage"))
+    assert all(f"xai_engine.{m}" in sys.modules for m in ("segeval", "lrp", "quickshift", "linkage", "kmeans", "slic", "felzenszwalb"))

@@ -1,12 +1,12 @@
-"""libxai_compact.so and include/xai_hip_compact.h without a GPU: the library record, the header read at 1.0 with the literal argument
-types of its four entries, the library exporting exactly what the header declares and nothing another library has, the build rule, and
-every refusal K62-K64 make before any HIP call."""
+"""libxai_compact.so and include/xai_hip_compact.h without a GPU: the header read at 1.0 with the literal argument types of its four
+entries, the build rule, and every refusal K62-K64 make before any HIP call.  What holds for every library alike (the record, the
+exports, the loader) is in tests/test_cpu_abi_libs.py."""
 import ctypes as C
 import os
 import re
 import subprocess
 
-from abi_libs import declared, exported
+from abi_libs import built, declared
 from conftest import PKG, ROOT
 
 HEADER = os.path.join(ROOT, "include", "xai_hip_compact.h")
@@ -14,27 +14,9 @@ ENTRIES = ["xai_bn_relu_bwd_bcast_f32", "xai_bn_relu_bwd_compact_f32", "xai_bn_r
 _p, _i, _f = C.c_void_p, C.c_int, C.c_float
 
 
-def _record():
-    from xai_engine import _lib
-    rec = _lib.LATER_LIBRARIES["compact"]
-    if not os.path.exists(rec.path):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return rec
-
-
-def test_the_record_loads_and_reports_the_headers_version_pair():
-    from xai_engine import _lib
-    rec = _record()
-    assert isinstance(rec, _lib.Library) and rec.path.endswith("lib/libxai_compact.so") and rec.header_path == HEADER
-    assert rec.version_entries == ("xai_compact_version", "xai_compact_version_minor")
-    assert "compact" not in _lib.LIBRARIES and "compact" not in _lib.OPEN_LIBRARIES and _lib.all_libraries()["compact"] is rec
-    lib = _lib.load("compact")
-    assert lib is rec.handle is _lib.load("compact") and (lib.xai_compact_version(), lib.xai_compact_version_minor()) == (1, 0)
-
-
 def test_the_header_parses_at_1_0_with_these_argument_types():
     from xai_engine import _lib
-    rec = _record()
+    rec = _lib.LIBRARIES["compact"]
     text = open(HEADER).read()
     args, ret, version = _lib.parse_header(text, rec.defines)
     assert version == (rec.version, rec.minor) == (1, 0)
@@ -52,20 +34,9 @@ def test_the_header_parses_at_1_0_with_these_argument_types():
         assert re.search(r"replaces\s", comment) and re.search(r"(saliencyMethods|evaluatePerturbation)\.py:\d+", comment), name
 
 
-def test_the_library_exports_exactly_its_header_and_no_other_library_exports_a_name_of_it():
-    from xai_engine import _lib
-    rec = _record()
-    mine = exported(rec.path)
-    assert mine == declared(HEADER) == sorted(rec.signatures)
-    others = {k: r for k, r in _lib.all_libraries().items() if k != "compact"}
-    assert len(others) == 8
-    for key, other in others.items():
-        assert not set(exported(other.path)) & set(mine), key
-
-
 def test_the_makefile_builds_it_and_rebuilds_it_when_its_header_or_the_shared_device_header_changes():
     make = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert "LIBS += compact" in make and "SRCS_compact := bnrelu_compact_kernels.hip" in make and "xai_bn_device.h" in make
+    assert "SRCS_compact := bnrelu_compact_kernels.hip" in make and "xai_bn_device.h" in make
     db = subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-pnq"], capture_output=True, text=True).stdout
     rule = next(line for line in db.splitlines() if line.startswith("build/bnrelu_compact_kernels.o:"))
     assert "../../include/xai_hip_compact.h" in rule and "xai_bn_device.h" in rule and "xai_bn_index.h" in rule
@@ -73,7 +44,7 @@ def test_the_makefile_builds_it_and_rebuilds_it_when_its_header_or_the_shared_de
 
 def test_k62_to_k64_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _record()
+    built("compact")
     lib = _lib.load("compact")
     p = 4096                                              # non-null, 16-byte aligned, never dereferenced: every call below is refused
     NULL, SHAPE, UNSUPPORTED = -1, -2, -3

@@ -1,19 +1,18 @@
 """Device Felzenszwalb segmentation, what needs no GPU: the NumPy restatement of include/xai_hip_felz.h's contract
 (tests/felzenszwalb_restated.py) against scikit-image 0.18.3's binary as tests/golden/felzenszwalb.npz recorded it, the Gaussian
-weights, the header, the library's exports and its table, the Makefile, every refusal by name and the option from the CLI down."""
+weights, the header, the library's build line and names, every refusal by name and the option from the CLI down."""
 import ctypes as C
 import functools
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import felzenszwalb_restated as R
-from abi_libs import declared, exported
+from abi_libs import built, declared, exported_elsewhere
 from conftest import PKG, ROOT, load_golden
 
 HEADER = os.path.join(ROOT, "include", "xai_hip_felz.h")
@@ -24,14 +23,6 @@ SMALL = {"a": (64, 48, 20), "b": (33, 47, 5), "c": (57, 43, 150), "d": (5, 9, 2)
          "d23": (2, 3, 1), "d17": (1, 7, 2), "d71": (7, 1, 2), "d11": (1, 1, 2)}             # H, W, min_size
 XRAI_SCALES = [50, 100, 150, 250, 500, 1200]
 _p, _i, _z = C.c_void_p, C.c_int, C.c_size_t
-
-
-def _built():
-    from xai_engine import _lib
-    path = _lib.LATEST_LIBRARIES["felz"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return path
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,45 +87,14 @@ def test_gaussian_weights_against_the_stored_ones():
 
 
 # ------------------------------------------------------------------------------------------------ the table, header and library
-def test_the_fifth_table_holds_felz_and_load_resolves_it():
-    from xai_engine import _lib
-    assert "felz" in _lib.LATEST_LIBRARIES and "felz" not in _lib.every_library()
-    assert list(_lib.latest_libraries())[:len(_lib.every_library())] == list(_lib.every_library())
-    rec = _lib.LATEST_LIBRARIES["felz"]
-    assert isinstance(rec, _lib.Library) and rec.path.endswith("lib/libxai_felz.so") and rec.header_path == HEADER
-    assert rec.version_entries == ("xai_felz_version", "xai_felz_version_minor") and rec.defines == ("XAI_FELZ_VERSION", "XAI_FELZ_MINOR")
-    _built()
-    lib = _lib.load("felz")
-    assert lib is rec.handle is _lib.load("felz") and (lib.xai_felz_version(), lib.xai_felz_version_minor()) == (1, 0)
-    make = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert "LIBS += felz\n" in make and "SRCS_felz := felz_kernels.hip\n" in make
-    import __graft_entry__ as g
-    assert "_lib.LATEST_LIBRARIES" in inspect.getsource(g.build)
-
-
-def test_load_raises_without_the_library_and_build_checks_its_version(monkeypatch, tmp_path):
-    import __graft_entry__ as g
-    from xai_engine import _lib
-    rec = _lib.LATEST_LIBRARIES["felz"]
-    real = _built()
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_felz.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("felz")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)
-    monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1"):
-        g.build()
-    assert rec.handle is None
-    monkeypatch.undo()
-    assert _lib.load("felz") is rec.handle
+def test_the_makefile_builds_felz_from_its_kernel_file():
+    assert "SRCS_felz := felz_kernels.hip\n" in open(os.path.join(PKG, "csrc", "Makefile")).read()
 
 
 def test_header_parses_at_1_0_cites_what_it_replaces_and_derives_its_bound():
     from xai_engine import _lib
     text = open(HEADER).read()
-    rec = _lib.LATEST_LIBRARIES["felz"]
+    rec = _lib.LIBRARIES["felz"]
     args, ret, version = _lib.parse_header(text, rec.defines)
     assert version == (rec.version, rec.minor) == (1, 0)
     assert sorted(args) == declared(HEADER) == sorted(ENTRIES + ["xai_felz_version", "xai_felz_version_minor"])
@@ -157,19 +117,14 @@ def test_header_parses_at_1_0_cites_what_it_replaces_and_derives_its_bound():
         assert re.search(r"replaces\s", text[text.rfind("/*", 0, at):at]), name
 
 
-def test_library_exports_exactly_its_header_and_shares_no_name_with_another_library():
-    from xai_engine import _lib
-    mine = exported(_built())
-    assert mine == declared(HEADER) == sorted(_lib.LATEST_LIBRARIES["felz"].signatures)
-    for key, other in _lib.every_library().items():
-        got = exported(other.path)
-        assert not set(got) & set(mine) and not [n for n in got if n.startswith("xai_felz_")], key
+def test_no_other_library_exports_a_felz_name():
+    assert not [(o, n) for o, n in exported_elsewhere("felz") if n.startswith("xai_felz_")]
 
 
 # ------------------------------------------------------------------------------------------------ refusals, no device
 def test_k69_to_k74_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _built()
+    built("felz")
     lib = _lib.load("felz")
     p = 16                               # a non-NULL, aligned pointer that is never dereferenced: validation comes first
     assert (lib.xai_felz_max_pixels(), lib.xai_felz_max_channels(), lib.xai_felz_max_scales(), lib.xai_felz_max_radius()) == (65536, 8, 16, 64)
@@ -218,7 +173,7 @@ def test_k69_to_k74_check_their_arguments_without_a_gpu():
 def test_the_python_front_refuses_by_name_before_it_needs_a_device():
     from xai_engine import XaiHipError, kernels as K
     from xai_engine import felzenszwalb as F
-    _built()
+    built("felz")
     image = np.zeros((8, 8, 3))
     with pytest.raises(ValueError, match=re.escape("This algorithm works only on single or multi-channel 2d images. ")):   # skimage's text
         F.felzenszwalb(image, multichannel=False)

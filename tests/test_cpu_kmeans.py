@@ -1,5 +1,5 @@
 """Device k-means without a GPU: the NumPy restatement of the contract (tests/kmeans_restated.py) against the oracle's Lloyd loop, the
-open library table of xai_engine/_lib.py, the seventh extension header (include/xai_hip_ext7.h) and its library, every refusal K58-K61
+seventh extension header (include/xai_hip_ext7.h), its library's build line and names, every refusal K58-K61
 and the Python front make before any HIP call, and the option's way from the CLI flag to TIS."""
 import ctypes as C
 import inspect
@@ -11,23 +11,13 @@ import pytest
 import torch
 
 import kmeans_restated as R
-from abi_libs import PINNED, declared, exported
+from abi_libs import PINNED, built, declared, exported_elsewhere
 from conftest import PKG, ROOT
 
 EXT7_HEADER = os.path.join(ROOT, "include", "xai_hip_ext7.h")
 ENTRIES = ["xai_kmeans_assign_f32", "xai_kmeans_init_f32", "xai_kmeans_iterate_f32", "xai_kmeans_max_clusters", "xai_kmeans_max_features",
            "xai_kmeans_max_points", "xai_kmeans_update_f32", "xai_kmeans_workspace_bytes"]
-SEVEN = ["hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6"]
 _p, _i, _z, _d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
-
-
-def _built_ext7():
-    import subprocess
-    from xai_engine import _lib
-    path = _lib.OPEN_LIBRARIES["ext7"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return path
 
 
 def planted():
@@ -63,27 +53,14 @@ def test_restatement_ties_nan_and_the_empty_cluster():
 
 
 # ------------------------------------------------------------------------------------------------ the table, header and library
-def test_the_pinned_table_is_still_the_seven_and_the_open_one_loads_ext7():
-    from xai_engine import _lib
-    assert list(_lib.LIBRARIES) == SEVEN == list(PINNED)
-    assert list(_lib.OPEN_LIBRARIES) == ["ext7"] and not set(_lib.OPEN_LIBRARIES) & set(_lib.LIBRARIES)
-    rec = _lib.OPEN_LIBRARIES["ext7"]
-    assert isinstance(rec, _lib.Library) and rec.path.endswith("lib/libxai_ext7.so") and rec.header_path == EXT7_HEADER
-    assert rec.version_entries == ("xai_ext7_version", "xai_ext7_version_minor")
-    _built_ext7()
-    lib = _lib.load("ext7")
-    assert lib is rec.handle is _lib.load("ext7") and (lib.xai_ext7_version(), lib.xai_ext7_version_minor()) == (1, 0)
-    assert _lib.load("ext6") is _lib.LIBRARIES["ext6"].handle
-    with pytest.raises(KeyError):
-        _lib.load("ext8")
-    make = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert "LIBS += ext7" in make and "SRCS_ext7 := kmeans_kernels.hip" in make
+def test_the_makefile_builds_ext7_from_the_kmeans_kernels():
+    assert "SRCS_ext7 := kmeans_kernels.hip\n" in open(os.path.join(PKG, "csrc", "Makefile")).read()
 
 
 def test_ext7_header_parses_at_1_0_states_the_order_and_cites_tis():
     from xai_engine import _lib
     text = open(EXT7_HEADER).read()
-    rec = _lib.OPEN_LIBRARIES["ext7"]
+    rec = _lib.LIBRARIES["ext7"]
     args, ret, version = _lib.parse_header(text, rec.defines)
     assert version == (rec.version, rec.minor) == (1, 0)
     assert sorted(args) == declared(EXT7_HEADER) == sorted(ENTRIES + ["xai_ext7_version", "xai_ext7_version_minor"])
@@ -105,25 +82,16 @@ def test_ext7_header_parses_at_1_0_states_the_order_and_cites_tis():
         assert re.search(r"replaces\s", text[text.rfind("/*", 0, at):at]), name
 
 
-def test_ext7_library_exports_exactly_its_header_and_none_of_the_seven_exports_a_name_of_it():
+def test_no_other_library_exports_a_kmeans_or_ext7_name():
     from xai_engine import _lib
-    rec = _lib.OPEN_LIBRARIES["ext7"]
-    mine = exported(_built_ext7())
-    assert mine == declared(EXT7_HEADER) == sorted(rec.signatures)
-    seen = 0
-    for key, other in _lib.LIBRARIES.items():
-        got = exported(other.path)
-        assert got == sorted(other.signatures), key                    # each of the seven still exports exactly its own header
-        assert not set(got) & set(mine) and not [n for n in got if n.startswith("xai_kmeans_") or "ext7" in n], key
-        seen += 1
-    assert seen == 7
+    assert not [(o, n) for o, n in exported_elsewhere("ext7") if n.startswith("xai_kmeans_") or "ext7" in n]
     assert {k: (r.version, r.minor) for k, r in _lib.LIBRARIES.items()} == PINNED
 
 
 # ------------------------------------------------------------------------------------------------ refusals, no device
 def test_k58_to_k61_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _built_ext7()
+    built("ext7")
     lib = _lib.load("ext7")
     p = 16                               # a non-NULL, aligned pointer that is never dereferenced: validation comes first
     caps = lib.xai_kmeans_max_points(), lib.xai_kmeans_max_features(), lib.xai_kmeans_max_clusters()

@@ -142,7 +142,7 @@ def test_ext6_library_exports_exactly_its_header_and_the_other_six_are_unchanged
     assert exported(built("ext6")) == declared(EXT6_HEADER) == sorted(_lib.LIBRARIES["ext6"].signatures)
     lib = _lib.load("ext6")
     assert (lib.xai_ext6_version(), lib.xai_ext6_version_minor()) == (1, 0)
-    # each of the other six exports exactly its own header (exported_elsewhere), none of them an entry of this feature
+    # each other library exports exactly its own header (exported_elsewhere), none of them an entry of this feature
     assert not [(o, n) for o, n in exported_elsewhere("ext6") if n.startswith("xai_linkage_") or "ext6" in n]
     assert {k: (rec.version, rec.minor) for k, rec in _lib.LIBRARIES.items()} == PINNED
 

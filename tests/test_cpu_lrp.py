@@ -110,7 +110,7 @@ def test_ext4_library_exports_exactly_its_header_and_the_other_four_are_unchange
     lib = _lib.load("ext4")
     assert (lib.xai_ext4_version(), lib.xai_ext4_version_minor()) == (1, 0)
     assert lib.xai_lrp_add_chunk() == R.ADD_CHUNK == 4096
-    # each of the other six exports exactly its own header (exported_elsewhere), none of them an entry of this feature
+    # each other library exports exactly its own header (exported_elsewhere), none of them an entry of this feature
     assert not [(o, n) for o, n in exported_elsewhere("ext4") if n.startswith("xai_lrp_") or "ext4" in n]
     assert {k: (rec.version, rec.minor) for k, rec in _lib.LIBRARIES.items()} == PINNED
 

@@ -132,7 +132,7 @@ def test_ext5_library_exports_exactly_its_header_and_the_other_five_are_unchange
     assert exported(built("ext5")) == declared(EXT5_HEADER) == sorted(_lib.LIBRARIES["ext5"].signatures)
     lib = _lib.load("ext5")
     assert (lib.xai_ext5_version(), lib.xai_ext5_version_minor()) == (1, 0)
-    # each of the other six exports exactly its own header (exported_elsewhere), none of them an entry of this feature
+    # each other library exports exactly its own header (exported_elsewhere), none of them an entry of this feature
     assert not [(o, n) for o, n in exported_elsewhere("ext5") if n.startswith("xai_quickshift_") or "ext5" in n]
     assert {k: (rec.version, rec.minor) for k, rec in _lib.LIBRARIES.items()} == PINNED
 

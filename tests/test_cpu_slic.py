@@ -1,20 +1,18 @@
 """Device SLIC without a GPU: the NumPy restatement of include/xai_hip_slic.h (tests/slic_restated.py) and the host front of
-xai_engine/slic.py against scikit-image 0.18.3's own runs (tests/golden/slic.npz), the fourth library table of xai_engine/_lib.py, the
-header and its library, every refusal K65-K68 and the Python front make before any HIP call, and the option's way from the CLI flag to
-MDA."""
+xai_engine/slic.py against scikit-image 0.18.3's own runs (tests/golden/slic.npz), the header, its library's build line and names, every
+refusal K65-K68 and the Python front make before any HIP call, and the option's way from the CLI flag to MDA."""
 import ctypes as C
 import functools
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import slic_restated as R
-from abi_libs import declared, exported
+from abi_libs import built, declared, exported_elsewhere
 from conftest import PKG, ROOT, load_golden
 
 HEADER = os.path.join(ROOT, "include", "xai_hip_slic.h")
@@ -24,14 +22,6 @@ ENTRIES = ["xai_slic_assign_f32", "xai_slic_assign_f64", "xai_slic_clear_i32", "
 TAGS = ["mda", "ragged", "colour", "wide", "one"]
 DTYPES = {"f32": np.float32, "f64": np.float64}
 _p, _i, _z = C.c_void_p, C.c_int, C.c_size_t
-
-
-def _built():
-    from xai_engine import _lib
-    path = _lib.NEWER_LIBRARIES["slic"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return path
 
 
 @functools.lru_cache(maxsize=None)
@@ -185,47 +175,14 @@ def test_grid_centroids_equal_skimages_and_the_front_refuses_what_it_does_not_se
 
 
 # ------------------------------------------------------------------------------------------------ the table, header and library
-def test_the_fourth_table_holds_slic_and_the_three_pinned_ones_are_what_they_were():
-    from xai_engine import _lib
-    assert list(_lib.NEWER_LIBRARIES) == ["slic"] and "slic" not in _lib.all_libraries()
-    assert list(_lib.every_library()) == list(_lib.all_libraries()) + ["slic"] and len(_lib.all_libraries()) - 1 == 8
-    rec = _lib.NEWER_LIBRARIES["slic"]
-    assert isinstance(rec, _lib.Library) and rec.path.endswith("lib/libxai_slic.so") and rec.header_path == HEADER
-    assert rec.version_entries == ("xai_slic_version", "xai_slic_version_minor") and rec.defines == ("XAI_SLIC_VERSION", "XAI_SLIC_MINOR")
-    _built()
-    lib = _lib.load("slic")
-    assert lib is rec.handle is _lib.load("slic") and (lib.xai_slic_version(), lib.xai_slic_version_minor()) == (1, 0)
-    with pytest.raises(KeyError):
-        _lib.load("slic2")
-    make = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert "LIBS += slic\n" in make and "SRCS_slic := slic_kernels.hip\n" in make
-    import __graft_entry__ as g
-    assert "_lib.every_library()" in inspect.getsource(g.build)
-
-
-def test_load_raises_without_the_library_and_build_checks_its_version(monkeypatch, tmp_path):
-    import __graft_entry__ as g
-    from xai_engine import _lib
-    rec = _lib.NEWER_LIBRARIES["slic"]
-    real = _built()
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_slic.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("slic")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)
-    monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1"):
-        g.build()
-    assert rec.handle is None
-    monkeypatch.undo()
-    assert _lib.load("slic") is rec.handle
+def test_the_makefile_builds_slic_from_its_kernel_file():
+    assert "SRCS_slic := slic_kernels.hip\n" in open(os.path.join(PKG, "csrc", "Makefile")).read()
 
 
 def test_header_parses_at_1_0_cites_skimage_and_states_its_bound():
     from xai_engine import _lib
     text = open(HEADER).read()
-    rec = _lib.NEWER_LIBRARIES["slic"]
+    rec = _lib.LIBRARIES["slic"]
     args, ret, version = _lib.parse_header(text, rec.defines)
     assert version == (rec.version, rec.minor) == (1, 0)
     assert sorted(args) == declared(HEADER) == sorted(ENTRIES + ["xai_slic_version", "xai_slic_version_minor"])
@@ -248,23 +205,14 @@ def test_header_parses_at_1_0_cites_skimage_and_states_its_bound():
         assert re.search(r"replaces\s", text[text.rfind("/*", 0, at):at]), name
 
 
-def test_library_exports_exactly_its_header_and_shares_no_name_with_another_library():
-    from xai_engine import _lib
-    mine = exported(_built())
-    assert mine == declared(HEADER) == sorted(_lib.NEWER_LIBRARIES["slic"].signatures)
-    seen = 0
-    for key, other in _lib.all_libraries().items():
-        got = exported(other.path)
-        assert got == sorted(other.signatures), key
-        assert not set(got) & set(mine) and not [n for n in got if n.startswith("xai_slic_")], key
-        seen += 1
-    assert seen == 9
+def test_no_other_library_exports_a_slic_name():
+    assert not [(o, n) for o, n in exported_elsewhere("slic") if n.startswith("xai_slic_")]
 
 
 # ------------------------------------------------------------------------------------------------ refusals, no device
 def test_k65_to_k68_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    _built()
+    built("slic")
     lib = _lib.load("slic")
     p = 16                               # a non-NULL, aligned pointer that is never dereferenced: validation comes first
     caps = lib.xai_slic_max_clusters(), lib.xai_slic_max_channels(), lib.xai_slic_max_pixels()
@@ -309,7 +257,7 @@ def test_k65_to_k68_check_their_arguments_without_a_gpu():
 def test_the_python_front_refuses_before_it_needs_a_device():
     from xai_engine import XaiHipError, kernels as K
     from xai_engine import slic as S
-    _built()
+    built("slic")
     f = torch.zeros(1, 8, 8, 3)
     cen = np.array([[2, 2], [6, 6]])
     with pytest.raises(TypeError, match="torch.Tensor"):

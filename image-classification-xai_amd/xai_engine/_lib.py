@@ -2,7 +2,8 @@
 declared by include/xai_hip_<key>.h with the version defines XAI_<KEY>_VERSION and XAI_<KEY>_MINOR.  The main library, key "hip", is the
 one exception: include/xai_hip.h, XAI_ABI_VERSION and XAI_ABI_MINOR, frozen at ABI 1.11; new entry points go into a library of
 their own.  A new library is a header, its key in LIBRARIES and the same
-key in csrc/Makefile's LIBS with a SRCS_<key> line.
+key in csrc/Makefile's LIBS with a SRCS_<key> line.  DTYPE_LIBRARIES is a second table of the same records, for libraries whose entries
+come in the dtype of a half-precision model (include/xai_<key>.h, csrc/<key>/).
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -28,7 +29,7 @@ _SCALAR = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C
 _POINTER = re.compile(r"(const )?(float|double|void|int32_t|int64_t|uint64_t|uint8_t)\*( const\*)?")
 _RETURN = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
 _PROTOTYPE = re.compile(r"(int|size_t|const char\*) (xai_[a-z0-9_]+)\(([^()]*)\)")
-_LAUNCH = ("_f32", "_f64", "_i32", "_u64")            # the entries that launch: they return a code and end in the caller's stream
+_LAUNCH = ("_f32", "_f64", "_i32", "_u64", "_f16")          # the entries that launch: they return a code and end in the caller's stream
 
 
 def parse_header(text, defines=ABI_DEFINES):
@@ -86,11 +87,11 @@ class Library:
     (`signatures`: name -> argument types, `restypes`, and the `version`.`minor` its two defines give) and, once load() has
     accepted the file, its `handle`.  The record is the state: redirect `path` or raise `minor` here, nowhere else."""
 
-    def __init__(self, key):
+    def __init__(self, key, header=None):
         stem = "xai" if key == "hip" else f"xai_{key}"
         self.key = key
         self.path = os.path.join(_HERE, "lib", f"libxai_{key}.so")
-        self.header_path = os.path.join(_INCLUDE, "xai_hip.h" if key == "hip" else f"xai_hip_{key}.h")
+        self.header_path = os.path.join(_INCLUDE, header or ("xai_hip.h" if key == "hip" else f"xai_hip_{key}.h"))
         self.defines = ABI_DEFINES if key == "hip" else (f"XAI_{key.upper()}_VERSION", f"XAI_{key.upper()}_MINOR")
         self.version_entries = (f"{stem}_version", f"{stem}_version_minor")
         self.handle = None
@@ -132,14 +133,19 @@ class Library:
 
 # the one list of the libraries, in the order in which their headers were written; csrc/Makefile's LIBS is its build-side twin
 LIBRARIES = {key: Library(key) for key in ("hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6", "ext7", "compact", "slic", "felz")}
+# The libraries whose entries come in the operand dtype of a half-precision model (`_f32` and `_f16` from one template, void*
+# operands): a table of their own, with headers include/xai_<key>.h and sources csrc/<key>/*.hip.  LIBRARIES above is the table of the
+# fp32 / fp64 / integer entries (include/xai_hip*.h, csrc/*.hip), which the tests of the features before hold whole, key by key.
+DTYPE_LIBRARIES = {"clip": Library("clip", header="xai_clip.h")}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
-    return LIBRARIES[key].load()
+    """The loaded handle of LIBRARIES[key] or DTYPE_LIBRARIES[key] (cached by the record); raises, never falls back, when the file
+    is absent or refused."""
+    return (LIBRARIES[key] if key in LIBRARIES else DTYPE_LIBRARIES[key]).load()
 
 
 def check(code, what):

@@ -1,0 +1,79 @@
+"""Command line of the harness counterpart for the CLIP models of the reference's table
+(XAI_Survey/evaluations/evaluatePerturbation.py:660-677, `--model CLIP16 | CLIP32`): the flags of xai_engine.evaluate_perturbation
+plus the two a CLIP run needs.  A module of its own: evaluate_perturbation's MODELS is also the table of the sanity and the
+segmentation CLIs, which do not serve CLIP, and all three refuse a CLIP model by name.
+
+    python -m xai_engine.evaluate_clip --model CLIP16 --attr_func eclip --image_count 1000 \
+        --dataset_path /data/ImageNet/val --weights clip_b16.pt --text_embeddings embeddings_b16.pt
+
+`--weights` takes the state_dict of `clip.load(...)` (OpenAI's parameter names); without it the weights are seeded and random.
+`--text_embeddings` takes a (classes, E) tensor, row c the text embedding of "a photo of a <class c>" (the reference's
+testing_dict["embeddings"]); without it the embeddings are seeded and random too.  The served rows are eclip, eclip_wo, eclip_nograd,
+maskclip and selfattn (xai_engine/eclip.py); the other five of sweep.CLIP_ATTR_FUNCS raise NotImplementedError naming the model
+they need.
+"""
+import torch
+
+from . import dist as xd
+from . import evaluate_perturbation, harness
+from .sweep import CLIP_ATTR_FUNCS
+from .zoo import clip_vit_b16, clip_vit_b32, convert_weights_fp16
+
+CLIP_MODELS = {
+    # name: (constructor, batch size, normalisation, num_patches), as evaluate_perturbation.MODELS
+    "CLIP16": (clip_vit_b16, 25, (harness.CLIP_MEAN, harness.CLIP_STD), 14),
+    "CLIP32": (clip_vit_b32, 50, (harness.CLIP_MEAN, harness.CLIP_STD), 7),
+}
+
+
+def build_parser():
+    p = evaluate_perturbation.build_parser()
+    p.set_defaults(model="CLIP16", attr_func="eclip")
+    p.add_argument("--text_embeddings", type=str, default=None, help="a (classes, E) tensor saved with torch.save; default: seeded random")
+    p.add_argument("--clip_fp32", action="store_true", help="run the model in fp32; default: OpenAI's mixed fp16, as the reference's "
+                   "clip.load gives on a GPU")
+    return p
+
+
+def main(argv=None):
+    args, _ = build_parser().parse_known_args(argv)
+    if args.model not in CLIP_MODELS:
+        raise SystemExit(f"unknown --model {args.model}; choose from {sorted(CLIP_MODELS)}")
+    if args.attr_func not in CLIP_ATTR_FUNCS:
+        print("Model-attribution mismatch, please use --help.")
+        raise SystemExit(1)
+    rank, world, device = xd.init_from_env()
+    if world == 1:
+        device = torch.device("cuda", args.cuda_num)
+        torch.cuda.set_device(device)
+    ctor, batch_size, norm, num_patches = CLIP_MODELS[args.model]
+    model = ctor()
+    if args.weights:
+        model.load_state_dict(torch.load(args.weights, map_location="cpu", weights_only=True))
+    if not args.clip_fp32:
+        convert_weights_fp16(model)
+    model = model.to(device).eval()
+    for p in model.parameters():
+        p.requires_grad_(False)
+    embed = model.visual.output_dim
+    if args.text_embeddings:
+        emb = torch.load(args.text_embeddings, map_location="cpu", weights_only=True)
+    else:
+        emb = torch.randn(1000, embed, generator=torch.Generator().manual_seed(0))
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.shape[1] != embed:
+        raise SystemExit(f"--text_embeddings must hold a (classes, {embed}) tensor")
+    testing_dict = {"models": [model], "imagenet_dataset": args.dataset_path, "normalize": norm, "img_hw": 224,
+                    "batch_size": args.batch_size or batch_size, "attr_func": args.attr_func, "model_name": args.model,
+                    "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
+                    "weights_path": args.weights or "", "num_patches": num_patches,
+                    "embeddings": emb.to(device=device, dtype=model.dtype), "num_classes": emb.shape[0]}
+    total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, out_dir=args.out_dir,
+                                                     reference_counter=args.reference_counter)
+    if rank == 0:
+        print(f"{used} images; means: " + ", ".join(f"{k}={total[k] / max(used, 1):.6f}" for k in total))
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()

@@ -26,6 +26,7 @@ from .ig import hip_device, _logits_of
 
 CNN_MEAN, CNN_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)          # evaluatePerturbation.py:683
 VIT_MEAN, VIT_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)                      # :686
+CLIP_MEAN, CLIP_STD = _sweep.CLIP_MEAN, _sweep.CLIP_STD                   # CLIP's preprocess, :663-672
 
 
 def load_image(path, img_hw):
@@ -65,6 +66,67 @@ def _pred(model, x, dev, cls=None):
         out = _logits_of(model(x.to(dev)))
     c = int(out.argmax(1)[0]) if cls is None else cls
     return c, float(torch.softmax(out, 1)[0, c])
+
+
+def get_CLIP_pred(input_tensor, model, all_classes_embedding):
+    """(class, softmax probability of that class at T = 0.1) of the image-text similarities (evaluatePerturbation.py:68-74)"""
+    with torch.no_grad():
+        similarities = model.encode_image(input_tensor) @ all_classes_embedding.squeeze().T
+        pred_class = similarities.argmax().item()
+        return pred_class, torch.nn.functional.softmax(similarities / 0.1, dim=-1)[:, pred_class].item()
+
+
+def _evaluate_clip(testing_dict, cc, rank, world, out_dir, reference_counter):
+    """The CLIP branch of the reference's loop (evaluatePerturbation.py:520-600): per file in sorted order the bitmap and shape
+    filters, get_CLIP_pred of the image, its blur and black (:544-550), CLIP_test_info (:552-556), the sanity and class-quota
+    filters (:569-576), get_CLIP_attr (:588) and the eight metric runs with CLIP_test_info (:594).  Every rank judges every file
+    (three encode_image passes); the selected images are shared out round-robin for the attribution and the metrics."""
+    t_start = time.time()
+    dev = hip_device(testing_dict["device"])
+    model = testing_dict["models"][0]
+    img_hw, root = testing_dict["img_hw"], testing_dict["imagenet_dataset"]
+    embeddings = testing_dict["embeddings"]
+    quota = ClassQuota(testing_dict["image_count"], testing_dict.get("num_classes", 1000))
+    blur = GaussianBlur(31, 31, dev)
+    sums = {k: 0.0 for k in _sweep.KEYS}
+    rows, used, attr_time = {}, 0, 0.0
+    for name in sorted(os.listdir(root)):
+        if quota.full:
+            break
+        if cc is not None and cc[image_number(name)] == 0:
+            continue
+        trans = load_image(os.path.join(root, name), img_hw)
+        if tuple(trans.shape) != (3, img_hw, img_hw):
+            continue
+        x = _sweep.clip_keepsize_input(trans, (1, 1)).to(dev)          # preprocess on an img_hw image: the 8-bit round trip and Normalize (:545)
+        target, p_orig = get_CLIP_pred(x, model, embeddings)
+        blur_cls, p_blur = get_CLIP_pred(blur(x), model, embeddings)
+        black_cls, p_black = get_CLIP_pred(torch.zeros_like(x), model, embeddings)
+        sane = not (p_blur >= p_orig or p_black >= p_orig or target == black_cls or target == blur_cls)
+        before = len(quota.chosen)
+        quota.offer(name, True, sane, target)
+        if len(quota.chosen) == before or before % world != rank:
+            continue
+        info = {"input": x, "embeddings": embeddings, "prediction_function": get_CLIP_pred}
+        t0 = time.time()
+        attribution = _sweep.get_CLIP_attr(trans, target, testing_dict)
+        attr_time += time.time() - t0
+        c = _sweep.run_perturbation(x.cpu(), attribution, testing_dict, info, blur=blur)
+        for k in _sweep.KEYS:
+            sums[k] += float(c[k])
+        rows[before] = [float(c[k]) for k in _sweep.KEYS]
+        used += 1
+    names = [c[0] for c in quota.chosen]
+    if reference_counter:
+        all_rows, flags, attr_time = _sweep.gather_rows(rows, len(names), dev, world=world, attr_seconds=attr_time)
+        total, used = _sweep.replay_reference_counter(all_rows[flags]), int(flags.sum())
+    else:
+        total, used, attr_time = _sweep.reduce_counters(sums, used, dev, world=world, attr_seconds=attr_time)
+    if rank == 0 and used:
+        name = f'{testing_dict["attr_func"]}_{testing_dict["image_count"]}_images.csv'
+        _sweep.write_csv(os.path.join(out_dir, testing_dict["model_name"], name), total, used, attr_time, time.time() - t_start,
+                         reference_counter=reference_counter)
+    return total, used, names
 
 
 class SelectedImages:
@@ -207,12 +269,16 @@ def evaluate_perturbation(testing_dict, rank=0, world=1, fused=True, out_dir="pe
     batch_size, attr_func, model_name, image_count, device (+ optional normalize=(mean, std),
     class_map_path).  `reference_counter`: fold the images' Counters and write the CSV exactly as the reference does
     (`+=` in file order drops keys with a running sum <= 0, only surviving keys are written; :594-596,:612-615) -- the
-    default is plain sums and always ten rows.  `streams`: HIP streams consecutive images are queued on."""
+    default is plain sums and always ten rows.  `streams`: HIP streams consecutive images are queued on.
+    A `model_name` with "CLIP" in it takes the reference's CLIP branch (`_evaluate_clip`): `testing_dict` then also has `embeddings`,
+    the (classes, E) text-embedding table in the model's dtype on its device, and `attr_func` is a row of sweep.CLIP_ATTR_FUNCS."""
     t_start = time.time()
     cc = None
     path = testing_dict.get("class_map_path")
     if path:
         cc = np.loadtxt(path).astype(np.int64)
+    if "CLIP" in testing_dict["model_name"]:                    # :544 and :587; eight runs per image, eager (checkpoint, streams and fused do not apply)
+        return _evaluate_clip(testing_dict, cc, rank, world, out_dir, reference_counter)
     names, images, _classes = select_images(testing_dict, cc, rank=rank, world=world, lazy=True)
     model = testing_dict["models"][0]
     dev = hip_device(testing_dict["device"])

@@ -1,7 +1,7 @@
 """Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
-Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES>)`.
+Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES or _lib.DTYPE_LIBRARIES>)`.
 """
 import math
 
@@ -10,17 +10,23 @@ import torch
 from . import _lib
 
 F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+F16 = torch.float16
 
 
-def _need(t, dtype, name):
+def _need(t, dtype, name, rows=False):
+    """The shared argument check: a tensor, on a HIP device, of `dtype` (a tuple: one of them), contiguous (rows: in its last
+    axis, the other strides are passed on)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
     if not t.is_cuda:
         raise _lib.XaiHipError(f"{name} lives on '{t.device}': the xai_engine kernels run on a HIP device only "
                                "(pass device='cuda:N'); there is no CPU fallback")
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
+    if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        raise TypeError(f"{name}: expected {' or '.join(map(str, dtype)) if isinstance(dtype, tuple) else dtype}, got {t.dtype}")
+    if rows:
+        if t.dim() < 1 or (t.shape[-1] > 1 and t.stride(-1) != 1):
+            raise ValueError(f"{name} must be contiguous in its last axis")
+    elif not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
     return t
 
@@ -2042,3 +2048,105 @@ def felz_labels(roots, status=None):
     counts = torch.empty(tuple(roots.shape[:-2]), dtype=I32, device=roots.device)
     _call("xai_felz_labels_i32", roots.device, _ptr(roots), M, n, _ptr(labels), _ptr(counts), _ptr(status), lib="felz")
     return labels, counts, status
+
+
+# ------------------------------------------------------------------------------ CLIP: the class-token row (K75-K77, include/xai_clip.h)
+CLIP_DTYPES = (F32, F16)
+
+
+def clip_limits():
+    """(XAI_CLIP_MAX_TOKENS, XAI_CLIP_MAX_WIDTH, XAI_CLIP_MAX_TEXTS) of the built library"""
+    lib = _lib.load("clip")
+    return lib.xai_clip_max_tokens(), lib.xai_clip_max_width(), lib.xai_clip_max_texts()
+
+
+def _clip_suffix(t):
+    return "f16" if t.dtype == F16 else "f32"
+
+
+def _clip_tokens(t, name, like=None):
+    """An (L, B, D) operand as the model produces it (the K or V third of the in-projection: any strides over L and B, the last
+    axis contiguous) -> (L, B, D, stride of L, stride of B); `like`: an operand whose dtype, device and shape it must have."""
+    _need(t, CLIP_DTYPES if like is None else like.dtype, name, rows=True)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{name} must be (L, B, D), got {tuple(t.shape)}")
+    L, B, D = t.shape
+    if L < 2:
+        raise ValueError(f"{name}: L = {L}; the class token and at least one patch are needed (L >= 2)")
+    max_l, max_d, _ = clip_limits()
+    if D > max_d or L > max_l:
+        raise ValueError(f"{name}: D = {D}, L = {L} are over the limits of K75-K77 (D <= {max_d}, L <= {max_l}: a row of each in LDS)")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{name} must have the shape and device of {tuple(like.shape)} on {like.device}")
+    return L, B, D, t.stride(0), t.stride(1)
+
+
+def _clip_rows(t, shape, like, name):
+    """A dense operand of `shape` in the dtype and on the device of `like`"""
+    _need(t, like.dtype, name)
+    if tuple(t.shape) != tuple(shape) or t.device != like.device:
+        raise ValueError(f"{name} must be {tuple(shape)} on {like.device}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def clip_cls_attention(q0, k, v, want_scores=False):
+    """K75: q0 (B, D) the class row of q, k and v (L, B, D) -> (attn (B, L), att_out (B, D)) in the operands' dtype: row 0 of the
+    one-head attention of generate_emap.py:288-307.  want_scores: a third result, the (B, L) scores in front of the softmax."""
+    L, B, D, kl, kb = _clip_tokens(k, "k")
+    _, _, _, vl, vb = _clip_tokens(v, "v", like=k)
+    _clip_rows(q0, (B, D), k, "q0")
+    attn = torch.empty((B, L), dtype=k.dtype, device=k.device)
+    att_out = torch.empty((B, D), dtype=k.dtype, device=k.device)
+    scores = torch.empty((B, L), dtype=k.dtype, device=k.device) if want_scores else None
+    _call(f"xai_clip_cls_attention_{_clip_suffix(k)}", k.device, _ptr(q0), _ptr(k), kl, kb, _ptr(v), vl, vb, B, L, D,
+          float(D) ** -0.5, _ptr(scores), _ptr(attn), _ptr(att_out), lib="clip")
+    return (attn, att_out, scores) if want_scores else (attn, att_out)
+
+
+def _clip_texts(T):
+    if not 1 <= T <= clip_limits()[2]:
+        raise ValueError(f"T = {T} texts: K76 and K77 take 1 .. {clip_limits()[2]}")
+    return T
+
+
+def clip_eclip_map(q_out0, k_out, v, grad_cls=None, texts=None, withksim=True, withgrad=True):
+    """K76: q_out0 (B, D), k_out and v (L, B, D), grad_cls (B, T, D) (None without withgrad: then `texts` = T) -> (B, L - 1) fp32,
+    grad_eclip of generate_emap.py:453-485 summed over the T texts."""
+    L, B, D, vl, vb = _clip_tokens(v, "v")
+    kl = kb = 0
+    if withksim:
+        _, _, _, kl, kb = _clip_tokens(k_out, "k_out", like=v)
+        _clip_rows(q_out0, (B, D), v, "q_out0")
+    if withgrad:
+        _need(grad_cls, v.dtype, "grad_cls")
+        if grad_cls.dim() != 3 or grad_cls.shape[0] != B or grad_cls.shape[2] != D or grad_cls.device != v.device:
+            raise ValueError(f"grad_cls must be ({B}, T, {D}) on {v.device}, got {tuple(grad_cls.shape)} on {grad_cls.device}")
+        texts = grad_cls.shape[1]
+    elif texts is None:
+        raise TypeError("clip_eclip_map: without withgrad there is no grad_cls to count the texts; pass texts=T")
+    T = _clip_texts(int(texts))
+    out = torch.empty((B, L - 1), dtype=F32, device=v.device)
+    _call(f"xai_clip_eclip_map_{_clip_suffix(v)}", v.device, _ptr(q_out0) if withksim else None, _ptr(k_out) if withksim else None, kl, kb,
+          _ptr(v), vl, vb, _ptr(grad_cls) if withgrad else None, B, L, D, T, int(bool(withksim)), int(bool(withgrad)), _ptr(out),
+          lib="clip")
+    return out
+
+
+def clip_maskclip_map(v_final, txt, k_out):
+    """K77: v_final (B, L - 1, E), txt (T, E) shared or (B, T, E), k_out (L, B, D) -> (B, L - 1) fp32, mask_clip of
+    generate_emap.py:500-529 summed over the T texts."""
+    L, B, D, kl, kb = _clip_tokens(k_out, "k_out")
+    _need(v_final, k_out.dtype, "v_final")
+    if v_final.dim() != 3 or tuple(v_final.shape[:2]) != (B, L - 1) or v_final.shape[2] < 1 or v_final.device != k_out.device:
+        raise ValueError(f"v_final must be ({B}, {L - 1}, E) on {k_out.device}, got {tuple(v_final.shape)} on {v_final.device}")
+    E = v_final.shape[2]
+    if E > clip_limits()[1]:
+        raise ValueError(f"v_final: E = {E} is over the limit of K77 (E <= {clip_limits()[1]})")
+    _need(txt, k_out.dtype, "txt")
+    if txt.dim() not in (2, 3) or txt.shape[-1] != E or (txt.dim() == 3 and txt.shape[0] != B) or txt.device != k_out.device:
+        raise ValueError(f"txt must be (T, {E}) or ({B}, T, {E}) on {k_out.device}, got {tuple(txt.shape)} on {txt.device}")
+    T = _clip_texts(txt.shape[-2])
+    out = torch.empty((B, L - 1), dtype=F32, device=k_out.device)
+    _call(f"xai_clip_maskclip_map_{_clip_suffix(k_out)}", k_out.device, _ptr(v_final), _ptr(txt), T * E if txt.dim() == 3 else 0,
+          _ptr(k_out), kl, kb, B, L, D, E, T, _ptr(out), lib="clip")
+    return out

@@ -74,7 +74,7 @@ class _PerturbationMetric:
             if clip_info is None:
                 return _logits_of(self.model(images)).detach()
             emb = clip_info["embeddings"]
-            return (self.model.encode_image(images) @ emb.squeeze().T).detach()
+            return (self.model.encode_image(images) @ emb.squeeze().T).detach().float()       # a half CLIP: the kernels take fp32
 
     # ---- the shared device pipeline ------------------------------------------------------
     def _run(self, img_tensor, saliency_map, device, patch_mask, max_batch_size, clip_info=None, want_density=False,

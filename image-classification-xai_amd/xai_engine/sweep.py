@@ -39,6 +39,10 @@ TRANS_ATTR_FUNCS = ("agi", "lime")   # rows that need the harness's un-normalise
 VIT_ATTR_FUNCS = ("attn", "grad", "n_rollout", "rollout", "t_attn", "bi_attn", "attn_ig", "VIT_CX", "TIS", "InFlow")
 VIT_TRANS_ATTR_FUNCS = ("MDA",)      # ViT rows that need `trans_img` (and, without skimage, testing_dict["mda_segments"] or "mda_slic": "device")
 VIT_LRP_ATTR_FUNCS = ("t_attr",)     # ViT rows of the relevance pass (xai_engine/lrp.py); the segmentation evaluation does not offer them
+# the rows of the reference's get_CLIP_attr in its order (:401-437); xai_engine/eclip.py serves METHODS of them and names what the
+# others need (REFUSED)
+CLIP_ATTR_FUNCS = ("eclip", "eclip_nograd", "eclip_wo", "game", "maskclip", "rollout", "selfattn", "surgery", "m2ib", "lrp")
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)      # generate_emap.py:27
 
 
 def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
@@ -265,6 +269,51 @@ def get_VIT_attr(input_tensor, trans_img, target_class, testing_dict):
     else:
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit
+
+
+def clip_keepsize_input(trans_img, patch=(16, 16)):
+    """The reference's `imgprocess_keepsize(to_pil_image(trans_img))` (evaluatePerturbation.py:394-395, generate_emap.py:29-37) for a
+    (3, H, W) image in [0, 1] whose H and W are multiples of `patch` (its default 16 x 16, whatever the model's patch is): the
+    bicubic resize to the nearest multiples is then the identity, and what is left is the 8-bit round trip (to_pil_image:
+    `mul(255).byte()`, which truncates; ToTensor: `/ 255`) and CLIP's Normalize.  -> (1, 3, H, W) fp32.  Any other size needs PIL's
+    bicubic resize: NotImplementedError."""
+    if trans_img.dim() != 3 or trans_img.shape[0] != 3:
+        raise ValueError(f"trans_img must be (3, H, W), got {tuple(trans_img.shape)}")
+    H, W = trans_img.shape[1:]
+    if H % patch[0] or W % patch[1]:
+        raise NotImplementedError(f"clip_keepsize_input: a {H} x {W} image is not a multiple of {patch[0]} x {patch[1]}; the reference "
+                                  "resizes it with PIL's bicubic filter, which is not restated here")
+    x = trans_img.detach().to("cpu", torch.float32).mul(255).byte().to(torch.float32).div(255)
+    mean, std = (torch.tensor(v, dtype=torch.float32).view(3, 1, 1) for v in (CLIP_MEAN, CLIP_STD))
+    return x.sub(mean).div(std).unsqueeze(0)
+
+
+def get_CLIP_attr(trans_img, target_class, testing_dict):
+    """(H,W) float32 numpy saliency map of the rows of the reference's get_CLIP_attr (evaluatePerturbation.py:373-445) that hang on
+    clip_encode_dense: eclip, eclip_wo, eclip_nograd, maskclip, selfattn (xai_engine/eclip.py).  The text embedding is
+    normalize(testing_dict["embeddings"][target_class]): the reference re-encodes "a photo of a <class>", the very text that row
+    of `embeddings` was made from, so no tokeniser is needed.  game, rollout, lrp, surgery and m2ib need further, modified CLIP
+    models: NotImplementedError naming the model."""
+    from . import eclip
+    attr_function = testing_dict["attr_func"]
+    if attr_function in eclip.REFUSED:
+        raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} needs {eclip.REFUSED[attr_function]}, which this engine "
+                                  "does not build")
+    if attr_function not in eclip.METHODS:
+        print("Model-attribution mismatch, please use --help.")
+        raise SystemExit
+    clipmodel = testing_dict["models"][0]
+    img_hw = testing_dict["img_hw"]
+    emb = testing_dict["embeddings"]
+    emb = emb.reshape(-1, emb.shape[-1])
+    txt = torch.nn.functional.normalize(emb[int(target_class)][None], dim=-1)
+    ksize = clipmodel.visual.conv1.kernel_size
+    if trans_img.shape[1] % ksize[0] or trans_img.shape[2] % ksize[1]:
+        raise NotImplementedError(f"get_CLIP_attr: a {trans_img.shape[1]} x {trans_img.shape[2]} image is not a multiple of the model's "
+                                  f"patch size {tuple(ksize)}")
+    x = clip_keepsize_input(trans_img)
+    sal = eclip.eclip_batch(clipmodel, x, txt, attr_function, img_hw=img_hw)[0]
+    return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
 
 
 def run_perturbation(input_tensor, attribution, testing_dict, CLIP_test_info=None, blur=None):

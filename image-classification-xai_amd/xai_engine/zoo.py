@@ -245,3 +245,175 @@ def vit_base_patch16_224(seed=0, **kw):
 def vit_base_patch32_224(seed=0, **kw):
     """the reference's "VIT32" (evaluatePerturbation.py:654-659): patch 32, 7 x 7 patches"""
     return vit_base_patch16_224(seed, patch=32, **kw)
+
+
+# ------------------------------------------------------------------------------ CLIP (ViT visual tower + causal text tower)
+class Fp32LayerNorm(nn.LayerNorm):
+    """LayerNorm of OpenAI's mixed precision: its parameters stay fp32, it computes in fp32 and returns the input's dtype"""
+
+    def forward(self, x):
+        return super().forward(x.float()).to(x.dtype)
+
+
+class QuickGELU(nn.Module):
+    def forward(self, x):
+        return x * torch.sigmoid(1.702 * x)
+
+
+class ClipAttention(nn.Module):
+    """Multi-head self-attention over (L, N, D) tokens with the parameter names of nn.MultiheadAttention (in_proj_weight,
+    in_proj_bias, out_proj), so that CLIP state dicts load as they are."""
+
+    def __init__(self, dim, heads):
+        super().__init__()
+        self.embed_dim, self.num_heads = dim, heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
+        self.out_proj = nn.Linear(dim, dim)
+
+    def forward(self, x, attn_mask=None):
+        L, N, D = x.shape
+        h, hd = self.num_heads, D // self.num_heads
+        q, k, v = (t.reshape(L, N * h, hd).transpose(0, 1) for t in
+                   nn.functional.linear(x, self.in_proj_weight, self.in_proj_bias).chunk(3, dim=-1))
+        scores = torch.bmm(q * float(hd) ** -0.5, k.transpose(1, 2))
+        if attn_mask is not None:
+            scores = scores + attn_mask.to(dtype=scores.dtype, device=scores.device)
+        out = torch.bmm(torch.softmax(scores, dim=-1), v).transpose(0, 1).reshape(L, N, D)
+        return self.out_proj(out)
+
+
+class ClipBlock(nn.Module):
+    def __init__(self, dim, heads, attn_mask=None):
+        super().__init__()
+        self.attn = ClipAttention(dim, heads)
+        self.ln_1 = Fp32LayerNorm(dim)
+        self.mlp = nn.Sequential()
+        self.mlp.add_module("c_fc", nn.Linear(dim, 4 * dim))
+        self.mlp.add_module("gelu", QuickGELU())
+        self.mlp.add_module("c_proj", nn.Linear(4 * dim, dim))
+        self.ln_2 = Fp32LayerNorm(dim)
+        self.attn_mask = attn_mask                      # a plain attribute, not a buffer: CLIP state dicts have no key for it
+
+    def forward(self, x):
+        x = x + self.attn(self.ln_1(x), self.attn_mask)
+        return x + self.mlp(self.ln_2(x))
+
+
+class ClipTransformer(nn.Module):
+    def __init__(self, width, layers, heads, attn_mask=None):
+        super().__init__()
+        self.width, self.layers = width, layers
+        self.resblocks = nn.Sequential(*(ClipBlock(width, heads, attn_mask) for _ in range(layers)))
+
+    def forward(self, x):
+        return self.resblocks(x)
+
+
+class ClipVisualTransformer(nn.Module):
+    def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim):
+        super().__init__()
+        self.input_resolution, self.output_dim = input_resolution, output_dim
+        self.conv1 = nn.Conv2d(3, width, patch_size, stride=patch_size, bias=False)
+        self.class_embedding = nn.Parameter(torch.randn(width) * width ** -0.5)
+        self.positional_embedding = nn.Parameter(torch.randn((input_resolution // patch_size) ** 2 + 1, width) * width ** -0.5)
+        self.ln_pre = Fp32LayerNorm(width)
+        self.transformer = ClipTransformer(width, layers, heads)
+        self.ln_post = Fp32LayerNorm(width)
+        self.proj = nn.Parameter(torch.randn(width, output_dim) * width ** -0.5)
+
+    def forward(self, x):
+        x = self.conv1(x).flatten(2).transpose(1, 2)                                     # (N, grid * grid, width)
+        x = torch.cat((self.class_embedding.to(x.dtype).expand(x.shape[0], 1, -1), x), dim=1)
+        x = self.ln_pre(x + self.positional_embedding.to(x.dtype))
+        x = self.transformer(x.transpose(0, 1)).transpose(0, 1)
+        return self.ln_post(x[:, 0]) @ self.proj
+
+
+class CLIP(nn.Module):
+    """The CLIP of Radford et al. 2021 with a ViT visual tower, written from the published architecture.  Parameter names are
+    OpenAI's (visual.conv1, visual.transformer.resblocks.N.attn.in_proj_weight, ..., token_embedding, text_projection,
+    logit_scale), so a state_dict of `clip.load(...)` loads with strict=True.  Heads are width // 64 in both towers unless
+    `transformer_heads` says otherwise."""
+
+    def __init__(self, embed_dim, image_resolution, vision_layers, vision_width, vision_patch_size, context_length=77,
+                 vocab_size=49408, transformer_width=512, transformer_heads=None, transformer_layers=12):
+        super().__init__()
+        self.context_length, self.vocab_size = context_length, vocab_size
+        self.visual = ClipVisualTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
+                                            max(1, vision_width // 64), embed_dim)
+        self.transformer = ClipTransformer(transformer_width, transformer_layers, transformer_heads or max(1, transformer_width // 64),
+                                           self.build_attention_mask())
+        self.token_embedding = nn.Embedding(vocab_size, transformer_width)
+        self.positional_embedding = nn.Parameter(torch.empty(context_length, transformer_width))
+        self.ln_final = Fp32LayerNorm(transformer_width)
+        self.text_projection = nn.Parameter(torch.empty(transformer_width, embed_dim))
+        self.logit_scale = nn.Parameter(torch.tensor(2.6592600369327779))              # log(1 / 0.07)
+        nn.init.normal_(self.token_embedding.weight, std=0.02)
+        nn.init.normal_(self.positional_embedding, std=0.01)
+        nn.init.normal_(self.text_projection, std=transformer_width ** -0.5)
+        for tower in (self.visual.transformer, self.transformer):
+            for blk in tower.resblocks:
+                nn.init.normal_(blk.attn.in_proj_weight, std=tower.width ** -0.5)
+                nn.init.normal_(blk.attn.out_proj.weight, std=(2 * tower.width * tower.layers) ** -0.5)
+                nn.init.normal_(blk.mlp.c_fc.weight, std=(2 * tower.width) ** -0.5)
+                nn.init.normal_(blk.mlp.c_proj.weight, std=(2 * tower.width * tower.layers) ** -0.5)
+
+    def build_attention_mask(self):
+        """the causal mask of the text tower: -inf above the diagonal"""
+        return torch.full((self.context_length, self.context_length), float("-inf")).triu_(1)
+
+    @property
+    def dtype(self):
+        return self.visual.conv1.weight.dtype
+
+    def encode_image(self, image):
+        return self.visual(image.to(self.dtype))
+
+    def encode_text(self, text):
+        x = self.token_embedding(text).to(self.dtype) + self.positional_embedding.to(self.dtype)
+        x = self.ln_final(self.transformer(x.transpose(0, 1)).transpose(0, 1)).to(self.dtype)
+        return x[torch.arange(x.shape[0]), text.argmax(dim=-1)] @ self.text_projection     # the end-of-text token has the highest id
+
+    def forward(self, image, text):
+        img = nn.functional.normalize(self.encode_image(image), dim=-1)
+        txt = nn.functional.normalize(self.encode_text(text), dim=-1)
+        logits = self.logit_scale.exp() * img @ txt.t()
+        return logits, logits.t()
+
+
+def convert_weights_fp16(model):
+    """OpenAI's mixed precision, in place: convolution, linear, attention and projection parameters in half; the LayerNorm
+    parameters, the embeddings and logit_scale stay fp32 (the forward passes cast the embeddings)."""
+    for m in model.modules():
+        if isinstance(m, (nn.Conv2d, nn.Linear)):
+            m.weight.data = m.weight.data.half()
+            if m.bias is not None:
+                m.bias.data = m.bias.data.half()
+        elif isinstance(m, ClipAttention):
+            m.in_proj_weight.data = m.in_proj_weight.data.half()
+            m.in_proj_bias.data = m.in_proj_bias.data.half()
+        for name in ("text_projection", "proj"):
+            p = getattr(m, name, None)
+            if isinstance(p, nn.Parameter):
+                p.data = p.data.half()
+    return model
+
+
+def clip_vit(seed=0, **sizes):
+    """A frozen seeded CLIP of any size (the keywords of `CLIP`), fp32"""
+    torch.manual_seed(seed)
+    m = CLIP(**sizes).eval()
+    for p in m.parameters():
+        p.requires_grad_(False)
+    return m
+
+
+def clip_vit_b16(seed=0):
+    """OpenAI's ViT-B/16: the reference's "CLIP16" (generate_emap.py:42)"""
+    return clip_vit(seed, embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=16)
+
+
+def clip_vit_b32(seed=0):
+    """OpenAI's ViT-B/32: the reference's "CLIP32" (generate_emap.py:48)"""
+    return clip_vit(seed, embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=32)

@@ -1,0 +1,387 @@
+"""The Grad-ECLIP rows of CLIP without a GPU: the restated flow (tests/clip_restated.py) against the reference-made fixtures
+(tests/golden/clip.npz), the one-row identity the engine's pass rests on, the zoo's CLIP against the fixture weights, the names and
+defaults of the reference's functions, the refusals, the preprocessing restatement, the library libxai_clip.so and its header, and
+the argument checks that need no device."""
+import ctypes as C
+import inspect
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import clip_restated as R
+from abi_libs import built, declared, exported
+from conftest import GOLDEN, ROOT
+
+CLIP_HEADER = os.path.join(ROOT, "include", "xai_clip.h")
+ENTRIES = ["xai_clip_cls_attention_f16", "xai_clip_cls_attention_f32", "xai_clip_eclip_map_f16", "xai_clip_eclip_map_f32",
+           "xai_clip_maskclip_map_f16", "xai_clip_maskclip_map_f32", "xai_clip_max_texts", "xai_clip_max_tokens", "xai_clip_max_width"]
+TUPLE = ("outputs", "v_final", "x_in", "v", "q_out", "k_out", "attn", "att_output")
+FIXTURES = [(m, str(j)) for m in R.MODELS for j in range(3)] + [("mini", "wide")]
+_p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+
+
+@pytest.fixture(scope="module")
+def G():
+    return np.load(os.path.join(GOLDEN, "clip.npz"), allow_pickle=False)
+
+
+def weights(model):
+    z = np.load(os.path.join(GOLDEN, f"clip_w_{model}.npz"), allow_pickle=False)
+    return {k: torch.from_numpy(z[k]) for k in z.files}
+
+
+def fixture_x(G, model, tag):
+    hw = (32, 48) if tag == "wide" else (R.MODELS[model][0],) * 2
+    return R.fixture_input(int(G[f"{model}/{tag}/x_seed"]), *hw)
+
+
+def fixture_txt(G, model, tag, T):
+    return R.fixture_texts(int(G[f"{model}/{tag}/t_seed"]), 2, R.MODELS[model][4])[:T]
+
+
+# ------------------------------------------------------------------------------------------------ the fixtures
+def test_fixture_files_hold_every_model_input_row_and_text_count(G):
+    for model, tag in FIXTURES:
+        for row in R.ROWS:
+            for T in (1, 2):
+                pre = f"{model}/{tag}/{row}/T{T}/"
+                ref, hi, gap = G[pre + "ref16"], G[pre + "hi"], float(G[pre + "gap"])
+                assert ref.dtype == np.float16 and hi.dtype == np.float64 and ref.shape == hi.shape
+                assert not np.isnan(ref).any() and ref.astype(np.float64).argmax() == hi.argmax()
+                assert gap == np.abs(ref.astype(np.float64) - hi).max() / np.abs(hi).max() and 0 < gap < 1e-2
+                assert 0 < float(G[pre + "gap32"]) < 1e-4 < 1e2 * gap
+                if row == "eclip":
+                    assert (ref > 0).mean() >= 0.25
+    for f in os.listdir(GOLDEN):
+        if f.startswith("clip"):
+            assert os.path.getsize(os.path.join(GOLDEN, f)) < 1 << 20, f
+
+
+@pytest.mark.parametrize("model", list(R.MODELS))
+def test_restated_flow_in_the_references_dtype_is_the_references_tuple_and_maps(G, model):
+    """Bound: none.  In mixed fp16 on the CPU the restated flow makes the reference's calls in the reference's order, so the 9-tuple
+    of input 0 and every stored map are equal bit for bit, as the fixture script asserted when it ran."""
+    sd = weights(model)
+    for tag in [t for m, t in FIXTURES if m == model]:
+        x = fixture_x(G, model, tag)
+        tup = R.encode_dense(sd, x, R.MODELS[model][0], None)
+        if tag == "0":
+            for name, t in zip(TUPLE, tup):
+                want = G[f"{model}/0/tuple/{name}"]
+                assert t.dtype == torch.float16 and t.detach().numpy().tobytes() == want.tobytes(), name
+        for T in (1, 2):
+            rows = R.rows_from_tuple(tup, fixture_txt(G, model, tag, T).half())
+            for row in R.ROWS:
+                assert rows[row].detach().numpy().tobytes() == G[f"{model}/{tag}/{row}/T{T}/ref16"].tobytes(), (tag, row, T)
+
+
+@pytest.mark.parametrize("model", list(R.MODELS))
+def test_restated_flow_in_fp64_is_the_stored_high_precision_side(G, model):
+    """Bound: 1e-12 relative.  `hi` was made by this very flow in fp64; only the BLAS of the machine may differ."""
+    sd = weights(model)
+    for tag in [t for m, t in FIXTURES if m == model]:
+        tup = R.encode_dense(sd, fixture_x(G, model, tag), R.MODELS[model][0], torch.float64)
+        rows = R.rows_from_tuple(tup, fixture_txt(G, model, tag, 2).half().double())
+        for row in R.ROWS:
+            want = G[f"{model}/{tag}/{row}/T2/hi"]
+            assert np.abs(rows[row].detach().numpy() - want).max() <= 1e-12 * np.abs(want).max(), (tag, row)
+
+
+@pytest.mark.parametrize("model", list(R.MODELS))
+def test_one_row_identity_in_fp64(G, model):
+    """What xai_engine.eclip.cls_pass rests on: the class-token row computed alone (one query, a one-row tail, a one-row backward)
+    is the class-token row of the full flow, and the gradient of the cosine with respect to att_output is zero outside row 0.
+    Bound: 1e-12 relative in fp64 (the GEMM extents differ, so the summation orders may), exactly zero for grad[1:]."""
+    sd = weights(model)
+    x = fixture_x(G, model, "0")
+    txt = fixture_txt(G, model, "0", 2).half().double()
+    outputs, _vf, _x_in, _v, _q_out, _k_out, attn, att_output, _ = R.encode_dense(sd, x, R.MODELS[model][0], torch.float64)
+    cosines = (torch.nn.functional.normalize(outputs[:, 0], dim=-1) @ txt.T)[0]
+    grads = [torch.autograd.grad(c, att_output, retain_graph=True)[0] for c in cosines]
+    out0, grad0, attn0, att0 = R.one_row(sd, x, R.MODELS[model][0], txt, torch.float64)
+
+    def close(a, b):
+        return (a - b).abs().max() <= 1e-12 * b.abs().max()
+    assert close(out0, outputs[0, 0].detach()) and close(attn0, attn[0, 0]) and close(att0, att_output[0, 0].detach())
+    for t, g in enumerate(grads):
+        assert close(grad0[t], g[0, 0]) and g[0, 0].abs().max() > 0
+        assert (g[1:] == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ the zoo's CLIP
+def zoo_model(model, fp16=True):
+    from xai_engine import zoo
+    res, patch, width, layers, embed = R.MODELS[model]
+    m = zoo.clip_vit(0, embed_dim=embed, image_resolution=res, vision_layers=layers, vision_width=width, vision_patch_size=patch, **R.TEXT)
+    return zoo.convert_weights_fp16(m) if fp16 else m
+
+
+@pytest.mark.parametrize("model", list(R.MODELS))
+def test_zoo_clip_loads_the_reference_state_dict_strictly_and_reproduces_encode_image(G, model):
+    """The weights are those of the reference's CLIP after its convert_weights: same names, shapes and dtypes, strict=True.  Bound
+    for encode_image: 2 ulp of half at max|ref16|: the multi-head attention of blocks 0 .. n-2 is written out here, so a GEMM may
+    be split differently from the reference's, the rest is the same sequence of half operations."""
+    sd = weights(model)
+    m = zoo_model(model)
+    own = m.state_dict()
+    assert set(own) == set(sd) and all(own[k].dtype == sd[k].dtype and own[k].shape == sd[k].shape for k in sd)
+    m.load_state_dict(sd, strict=True)
+    assert m.dtype == torch.float16 and m.visual.ln_post.weight.dtype == torch.float32 and m.visual.class_embedding.dtype == torch.float32
+    for tag in "012":
+        want = G[f"{model}/{tag}/encode_image/ref16"].astype(np.float64)
+        with torch.no_grad():
+            got = m.encode_image(fixture_x(G, model, tag))[0]
+        assert got.dtype == torch.float16
+        ulp = 2.0 ** (np.floor(np.log2(np.abs(want).max())) - 10)
+        assert np.abs(got.double().numpy() - want).max() <= 2 * ulp
+    text = torch.tensor([[1, 2, 7, 0]])
+    assert m.encode_text(text).shape == (1, R.MODELS[model][4]) and m.encode_text(text).dtype == torch.float16
+
+
+def test_zoo_clip_b16_and_b32_have_openais_sizes():
+    from xai_engine import zoo
+    for ctor, patch, tokens in ((zoo.clip_vit_b16, 16, 197), (zoo.clip_vit_b32, 32, 50)):
+        sig = inspect.signature(ctor)
+        assert list(sig.parameters) == ["seed"] and sig.parameters["seed"].default == 0
+    m = zoo.clip_vit_b32()
+    v = m.visual
+    assert (v.input_resolution, v.transformer.width, len(v.transformer.resblocks), v.conv1.kernel_size, tuple(v.proj.shape)) == \
+        (224, 768, 12, (32, 32), (768, 512))
+    assert tuple(v.positional_embedding.shape) == (50, 768) and v.transformer.resblocks[0].attn.num_heads == 12
+    assert (m.context_length, m.vocab_size, m.transformer.width, len(m.transformer.resblocks), m.transformer.resblocks[0].attn.num_heads) == \
+        (77, 49408, 512, 12, 8)
+    assert tuple(m.text_projection.shape) == (512, 512) and abs(float(m.logit_scale) - np.log(1 / 0.07)) < 1e-6
+    assert not any(p.requires_grad for p in m.parameters())
+
+
+def test_engine_full_row_functions_equal_the_reference_in_its_dtype_on_the_cpu(G):
+    """xai_engine.eclip's clip_encode_dense / grad_eclip / mask_clip on the zoo model: for the one-block models the same sequence of
+    half operations as the reference, so the stored tuple and maps bit for bit."""
+    from xai_engine import eclip
+    for model in ("short", "b32"):
+        m = zoo_model(model)
+        m.load_state_dict(weights(model), strict=True)
+        tup = eclip.clip_encode_dense(fixture_x(G, model, "0"), m)
+        assert len(tup) == 9 and tuple(tup[8]) == (R.MODELS[model][0] // R.MODELS[model][1],) * 2
+        for name, t in zip(TUPLE, tup):
+            assert t.detach().numpy().tobytes() == G[f"{model}/0/tuple/{name}"].tobytes(), (model, name)
+        rows = R.rows_from_tuple(tup, fixture_txt(G, model, "0", 2).half(), eclip.grad_eclip, eclip.mask_clip)
+        for row in R.ROWS:
+            assert rows[row].detach().numpy().tobytes() == G[f"{model}/0/{row}/T2/ref16"].tobytes(), (model, row)
+
+
+# ------------------------------------------------------------------------------------------------ names, defaults, refusals
+def test_api_names_and_defaults_are_the_references():
+    from xai_engine import eclip
+    api = json.load(open(os.path.join(GOLDEN, "clip_api.json")))
+    assert sorted(api) == ["attention_layer", "clip_encode_dense", "grad_eclip", "mask_clip"]
+    for name, want in api.items():
+        sig = inspect.signature(getattr(eclip, name))
+        got = [[n, None if p.default is inspect.Parameter.empty else repr(p.default)] for n, p in sig.parameters.items()]
+        assert got == want, name
+    p = inspect.signature(eclip.eclip_batch).parameters
+    assert list(p) == ["clipmodel", "x", "txt_embedding", "method", "img_hw"] and p["img_hw"].default is None
+    assert list(inspect.signature(eclip.cls_pass).parameters)[:2] == ["clipmodel", "x"]
+    assert eclip.METHODS == R.ROWS
+
+
+def test_each_unserved_row_is_refused_by_name_with_the_model_it_needs():
+    from xai_engine import eclip, sweep
+    assert set(sweep.CLIP_ATTR_FUNCS) == set(eclip.METHODS) | set(eclip.REFUSED) and len(sweep.CLIP_ATTR_FUNCS) == 10
+    needs = {"game": "Game_MM_CLIP", "rollout": "Game_MM_CLIP", "lrp": "CLIP_lrp", "surgery": "CLIP Surgery", "m2ib": "M2IB"}
+    for row, what in needs.items():
+        with pytest.raises(NotImplementedError, match=rf"{row}.*{what}"):
+            eclip.eclip_batch(None, None, None, row)
+        with pytest.raises(NotImplementedError, match=rf"{row}.*{what}"):
+            sweep.get_CLIP_attr(None, 0, {"attr_func": row})
+    with pytest.raises(ValueError, match="unknown row 'gradcam'"):
+        eclip.eclip_batch(None, None, None, "gradcam")
+    with pytest.raises(SystemExit):
+        sweep.get_CLIP_attr(None, 0, {"attr_func": "ig"})
+
+
+def test_a_model_without_the_layout_is_a_type_error_naming_the_attribute():
+    from xai_engine import eclip
+    m = zoo_model("short")
+    with pytest.raises(TypeError, match=r"Linear has no `visual`"):
+        eclip.check_layout(torch.nn.Linear(2, 2))
+    del m.visual.ln_post
+    with pytest.raises(TypeError, match=r"CLIP has no `visual\.ln_post`"):
+        eclip.clip_encode_dense(torch.zeros(1, 3, 32, 32), m)
+    m = zoo_model("short")
+    del m.visual.transformer.resblocks[-1].attn.in_proj_bias
+    with pytest.raises(TypeError, match=r"`visual\.transformer\.resblocks\[-1\]\.attn\.in_proj_bias`"):
+        eclip.eclip_batch(m, torch.zeros(1, 3, 32, 32), torch.zeros(1, 16), "eclip")
+
+
+def test_a_model_on_the_cpu_is_refused_by_the_pass_not_run_in_torch():
+    from xai_engine import eclip, _lib
+    with pytest.raises(_lib.XaiHipError, match="not a HIP GPU"):
+        eclip.eclip_batch(zoo_model("short"), torch.zeros(1, 3, 32, 32), torch.zeros(1, 16), "selfattn")
+
+
+def test_keepsize_preprocessing_on_a_uint8_valued_tensor():
+    """to_pil_image truncates `mul(255)` to a byte and ToTensor divides by 255.  On k / 255 inputs (what the harness loads from an
+    8-bit file) fl(fl(k / 255) * 255) is k for every k, so the round trip returns the image; a value between two levels is
+    truncated, not rounded (0.5 -> 127 / 255).  Then CLIP's Normalize, in fp32."""
+    from xai_engine import sweep
+    k = torch.arange(256, dtype=torch.float32).repeat(3, 4).reshape(3, 32, 32)
+    trans = k / 255
+    trans[0, 0, 0], trans[1, 0, 0] = 0.5, 0.99999
+    got = sweep.clip_keepsize_input(trans)
+    kk = k.numpy().copy()
+    kk[0, 0, 0], kk[1, 0, 0] = 127, 254
+    assert np.array_equal(np.trunc(trans.numpy() * np.float32(255)), kk)
+    mean = np.array(sweep.CLIP_MEAN, np.float32).reshape(3, 1, 1)
+    std = np.array(sweep.CLIP_STD, np.float32).reshape(3, 1, 1)
+    want = ((kk / np.float32(255)) - mean) / std
+    assert got.dtype == torch.float32 and tuple(got.shape) == (1, 3, 32, 32) and got.numpy().tobytes() == want[None].tobytes()
+    assert (sweep.CLIP_MEAN, sweep.CLIP_STD) == ((0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711))
+    with pytest.raises(NotImplementedError, match="bicubic"):
+        sweep.clip_keepsize_input(torch.zeros(3, 40, 32))
+    with pytest.raises(NotImplementedError, match="patch size"):
+        sweep.get_CLIP_attr(torch.zeros(3, 16, 16), 0, {"attr_func": "eclip", "models": [zoo_model("b32")], "img_hw": 16,
+                                                        "embeddings": torch.zeros(2, 16)})
+
+
+def test_clip_cli_is_a_module_of_its_own_and_the_three_older_clis_still_refuse_clip():
+    from xai_engine import evaluate_clip as cli, evaluate_perturbation, harness
+    assert list(cli.CLIP_MODELS) == ["CLIP16", "CLIP32"] and not [m for m in evaluate_perturbation.MODELS if "CLIP" in m]
+    assert [v[1:] for v in cli.CLIP_MODELS.values()] == [(25, (harness.CLIP_MEAN, harness.CLIP_STD), 14), (50, (harness.CLIP_MEAN, harness.CLIP_STD), 7)]
+    args = cli.build_parser().parse_args(["--model", "CLIP32", "--attr_func", "maskclip", "--clip_fp32", "--text_embeddings", "e.pt"])
+    assert (args.model, args.attr_func, args.clip_fp32, args.text_embeddings) == ("CLIP32", "maskclip", True, "e.pt")
+    d = cli.build_parser().parse_args([])
+    assert (d.model, d.attr_func, d.clip_fp32, d.text_embeddings, d.image_count) == ("CLIP16", "eclip", False, None, 1000)
+    with pytest.raises(SystemExit):
+        cli.main(["--model", "CLIP16", "--attr_func", "ig"])
+    for name in ("CLIP8", "R50", "VIT16"):
+        with pytest.raises(SystemExit, match=f"unknown --model {name}"):
+            cli.main(["--model", name])
+    with pytest.raises(SystemExit, match="unknown --model CLIP16"):
+        evaluate_perturbation.main(["--model", "CLIP16"])
+
+
+# ------------------------------------------------------------------------------------------------ the library and its header
+def built_clip():
+    """the path of libxai_clip.so, built first where it is absent"""
+    import subprocess
+    from xai_engine import _lib
+    path = _lib.DTYPE_LIBRARIES["clip"].path
+    if not os.path.exists(path):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "image-classification-xai_amd", "csrc"), "-j8"], check=True)
+    return path
+
+
+def test_clip_header_library_record_and_the_pin_at_1_0():
+    """libxai_clip.so is the one record of _lib.DTYPE_LIBRARIES (entries in _f32 and _f16), beside the eleven of LIBRARIES: header
+    include/xai_clip.h, source csrc/clip/clip_kernels.hip, built by csrc/Makefile's `all`, loaded by _lib.load("clip") and
+    version-checked by build()"""
+    from xai_engine import _lib
+    assert list(_lib.DTYPE_LIBRARIES) == ["clip"] and "clip" not in _lib.LIBRARIES and "_f16" in _lib._LAUNCH
+    rec = _lib.DTYPE_LIBRARIES["clip"]
+    assert isinstance(rec, _lib.Library) and os.path.basename(rec.path) == "libxai_clip.so"
+    assert os.path.samefile(rec.header_path, CLIP_HEADER) and (rec.version, rec.minor) == (1, 0)
+    assert rec.defines == ("XAI_CLIP_VERSION", "XAI_CLIP_MINOR") and rec.version_entries == ("xai_clip_version", "xai_clip_version_minor")
+    text = open(CLIP_HEADER).read()
+    assert re.search(r"^#define XAI_CLIP_VERSION 1$", text, flags=re.M) and re.search(r"^#define XAI_CLIP_MINOR 0$", text, flags=re.M)
+    names = sorted(ENTRIES + ["xai_clip_version", "xai_clip_version_minor"])
+    assert declared(CLIP_HEADER) == names == exported(built_clip()) == sorted(rec.signatures)
+    for other, orec in _lib.LIBRARIES.items():                    # my symbols are in no other library, and in no other header
+        assert not [n for n in exported(built(other)) if n in names or n.startswith("xai_clip_")], other
+        assert not set(names) & set(orec.signatures), other
+    lib = _lib.load("clip")
+    assert lib is rec.handle is _lib.load("clip")
+    assert (lib.xai_clip_version(), lib.xai_clip_version_minor()) == (1, 0)
+    assert (lib.xai_clip_max_tokens(), lib.xai_clip_max_width(), lib.xai_clip_max_texts()) == (4096, 8192, 1024)
+    assert 4 * (4096 + 8192) <= 48 * 1024                      # the LDS budget the header states
+    att = [_p, _p, _l, _l, _p, _l, _l, _i, _i, _i, _f, _p, _p, _p, _p]
+    ecl = [_p, _p, _l, _l, _p, _l, _l, _p, _i, _i, _i, _i, _i, _i, _p, _p]
+    msk = [_p, _p, _l, _p, _l, _l, _i, _i, _i, _i, _i, _p, _p]
+    for sfx in ("f32", "f16"):
+        assert rec.signatures[f"xai_clip_cls_attention_{sfx}"] == att
+        assert rec.signatures[f"xai_clip_eclip_map_{sfx}"] == ecl
+        assert rec.signatures[f"xai_clip_maskclip_map_{sfx}"] == msk
+        for name in (f"xai_clip_cls_attention_{sfx}", f"xai_clip_eclip_map_{sfx}", f"xai_clip_maskclip_map_{sfx}"):
+            assert list(getattr(lib, name).argtypes) == rec.signatures[name] and getattr(lib, name).restype is _i
+    make = open(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "Makefile")).read()
+    assert "clip/clip_kernels.hip" in make and os.path.exists(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "clip", "clip_kernels.hip"))
+    with pytest.raises(KeyError):
+        _lib.load("clip2")
+
+
+def test_loader_and_build_refuse_an_older_or_stale_clip_library(monkeypatch, tmp_path):
+    import __graft_entry__ as g
+    from xai_engine import _lib
+    rec = _lib.DTYPE_LIBRARIES["clip"]
+    real = built_clip()
+    for key in _lib.LIBRARIES:
+        built(key)
+    monkeypatch.setattr(rec, "handle", None)
+    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_clip.so"))
+    with pytest.raises(_lib.XaiHipError, match="not found"):
+        _lib.load("clip")
+    monkeypatch.setattr(rec, "path", real)
+    monkeypatch.setattr(rec, "minor", 1)                          # the package wants a later minor than the library has
+    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1.*\(include/xai_clip\.h\)"):
+        _lib.load("clip")
+    monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
+    with pytest.raises(_lib.XaiHipError, match=r"libxai_clip\.so has ABI 1\.0, this package needs 1\.1"):
+        g.build()                                                 # build() checks this library too
+    assert rec.handle is None
+    monkeypatch.setattr(rec, "minor", 0)
+    monkeypatch.setitem(rec.signatures, "xai_clip_not_in_the_library_f16", [_p])
+    monkeypatch.setitem(rec.restypes, "xai_clip_not_in_the_library_f16", _i)
+    with pytest.raises(AttributeError):
+        _lib.load("clip")
+    monkeypatch.undo()
+    assert _lib.load("clip") is rec.handle is not None
+
+
+def test_entries_refuse_bad_arguments_before_any_hip_call():
+    """the checks come first, so a refused call needs no device: null pointers, extents, strides, limits"""
+    from xai_engine import _lib
+    lib = _lib.load("clip")
+    NUL, SHAPE, UNSUP = -1, -2, -3
+    hdr = open(os.path.join(ROOT, "include", "xai_hip.h")).read()
+    for name, val in (("XAI_E_NULL", NUL), ("XAI_E_SHAPE", SHAPE), ("XAI_E_UNSUPPORTED", UNSUP)):
+        assert f"#define {name} ({val})" in hdr, name
+    buf = (C.c_float * 16)()
+    p = C.addressof(buf)
+    for sfx in ("f32", "f16"):
+        att = getattr(lib, f"xai_clip_cls_attention_{sfx}")
+        ecl = getattr(lib, f"xai_clip_eclip_map_{sfx}")
+        msk = getattr(lib, f"xai_clip_maskclip_map_{sfx}")
+        assert att(None, p, 4, 4, p, 4, 4, 1, 2, 4, 0.5, None, p, p, None) == NUL
+        assert att(p, p, 4, 4, p, 4, 4, 1, 2, 4, 0.5, None, None, p, None) == NUL
+        assert att(p, p, 4, 4, p, 4, 4, 1, 1, 4, 0.5, None, p, p, None) == SHAPE          # L >= 2
+        assert att(p, p, 4, 4, p, 4, 4, 0, 2, 4, 0.5, None, p, p, None) == SHAPE
+        assert att(p, p, 3, 4, p, 4, 4, 1, 2, 4, 0.5, None, p, p, None) == SHAPE          # a row stride below D
+        assert att(p, p, 8, 3, p, 8, 4, 2, 2, 4, 0.5, None, p, p, None) == SHAPE          # an image stride below D with B > 1
+        assert att(p, p, 8200, 8200, p, 8200, 8200, 1, 2, 8193, 0.5, None, p, p, None) == UNSUP
+        assert att(p, p, 4, 4, p, 4, 4, 1, 4097, 4, 0.5, None, p, p, None) == UNSUP
+        assert att(p, p, 4, 4, p, 4, 4, 65536, 2, 4, 0.5, None, p, p, None) == UNSUP
+        assert ecl(None, p, 4, 4, p, 4, 4, p, 1, 2, 4, 1, 1, 1, p, None) == NUL
+        assert ecl(p, p, 4, 4, p, 4, 4, None, 1, 2, 4, 1, 1, 1, p, None) == NUL      # withgrad needs grad_cls
+        assert ecl(p, p, 4, 4, None, 4, 4, None, 1, 2, 4, 1, 0, 0, p, None) == NUL   # v always
+        assert ecl(None, None, 0, 0, p, 4, 4, None, 1, 1, 4, 1, 0, 0, p, None) == SHAPE
+        assert ecl(p, p, 4, 4, p, 4, 4, p, 1, 2, 4, 0, 1, 1, p, None) == SHAPE       # T >= 1
+        assert ecl(p, p, 4, 4, p, 4, 4, p, 1, 2, 4, 1025, 1, 1, p, None) == UNSUP
+        assert msk(p, None, 0, p, 4, 4, 1, 2, 4, 4, 1, p, None) == NUL
+        assert msk(p, p, -1, p, 4, 4, 1, 2, 4, 4, 1, p, None) == SHAPE
+        assert msk(p, p, 0, p, 4, 4, 1, 2, 4, 0, 1, p, None) == SHAPE
+        assert msk(p, p, 0, p, 4, 4, 1, 2, 4, 8193, 1, p, None) == UNSUP
+
+
+def test_wrappers_refuse_what_is_no_device_tensor():
+    from xai_engine import kernels as K, _lib
+    t16 = torch.zeros(5, 1, 8, dtype=torch.float16)
+    with pytest.raises(TypeError, match="k: expected a torch.Tensor"):
+        K.clip_cls_attention(torch.zeros(1, 8), None, t16)
+    for call in (lambda: K.clip_cls_attention(t16[0], t16, t16), lambda: K.clip_eclip_map(t16[0], t16, t16, texts=1, withgrad=False),
+                 lambda: K.clip_maskclip_map(torch.zeros(1, 4, 8), torch.zeros(1, 8), t16)):
+        with pytest.raises(_lib.XaiHipError, match="HIP device only"):
+            call()

@@ -30,11 +30,6 @@ constexpr int kFelzMaxChains = 1 << 20;
 
 __host__ __device__ inline int felz_edges(int H, int W) { return H * (W - 1) + (H - 1) * W + 2 * (H - 1) * (W - 1); }
 
-__global__ void felz_clear_kernel(int32_t* __restrict__ status, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) status[i] = 0;
-}
-
 // ------------------------------------------------------------------------------------------------ K69
 __device__ __forceinline__ int felz_reflect(int idx, int n) {
   const int period = 2 * n;
@@ -152,23 +147,13 @@ __global__ __launch_bounds__(kFelzBlock) void felz_count_kernel(const uint64_t* 
 
 __global__ __launch_bounds__(kFelzScan) void felz_scan_kernel(uint32_t* __restrict__ counts, int total) {
   __shared__ uint32_t wsum[kFelzScan / kWave];
-  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  const int t = threadIdx.x;
   uint32_t* c = counts + static_cast<size_t>(blockIdx.x) * total;
   uint32_t run = 0;
   for (int base = 0; base < total; base += kFelzScan) {
     const int i = base + t;
-    const uint32_t v = i < total ? c[i] : 0u;
-    const uint32_t incl = wave_scan_incl(v);
-    if (lane == kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t pre = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kFelzScan / kWave; ++w) {
-      if (w < wave) pre += wsum[w];
-      sum += wsum[w];
-    }
-    if (i < total) c[i] = run + pre + incl - v;
-    run += sum;
+    const uint32_t below = block_scan_excl<kFelzScan>(i < total ? c[i] : 0u, run, wsum);
+    if (i < total) c[i] = below;
     __syncthreads();
   }
 }
@@ -376,24 +361,15 @@ __global__ __launch_bounds__(kWave) void felz_merge_kernel(const uint64_t* __res
 __global__ __launch_bounds__(kFelzScan) void felz_labels_kernel(const int32_t* __restrict__ roots, int n, int32_t* __restrict__ labels,
                                                                 int32_t* __restrict__ counts, int32_t* __restrict__ status) {
   __shared__ uint32_t wsum[kFelzScan / kWave];
-  const int m = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  const int m = blockIdx.x, t = threadIdx.x;
   const int32_t* rt = roots + static_cast<size_t>(m) * n;
   int32_t* lab = labels + static_cast<size_t>(m) * n;
   uint32_t run = 0;                                  // the roots below this pass
   for (int base = 0; base < n; base += kFelzScan) {
     const int p = base + t;
     const uint32_t flag = (p < n && rt[p] == p) ? 1u : 0u;
-    const uint32_t incl = wave_scan_incl(flag);
-    if (lane == kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t pre = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kFelzScan / kWave; ++w) {
-      if (w < wave) pre += wsum[w];
-      total += wsum[w];
-    }
-    if (flag) lab[p] = static_cast<int32_t>(run + pre + incl - 1);
-    run += total;
+    const uint32_t below = block_scan_excl<kFelzScan>(flag, run, wsum);
+    if (flag) lab[p] = static_cast<int32_t>(below);
     __syncthreads();
   }
   if (t == 0) counts[m] = static_cast<int32_t>(run);
@@ -422,10 +398,8 @@ int felz_check(int B, int H, int W) {
 
 int felz_chunks(int E) { return static_cast<int>(xai_ceil_div(E, kFelzChunk)); }
 
-size_t felz_align8(size_t v) { return (v + 7) & ~static_cast<size_t>(7); }
-
 size_t felz_sort_bytes(int B, int E) {
-  return felz_align8(static_cast<size_t>(B) * E * 8) + felz_align8(static_cast<size_t>(B) * E * 4) +
+  return xai_align_up(static_cast<size_t>(B) * E * 8, 8) + xai_align_up(static_cast<size_t>(B) * E * 4, 8) +
          static_cast<size_t>(B) * kFelzDigits * felz_chunks(E) * 4;
 }
 
@@ -452,8 +426,7 @@ XAI_EXPORT size_t xai_felz_workspace_bytes(int B, int H, int W, int S) {
 XAI_EXPORT int xai_felz_clear_i32(int32_t* status, int n, xai_stream_t stream) {
   XAI_REQUIRE_PTR(status);
   XAI_REQUIRE(n >= 1, XAI_E_SHAPE);
-  felz_clear_kernel<<<unsigned(xai_ceil_div(n, kFelzBlock)), kFelzBlock, 0, static_cast<hipStream_t>(stream)>>>(status, n);
-  return xai_launch_status();
+  return xai_clear_i32(status, n, static_cast<hipStream_t>(stream));
 }
 
 XAI_EXPORT int xai_felz_smooth_f64(const double* src, const double* weights, int radius, int axis, int B, int H, int W, int C, double* dst,
@@ -504,8 +477,8 @@ XAI_EXPORT int xai_felz_sort_u64(uint64_t* keys, int32_t* index, int B, int H, i
   const int nchunks = felz_chunks(E);
   char* w = static_cast<char*>(ws);
   uint64_t* keys_b = reinterpret_cast<uint64_t*>(w);
-  int32_t* index_b = reinterpret_cast<int32_t*>(w + felz_align8(static_cast<size_t>(B) * E * 8));
-  uint32_t* counts = reinterpret_cast<uint32_t*>(w + felz_align8(static_cast<size_t>(B) * E * 8) + felz_align8(static_cast<size_t>(B) * E * 4));
+  int32_t* index_b = reinterpret_cast<int32_t*>(w + xai_align_up(static_cast<size_t>(B) * E * 8, 8));
+  uint32_t* counts = reinterpret_cast<uint32_t*>(w + xai_align_up(static_cast<size_t>(B) * E * 8, 8) + xai_align_up(static_cast<size_t>(B) * E * 4, 8));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(unsigned(xai_ceil_div(nchunks, kFelzBlock / kWave)), unsigned(B));
   uint64_t* kin = keys;

@@ -170,14 +170,9 @@ __global__ __launch_bounds__(kSelectThreads) void mda_select_kernel(const float*
     const int32_t s = order_i[j];
     cnt += (s >= 0 && s < S && taken_i[s] == 0) ? 1u : 0u;
   }
-  const uint32_t incl = wave_scan_incl(cnt);
-  if ((t & (kWave - 1)) == kWave - 1) s_wsum[t / kWave] = incl;
-  __syncthreads();
-  uint32_t rank = incl - cnt, total = 0;
-  for (int w = 0; w < kSelectWaves; ++w) {
-    if (w < t / kWave) rank += s_wsum[w];
-    total += s_wsum[w];
-  }
+  // one pass, and nothing writes s_wsum after it: no barrier behind the scan
+  uint32_t total = 0;
+  uint32_t rank = block_scan_excl<kSelectThreads>(cnt, total, s_wsum);
   for (int j = lo; j < hi && rank < static_cast<uint32_t>(n_next); ++j) {
     const int32_t s = order_i[j];
     if (s >= 0 && s < S && taken_i[s] == 0) cand_i[rank++] = s;

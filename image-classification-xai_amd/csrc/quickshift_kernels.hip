@@ -25,7 +25,6 @@ constexpr size_t kQsLdsCap = 65536;
 constexpr double kQsMaxKernelSize = 10000.0;
 constexpr int kQsThreads = 256;     // K55's element-wise launches
 constexpr int kQsScanThreads = 1024;  // K55's one workgroup per image
-constexpr int kQsScanWaves = kQsScanThreads / kWave;
 
 // The tile plus halo of one workgroup: plane ch of `lds` is [TW][TW] doubles, TW = kQsTile + 2 kw, origin at pixel (r0, c0) of the image.
 // Cells outside the image are never read by a window (it is clipped to the image); they are set to 0.
@@ -148,25 +147,16 @@ __global__ __launch_bounds__(kQsThreads) void roots_kernel(const int32_t* __rest
 
 __global__ __launch_bounds__(kQsScanThreads) void scan_kernel(const int32_t* __restrict__ root, int n, int32_t* __restrict__ scan,
                                                               int32_t* __restrict__ D) {
-  __shared__ uint32_t wsum[kQsScanWaves];
-  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  __shared__ uint32_t wsum[kQsScanThreads / kWave];
+  const int t = threadIdx.x;
   const int32_t* rt = root + static_cast<int64_t>(blockIdx.x) * n;
   int32_t* sc = scan + static_cast<int64_t>(blockIdx.x) * n;
   uint32_t carry = 0;
   for (int64_t base = 0; base < n; base += kQsScanThreads) {
     const int64_t i = base + t;
     const uint32_t flag = (i < n && rt[i] == static_cast<int32_t>(i)) ? 1u : 0u;
-    const uint32_t incl = wave_scan_incl(flag);
-    if (lane == kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t pre = carry, total = 0;
-#pragma unroll
-    for (int k = 0; k < kQsScanWaves; ++k) {
-      if (k < wave) pre += wsum[k];
-      total += wsum[k];
-    }
-    if (i < n) sc[i] = static_cast<int32_t>(pre + incl - flag);
-    carry += total;
+    const uint32_t below = block_scan_excl<kQsScanThreads>(flag, carry, wsum);
+    if (i < n) sc[i] = static_cast<int32_t>(below);
     __syncthreads();
   }
   if (t == 0) D[blockIdx.x] = static_cast<int32_t>(carry);

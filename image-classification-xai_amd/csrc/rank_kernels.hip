@@ -114,7 +114,8 @@ __global__ __launch_bounds__(kBins) void rank_scan_kernel(int64_t hw, int n_tile
     for (int u = 0; u < 8; ++u) total += c[u];
   }
   for (; t < n_tiles; ++t) total += hist[t * kBins + d];
-  const uint32_t incl = wave_scan_incl(total);            // exclusive scan of the 256 digit totals
+  // exclusive scan of the 256 digit totals; not block_scan_excl: one value per lane, once, needs no second barrier
+  const uint32_t incl = wave_scan_incl(total);
   if (lane == 63) wsum[wave] = incl;
   const bool one_bin = __any(total == static_cast<uint32_t>(hw));
   __syncthreads();

@@ -53,11 +53,6 @@ __device__ __forceinline__ void slic_bounds(T c, T two_step, int n, int& lo, int
   hi = static_cast<int>(b);
 }
 
-__global__ void slic_clear_kernel(int32_t* __restrict__ status, int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) status[b] = 0;
-}
-
 // ------------------------------------------------------------------------------------------------ K65
 template <typename T>
 __global__ __launch_bounds__(kSlicList) void slic_assign_kernel(const T* __restrict__ features, const T* __restrict__ centres, int H, int W,
@@ -262,7 +257,7 @@ __global__ __launch_bounds__(kSlicCc) void slic_components_kernel(const int32_t*
 __global__ __launch_bounds__(kSlicCc) void slic_number_kernel(const int32_t* __restrict__ comp, int n, int start_label, int32_t* __restrict__ out,
                                                               int32_t* __restrict__ nlabels, int32_t* ranks) {
   __shared__ uint32_t wsum[kSlicCc / kWave];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  const int b = blockIdx.x, t = threadIdx.x;
   const size_t image = static_cast<size_t>(b) * n;
   const int32_t* cm = comp + image;
   int32_t* rank = ranks + image;
@@ -270,17 +265,8 @@ __global__ __launch_bounds__(kSlicCc) void slic_number_kernel(const int32_t* __r
   for (int base = 0; base < n; base += kSlicCc) {
     const int p = base + t;
     const uint32_t flag = (p < n && cm[p] == p) ? 1u : 0u;
-    const uint32_t incl = wave_scan_incl(flag);
-    if (lane == kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t pre = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kSlicCc / kWave; ++w) {
-      if (w < wave) pre += wsum[w];
-      total += wsum[w];
-    }
-    if (flag) rank[p] = static_cast<int32_t>(run + pre + incl - 1);
-    run += total;
+    const uint32_t below = block_scan_excl<kSlicCc>(flag, run, wsum);
+    if (flag) rank[p] = static_cast<int32_t>(below);
     __syncthreads();
   }
   if (t == 0) nlabels[b] = static_cast<int32_t>(run);
@@ -322,11 +308,6 @@ int slic_update(const T* features, const int32_t* labels, int B, int H, int W, i
   return xai_launch_status();
 }
 
-int slic_clear(int32_t* status, int B, hipStream_t s) {
-  slic_clear_kernel<<<unsigned(xai_ceil_div(B, 256)), 256, 0, s>>>(status, B);
-  return xai_launch_status();
-}
-
 template <typename T>
 int slic_assign_entry(const T* features, const T* centres, int B, int H, int W, int C, int S, int step, int32_t* labels, int32_t* status,
                       xai_stream_t stream) {
@@ -362,7 +343,7 @@ int slic_iterate_entry(const T* features, int B, int H, int W, int C, int S, int
   if (rc != XAI_OK) return rc;
   XAI_REQUIRE(iterations >= 1, XAI_E_SHAPE);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int st = slic_clear(status, B, s);
+  int st = xai_clear_i32(status, B, s);
   for (int it = 0; it < iterations && st == XAI_OK; ++it) {
     st = slic_assign<T>(features, centres, B, H, W, C, S, step, labels, status, s);
     if (st == XAI_OK) st = slic_update<T>(features, labels, B, H, W, C, S, step, centres, status, s);
@@ -384,7 +365,7 @@ XAI_EXPORT size_t xai_slic_workspace_bytes(int B, int H, int W) {
 XAI_EXPORT int xai_slic_clear_i32(int32_t* status, int B, xai_stream_t stream) {
   XAI_REQUIRE_PTR(status);
   XAI_REQUIRE(B >= 1, XAI_E_SHAPE);
-  return slic_clear(status, B, static_cast<hipStream_t>(stream));
+  return xai_clear_i32(status, B, static_cast<hipStream_t>(stream));
 }
 
 XAI_EXPORT int xai_slic_assign_f32(const float* features, const float* centres, int B, int H, int W, int C, int S, int step, int32_t* labels,

@@ -41,6 +41,8 @@ static inline bool xai_can_vec4(int64_t n, std::initializer_list<const void*> pt
 }
 
 static inline int64_t xai_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// n rounded up to a multiple of `to`, a power of two: the parts of a workspace
+static inline size_t xai_align_up(size_t n, size_t to) { return (n + to - 1) & ~(to - 1); }
 
 // ---- host launch blocks: DESIGN.md ("Host launch blocks") has the rule for what may be shared.
 // f(std::true_type) or f(std::false_type): a launch written once in a generic lambda names its kernel from the constant,
@@ -114,6 +116,45 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
     if (lane >= off) v += up;
   }
   return v;
+}
+
+// Streamed exclusive prefix sum of one value per lane over a workgroup of THREADS lanes -> `run` (on entry) plus the sum of v over
+// the lanes below this one; `run` grows by the sum over the workgroup, the same in every lane, so a loop that walks an array THREADS
+// elements a pass calls this once per pass.  wave_scan_incl inside a wave, the waves' totals through `wsum`: THREADS / 64 words,
+// whatever is in them.  All lanes of the workgroup must call.
+// Of the scan's two barriers one is inside, between the waves' totals written to `wsum` and their reads.  The other is the
+// caller's: `wsum` is being read until the workgroup's next barrier, so a loop ends its pass with __syncthreads() behind its own
+// store (which that barrier also shows to the workgroup), and `wsum` is free again from there; one call whose `wsum` nothing
+// writes afterwards needs none.  Inside, that barrier would stand between the ranks and their store and cost every pass the
+// time of the sums (profiles/r22_scan_blocks.txt).
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t& run, uint32_t* wsum) {
+  static_assert(THREADS % kWave == 0, "whole waves");
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const uint32_t incl = wave_scan_incl(v);
+  if (lane == kWave - 1) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t pre = run + incl - v, total = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / kWave; ++w) {
+    if (w < wave) pre += wsum[w];
+    total += wsum[w];
+  }
+  run += total;
+  return pre;
+}
+
+// ptr[0..n) = 0 on `stream`, n >= 1: the status words of the segmenters.  -> xai_launch_status()
+// Templates, so that only the files that clear anything carry the kernel.
+template <int BLOCK>
+__global__ void clear_i32_kernel(int32_t* __restrict__ ptr, int n) {
+  const int i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < n) ptr[i] = 0;
+}
+template <int BLOCK = 256>
+static inline int xai_clear_i32(int32_t* ptr, int n, hipStream_t stream) {
+  clear_i32_kernel<BLOCK><<<unsigned(xai_ceil_div(n, BLOCK)), BLOCK, 0, stream>>>(ptr, n);
+  return xai_launch_status();
 }
 
 // argmax order of torch.max on the CPU: the first NaN if there is one, else the first maximal value.
@@ -216,7 +257,7 @@ __device__ __forceinline__ uint32_t select_digit(const uint32_t* hist, uint32_t&
   static_assert(THREADS % kWave == 0, "whole waves");
   const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
   const uint32_t c0 = hist[2 * t], c1 = hist[2 * t + 1], c = c0 + c1;
-  const uint32_t incl = wave_scan_incl(c);
+  const uint32_t incl = wave_scan_incl(c);             // not block_scan_excl: the `pick` exchange sits between the scan's two barriers
   if (lane == kWave - 1) wsum[wave] = incl;
   __syncthreads();
   uint32_t pre = incl - c;

@@ -354,13 +354,11 @@ __global__ __launch_bounds__(kRankBlock) void rank_kernel(RankArgs a) {
   }
 }
 
-inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
-
 }  // namespace
 
 XAI_EXPORT size_t xai_xrai_workspace_bytes(int n_img, int H, int W, int64_t M_total) {
   if (n_img < 1 || H < 1 || W < 1 || M_total < 0) return 0;
-  return 3 * align16(static_cast<size_t>(M_total > 0 ? M_total : 1) * 4);       // cached counts, cached gains, the fast order
+  return 3 * xai_align_up(static_cast<size_t>(M_total > 0 ? M_total : 1) * 4, 16);       // cached counts, cached gains, the fast order
 }
 
 XAI_EXPORT int xai_xrai_pack_u64(const int32_t* labels, const int32_t* label_min, const int32_t* label_max, int S,
@@ -406,7 +404,7 @@ XAI_EXPORT int xai_xrai_rank_f32(const float* attr, const uint64_t* bits, const 
   const int64_t hw = static_cast<int64_t>(H) * W;
   XAI_REQUIRE(hw <= static_cast<int64_t>(kMaxWords) * 64 && M_total <= INT32_MAX && n_img <= 65535 * 32, XAI_E_UNSUPPORTED);
   XAI_REQUIRE(workspace_bytes >= xai_xrai_workspace_bytes(n_img, H, W, M_total) && xai_aligned16(workspace), XAI_E_SHAPE);
-  const size_t part = align16(static_cast<size_t>(M_total > 0 ? M_total : 1) * 4);
+  const size_t part = xai_align_up(static_cast<size_t>(M_total > 0 ? M_total : 1) * 4, 16);
   char* ws = static_cast<char*>(workspace);
   RankArgs a;
   a.attr = attr;

@@ -13,16 +13,23 @@ F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64,
 F16 = torch.float16
 
 
+def _typed(t, dtype, name):
+    """The half of _need that asks no device: a tensor of `dtype` (a tuple: one of them).  On its own in the wrappers that report
+    the device last, after every refusal a host can test (shape, limits); _need follows there."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        raise TypeError(f"{name}: expected {' or '.join(map(str, dtype)) if isinstance(dtype, tuple) else dtype}, got {t.dtype}")
+    return t
+
+
 def _need(t, dtype, name, rows=False):
     """The shared argument check: a tensor, on a HIP device, of `dtype` (a tuple: one of them), contiguous (rows: in its last
     axis, the other strides are passed on)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
-    if not t.is_cuda:
+    if isinstance(t, torch.Tensor) and not t.is_cuda:
         raise _lib.XaiHipError(f"{name} lives on '{t.device}': the xai_engine kernels run on a HIP device only "
                                "(pass device='cuda:N'); there is no CPU fallback")
-    if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
-        raise TypeError(f"{name}: expected {' or '.join(map(str, dtype)) if isinstance(dtype, tuple) else dtype}, got {t.dtype}")
+    _typed(t, dtype, name)
     if rows:
         if t.dim() < 1 or (t.shape[-1] > 1 and t.stride(-1) != 1):
             raise ValueError(f"{name} must be contiguous in its last axis")
@@ -68,10 +75,16 @@ def _out(t, name, shape, like, wrong=None, dtype=F32, alloc=torch.empty):
     return t
 
 
-def _workspace(entry, dev, *extents, lib="hip", required=False):
+def _workspace(entry, dev, *extents, lib="hip", required=False, ws=None, wrong=None):
     """-> (uint8 device scratch of `entry`(*extents) bytes, or None for 0 bytes; the byte count).  `entry` is a *_workspace_bytes
-    of library `lib`; required: 0 bytes there means the extents are refused, not that no scratch is needed."""
+    of library `lib`; required: 0 bytes there means the extents are refused, not that no scratch is needed.  `ws`: the caller's
+    scratch instead of a new one, uint8 on `dev` and at least that long, else ValueError(wrong)."""
     nbytes = int(getattr(_lib.load(lib), entry)(*extents))
+    if ws is not None:
+        _need(ws, U8, "ws")
+        if ws.device != dev or ws.numel() < nbytes:
+            raise ValueError(wrong)
+        return ws, nbytes
     if required and nbytes <= 0:
         raise ValueError(f"{entry}{extents}: no such workspace (an extent is not positive, or too large)")
     return (torch.empty(nbytes, dtype=U8, device=dev) if nbytes else None), nbytes
@@ -83,6 +96,46 @@ def _shaped_like(t, like, name, like_name, dtype=F32):
         _need(t, dtype, name)
         if t.shape != like.shape:
             raise ValueError(f"{name} must have the shape of {like_name}")
+
+
+def _int(v, name, least=None):
+    """A Python int (no bool, no float), at least `least`"""
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
+    if least is not None and v < least:
+        raise ValueError(f"{name} must be >= {least}, got {v}")
+    return v
+
+
+def _suffix(t):
+    """The ending of the entry of t's dtype, in the libraries that have one entry per dtype"""
+    return {F16: "f16", F32: "f32", F64: "f64"}[t.dtype]
+
+
+def _bhwc(t, dtype, name):
+    """t (B, H, W, C) of `dtype` with at least one element -> (B, H, W, C) as ints.  The front half of a segmenter's image check:
+    its own limits come next, then _need for the device and the contiguity."""
+    _typed(t, dtype, name)
+    if t.dim() != 4 or t.numel() == 0:
+        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(t.shape)}")
+    return tuple(int(v) for v in t.shape)
+
+
+def _status(lib, status, n=None, dev=None, count=None):
+    """The int32 status words of library `lib`.  None: `n` new ones on `dev`, cleared by the library's xai_<lib>_clear_i32.  A
+    caller's: with `n`, exactly n of them on `dev`, returned as they are; without, at least one, cleared."""
+    if status is None:
+        status = torch.empty(n, dtype=I32, device=dev)
+    else:
+        _need(status, I32, "status")
+        if n is not None:
+            if status.numel() != n or status.device != dev:
+                raise ValueError(f"status must hold {count or n} int32 on the device of its images")
+            return status
+        if status.numel() < 1:
+            raise ValueError("status must hold at least one int32")
+    _call(f"xai_{lib}_clear_i32", status.device, _ptr(status), status.numel(), lib=lib)
+    return status
 
 
 # ------------------------------------------------------------------------------ IG
@@ -1520,16 +1573,10 @@ def quickshift_lds_bytes(C, kernel_size):
     return _lib.load("ext5").xai_quickshift_lds_bytes(int(C), float(kernel_size))
 
 
-def _quickshift_shape(features, name="features"):
-    _need(features, F64, name)
-    if features.dim() != 4 or features.numel() == 0:
-        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(features.shape)}")
-    return tuple(features.shape)
-
-
 def quickshift_density(features, noise, kernel_size, out=None):
     """K53: features (B, H, W, C) fp64, noise (B, H, W) fp64 -> the densities (B, H, W) fp64, the tie noise added"""
-    B, H, W, C = _quickshift_shape(features)
+    B, H, W, C = _bhwc(features, F64, "features")
+    _need(features, F64, "features")
     _need(noise, F64, "noise")
     if tuple(noise.shape) != (B, H, W):
         raise ValueError(f"noise must be {(B, H, W)}, got {tuple(noise.shape)}")
@@ -1541,7 +1588,8 @@ def quickshift_density(features, noise, kernel_size, out=None):
 def quickshift_parent(features, dens, kernel_size, max_dist, want_tree=False):
     """K54: -> (parent (B, H, W) int32 with the max_dist cut, closest (B, H, W) fp64, dist = sqrt(closest), tree): tree is the
     parent before the cut (skimage's return_tree) with `want_tree`, else None"""
-    B, H, W, C = _quickshift_shape(features)
+    B, H, W, C = _bhwc(features, F64, "features")
+    _need(features, F64, "features")
     _need(dens, F64, "dens")
     if tuple(dens.shape) != (B, H, W):
         raise ValueError(f"dens must be {(B, H, W)}, got {tuple(dens.shape)}")
@@ -1562,8 +1610,9 @@ def quickshift_labels(parent, labels=None):
     B, H, W = parent.shape
     labels = _out(labels, "labels", (B, H, W), parent, dtype=I32)
     D = torch.empty((B,), dtype=I32, device=parent.device)
-    nbytes = _lib.load("ext5").xai_quickshift_workspace_bytes(B, H, W)
-    ws = torch.empty(max(nbytes, 4), dtype=U8, device=parent.device)
+    ws, _ = _workspace("xai_quickshift_workspace_bytes", parent.device, B, H, W, lib="ext5")
+    if ws is None:                                         # 0 bytes: a shape the entry refuses; it says how, given an address
+        ws = torch.empty(4, dtype=U8, device=parent.device)
     _call("xai_quickshift_labels_i32", parent.device, _ptr(parent), B, H, W, _ptr(labels), _ptr(D), _ptr(ws), ws.numel(), lib="ext5")
     return labels, D
 
@@ -1578,10 +1627,7 @@ def linkage_max_n():
 
 
 def _linkage_n(distance):
-    if not isinstance(distance, torch.Tensor):
-        raise TypeError(f"distance: expected a torch.Tensor, got {type(distance).__name__}")
-    if distance.dtype != F32:
-        raise TypeError(f"distance: expected {F32}, got {distance.dtype}")
+    _typed(distance, F32, "distance")
     if distance.dim() != 2 or distance.shape[0] != distance.shape[1]:
         raise ValueError(f"distance must be (n, n), got {tuple(distance.shape)}")
     n = int(distance.shape[0])
@@ -1596,7 +1642,7 @@ def _linkage_n(distance):
 def linkage_workspace(distance):
     """The scratch K56 fills and K57 reads: uint8, xai_linkage_workspace_bytes(n) bytes"""
     n = _linkage_n(distance)
-    return torch.empty(_lib.load("ext6").xai_linkage_workspace_bytes(n), dtype=U8, device=distance.device)
+    return _workspace("xai_linkage_workspace_bytes", distance.device, n, lib="ext6")[0]
 
 
 def linkage_complete(distance, ws, info, lanes=0):
@@ -1639,21 +1685,16 @@ def kmeans_limits():
 
 def _kmeans_extents(points, k):
     """points (n, d) fp32 contiguous on a HIP device and 1 <= k <= n inside THE LIMITS -> (n, d, k); the one check of every wrapper"""
-    if not isinstance(points, torch.Tensor):
-        raise TypeError(f"points: expected a torch.Tensor, got {type(points).__name__}")
-    if points.dtype != F32:
-        raise TypeError(f"points: expected {F32}, got {points.dtype}")
+    _typed(points, F32, "points")
     if points.dim() != 2 or points.shape[0] < 1 or points.shape[1] < 1:
         raise ValueError(f"points must be (n, d) with n, d >= 1, got {tuple(points.shape)}")
-    if isinstance(k, bool) or not isinstance(k, int):
-        raise TypeError(f"n_clusters: expected an int, got {type(k).__name__}")
     n, d = int(points.shape[0]), int(points.shape[1])
-    if not 1 <= k <= n:
+    if not 1 <= _int(k, "n_clusters") <= n:
         raise ValueError(f"n_clusters must be in [1, n = {n}], got {k}")
     cap = kmeans_limits()
     if n > cap[0] or d > cap[1] or k > cap[2]:
         raise ValueError(f"(n, d, k) = ({n}, {d}, {k}) is over THE LIMITS {cap} (include/xai_hip_ext7.h)")
-    if not points.is_contiguous():
+    if not points.is_contiguous():                         # said here, ahead of _need: the device is reported last
         raise ValueError("points must be contiguous")
     _need(points, F32, "points")
     return n, d, k
@@ -1666,15 +1707,14 @@ def _kmeans_buffers(points, n, d, k, C, ws, state, assign=None, counts=None):
             _need(t, dtype, name)
             if t.numel() != numel or t.device != points.device:
                 raise ValueError(f"{name} must hold {numel} elements on the device of points")
-    _need(ws, U8, "ws")
-    if ws.device != points.device or ws.numel() < _lib.load("ext7").xai_kmeans_workspace_bytes(n, d, k):
-        raise ValueError("ws must be kmeans_workspace(points, k) on the device of points")
+    _workspace("xai_kmeans_workspace_bytes", points.device, n, d, k, lib="ext7", ws=_typed(ws, U8, "ws"),
+               wrong="ws must be kmeans_workspace(points, k) on the device of points")
 
 
 def kmeans_workspace(points, k):
     """The scratch of K58-K61 (e_j, xx_i, cc_j): uint8, xai_kmeans_workspace_bytes(n, d, k) bytes"""
     n, d, k = _kmeans_extents(points, k)
-    return torch.empty(_lib.load("ext7").xai_kmeans_workspace_bytes(n, d, k), dtype=U8, device=points.device)
+    return _workspace("xai_kmeans_workspace_bytes", points.device, n, d, k, lib="ext7")[0]
 
 
 def kmeans_init(points, first, C, ws, state):
@@ -1697,11 +1737,7 @@ def kmeans_assign(points, C, assign, ws, state):
 
 
 def _kmeans_stop(max_iter, tol):
-    if isinstance(max_iter, bool) or not isinstance(max_iter, int):
-        raise TypeError(f"max_iter: expected an int, got {type(max_iter).__name__}")
-    if max_iter < 1:
-        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
-    return max_iter, float(tol)
+    return _int(max_iter, "max_iter", 1), float(tol)
 
 
 def kmeans_update(points, C, assign, counts, ws, state, max_iter, tol):
@@ -1738,13 +1774,7 @@ def slic_limits():
 
 def _slic_shape(features, name="features"):
     """features (B, H, W, C) float32 or float64, contiguous, on a HIP device, inside THE LIMITS -> (B, H, W, C)"""
-    if not isinstance(features, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor, got {type(features).__name__}")
-    if features.dtype not in (F32, F64):
-        raise TypeError(f"{name}: expected {F32} or {F64}, got {features.dtype}")
-    if features.dim() != 4 or features.numel() == 0:
-        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(features.shape)}")
-    B, H, W, C = (int(v) for v in features.shape)
+    B, H, W, C = _bhwc(features, (F32, F64), name)
     cap = slic_limits()
     if C > cap[1] or H * W > cap[2] or B > 65535 or H > 16 * 65535:
         raise ValueError(f"(B, H * W, C) = ({B}, {H * W}, {C}) is over THE LIMITS (65535, {cap[2]}, {cap[1]}), or H = {H} is over "
@@ -1755,8 +1785,7 @@ def _slic_shape(features, name="features"):
 
 def _slic_centres(centres, features, B, C):
     """centres (B, S, 2 + C) of the features' dtype on their device, 1 <= S <= the limit -> S"""
-    if not isinstance(centres, torch.Tensor):
-        raise TypeError(f"centres: expected a torch.Tensor, got {type(centres).__name__}")
+    _typed(centres, features.dtype, "centres")
     if centres.dim() != 3 or centres.shape[0] != B or centres.shape[1] < 1 or centres.shape[2] != 2 + C:
         raise ValueError(f"centres must be (B, S, 2 + C) = ({B}, S >= 1, {2 + C}), got {tuple(centres.shape)}")
     S = int(centres.shape[1])
@@ -1766,14 +1795,6 @@ def _slic_centres(centres, features, B, C):
     if centres.device != features.device:
         raise ValueError("centres must be on the device of features")
     return S
-
-
-def _slic_int(v, name, least):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
-    if v < least:
-        raise ValueError(f"{name} must be >= {least}, got {v}")
-    return v
 
 
 def _slic_image_ints(t, name, like=None):
@@ -1786,13 +1807,6 @@ def _slic_image_ints(t, name, like=None):
     return tuple(int(v) for v in t.shape)
 
 
-def _slic_status(status, B, like):
-    _need(status, I32, "status")
-    if status.numel() != B or status.device != like.device:
-        raise ValueError(f"status must hold {B} int32 on the device of its images")
-    return status
-
-
 def _slic_apart(a, b, name_a, name_b):
     """K67 and K68 read other pixels of their input while they write their output: the two may share no byte"""
     lo_a, lo_b = a.data_ptr(), b.data_ptr()
@@ -1800,17 +1814,9 @@ def _slic_apart(a, b, name_a, name_b):
         raise ValueError(f"{name_a} must not overlap {name_b}")
 
 
-def _slic_suffix(t):
-    return "f32" if t.dtype == F32 else "f64"
-
-
 def slic_clear(status):
     """status (B,) int32 = 0, by a kernel"""
-    _need(status, I32, "status")
-    if status.numel() < 1:
-        raise ValueError("status must hold at least one int32")
-    _call("xai_slic_clear_i32", status.device, _ptr(status), status.numel(), lib="slic")
-    return status
+    return _status("slic", _typed(status, I32, "status"))
 
 
 def slic_assign(features, centres, step, labels=None, status=None):
@@ -1818,12 +1824,12 @@ def slic_assign(features, centres, step, labels=None, status=None):
     UNCOVERED bit of status[b] where none does.  `status` None: a new, cleared word per image."""
     B, H, W, C = _slic_shape(features)
     S = _slic_centres(centres, features, B, C)
-    step = _slic_int(step, "step", 1)
+    step = _int(step, "step", 1)
     if labels is None:
         labels = torch.empty((B, H, W), dtype=I32, device=features.device)
     _slic_image_ints(labels, "labels", features)
-    status = slic_clear(torch.empty(B, dtype=I32, device=features.device)) if status is None else _slic_status(status, B, features)
-    _call(f"xai_slic_assign_{_slic_suffix(features)}", features.device, _ptr(features), _ptr(centres), B, H, W, C, S, step, _ptr(labels),
+    status = _status("slic", status, B, features.device)
+    _call(f"xai_slic_assign_{_suffix(features)}", features.device, _ptr(features), _ptr(centres), B, H, W, C, S, step, _ptr(labels),
           _ptr(status), lib="slic")
     return labels, status
 
@@ -1833,10 +1839,10 @@ def slic_update(features, labels, centres, step, status=None):
     order; the EMPTY bit of status[b] for a cluster without a pixel (its centre becomes NaN)"""
     B, H, W, C = _slic_shape(features)
     S = _slic_centres(centres, features, B, C)
-    step = _slic_int(step, "step", 1)
+    step = _int(step, "step", 1)
     _slic_image_ints(labels, "labels", features)
-    status = slic_clear(torch.empty(B, dtype=I32, device=features.device)) if status is None else _slic_status(status, B, features)
-    _call(f"xai_slic_update_{_slic_suffix(features)}", features.device, _ptr(features), _ptr(labels), B, H, W, C, S, step, _ptr(centres),
+    status = _status("slic", status, B, features.device)
+    _call(f"xai_slic_update_{_suffix(features)}", features.device, _ptr(features), _ptr(labels), B, H, W, C, S, step, _ptr(centres),
           _ptr(status), lib="slic")
     return centres, status
 
@@ -1846,13 +1852,13 @@ def slic_iterate(features, centres, step, iterations, labels=None, status=None):
     status); centres is updated in place"""
     B, H, W, C = _slic_shape(features)
     S = _slic_centres(centres, features, B, C)
-    step = _slic_int(step, "step", 1)
-    iterations = _slic_int(iterations, "max_iter", 1)
+    step = _int(step, "step", 1)
+    iterations = _int(iterations, "max_iter", 1)
     if labels is None:
         labels = torch.empty((B, H, W), dtype=I32, device=features.device)
     _slic_image_ints(labels, "labels", features)
-    status = torch.empty(B, dtype=I32, device=features.device) if status is None else _slic_status(status, B, features)
-    _call(f"xai_slic_iterate_{_slic_suffix(features)}", features.device, _ptr(features), B, H, W, C, S, step, iterations, _ptr(centres),
+    status = torch.empty(B, dtype=I32, device=features.device) if status is None else _status("slic", status, B, features.device)
+    _call(f"xai_slic_iterate_{_suffix(features)}", features.device, _ptr(features), B, H, W, C, S, step, iterations, _ptr(centres),
           _ptr(labels), _ptr(status), lib="slic")
     return labels, status
 
@@ -1860,30 +1866,23 @@ def slic_iterate(features, centres, step, iterations, labels=None, status=None):
 def slic_workspace(labels):
     """The scratch of K67 and K68: uint8, xai_slic_workspace_bytes(B, H, W) bytes"""
     B, H, W = _slic_image_ints(labels, "labels")
-    ws, _ = _workspace("xai_slic_workspace_bytes", labels.device, B, H, W, lib="slic", required=True)
-    return ws
+    return _workspace("xai_slic_workspace_bytes", labels.device, B, H, W, lib="slic", required=True)[0]
 
 
-def _slic_ws(ws, t, B, H, W):
-    if ws is None:
-        return slic_workspace(t)
-    _need(ws, U8, "ws")
-    if ws.device != t.device or ws.numel() < _lib.load("slic").xai_slic_workspace_bytes(B, H, W):
-        raise ValueError("ws must be slic_workspace(labels) on the device of labels")
-    return ws
+_SLIC_WS = "ws must be slic_workspace(labels) on the device of labels"
 
 
 def slic_components(labels, min_size, max_size, status=None, ws=None, comp=None):
     """K67: comp (B, H, W) int32 = the least flat index of each pixel's 4-connected component of equal label; the IRREGULAR bit of
     status[b] when a component's size is outside [min_size, max_size) or the sweeps ran out.  A given `comp` may not overlap labels."""
     B, H, W = _slic_image_ints(labels, "labels")
-    min_size = _slic_int(min_size, "min_size", 0)
-    max_size = _slic_int(max_size, "max_size", min_size)
-    ws = _slic_ws(ws, labels, B, H, W)
+    min_size = _int(min_size, "min_size", 0)
+    max_size = _int(max_size, "max_size", min_size)
+    ws, _ = _workspace("xai_slic_workspace_bytes", labels.device, B, H, W, lib="slic", required=True, ws=ws, wrong=_SLIC_WS)
     comp = torch.empty_like(labels) if comp is None else comp
     _slic_image_ints(comp, "comp", labels)
     _slic_apart(comp, labels, "comp", "labels")
-    status = slic_clear(torch.empty(B, dtype=I32, device=labels.device)) if status is None else _slic_status(status, B, labels)
+    status = _status("slic", status, B, labels.device)
     _call("xai_slic_components_i32", labels.device, _ptr(labels), B, H, W, min_size, max_size, _ptr(comp), _ptr(status), _ptr(ws),
           ws.numel(), lib="slic")
     return comp
@@ -1895,7 +1894,7 @@ def slic_number(comp, start_label=0, ws=None, out=None):
     B, H, W = _slic_image_ints(comp, "comp")
     if start_label not in (0, 1):
         raise ValueError("start_label should be 0 or 1.")
-    ws = _slic_ws(ws, comp, B, H, W)
+    ws, _ = _workspace("xai_slic_workspace_bytes", comp.device, B, H, W, lib="slic", required=True, ws=ws, wrong=_SLIC_WS)
     out = torch.empty_like(comp) if out is None else out
     _slic_image_ints(out, "out", comp)
     _slic_apart(out, comp, "out", "comp")
@@ -1922,11 +1921,7 @@ def felz_edges(H, W):
 
 def _felz_image(image, name="image"):
     """image (B, H, W, C) float64, contiguous, on a HIP device, inside THE LIMITS -> (B, H, W, C)"""
-    if not isinstance(image, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor, got {type(image).__name__}")
-    if image.dim() != 4 or image.numel() == 0:
-        raise ValueError(f"{name} must be (B, H, W, C) with at least one element, got {tuple(image.shape)}")
-    B, H, W, C = (int(v) for v in image.shape)
+    B, H, W, C = _bhwc(image, F64, name)
     cap = felz_limits()
     if H * W > cap[0] or C > cap[1] or B > 65535:
         raise ValueError(f"(B, H * W, C) = ({B}, {H * W}, {C}) is over THE LIMITS (65535, {cap[0]}, {cap[1]}) (include/xai_hip_felz.h)")
@@ -1934,24 +1929,9 @@ def _felz_image(image, name="image"):
     return B, H, W, C
 
 
-def _felz_status(status, like):
-    if status is None:
-        status = torch.empty(1, dtype=I32, device=like.device)
-        _call("xai_felz_clear_i32", like.device, _ptr(status), 1, lib="felz")
-        return status
-    _need(status, I32, "status")
-    if status.numel() != 1 or status.device != like.device:
-        raise ValueError("status must hold one int32 on the device of its images")
-    return status
-
-
 def felz_clear(status):
     """status (n,) int32 = 0, by a kernel"""
-    _need(status, I32, "status")
-    if status.numel() < 1:
-        raise ValueError("status must hold at least one int32")
-    _call("xai_felz_clear_i32", status.device, _ptr(status), status.numel(), lib="felz")
-    return status
+    return _status("felz", _typed(status, I32, "status"))
 
 
 def felz_smooth(image, weights, axis):
@@ -1976,7 +1956,7 @@ def felz_costs(image, status=None):
     has no edge: its arrays hold one column that nothing reads or writes, so that they have an address."""
     B, H, W, C = _felz_image(image)
     E = felz_edges(H, W)
-    status = _felz_status(status, image)
+    status = _status("felz", status, 1, image.device, "one")
     keys = torch.empty((B, max(E, 1)), dtype=I64, device=image.device)
     index = torch.empty((B, max(E, 1)), dtype=I32, device=image.device)
     _call("xai_felz_costs_u64", image.device, _ptr(image), B, H, W, C, _ptr(keys), _ptr(index), _ptr(status), lib="felz")
@@ -1985,8 +1965,10 @@ def felz_costs(image, status=None):
 
 def felz_workspace(dev, B, H, W, S):
     """The scratch of K71-K73: uint8, xai_felz_workspace_bytes(B, H, W, S) bytes"""
-    ws, _ = _workspace("xai_felz_workspace_bytes", dev, B, H, W, S, lib="felz", required=True)
-    return ws
+    return _workspace("xai_felz_workspace_bytes", dev, B, H, W, S, lib="felz", required=True)[0]
+
+
+_FELZ_WS = "ws must be felz_workspace(device, B, H, W, S) on the device of the keys"
 
 
 def _felz_pairs(keys, index, H, W):
@@ -1998,19 +1980,10 @@ def _felz_pairs(keys, index, H, W):
     return int(keys.shape[0])
 
 
-def _felz_ws(ws, dev, B, H, W, S):
-    if ws is None:
-        return felz_workspace(dev, B, H, W, S)
-    _need(ws, U8, "ws")
-    if ws.device != dev or ws.numel() < _lib.load("felz").xai_felz_workspace_bytes(B, H, W, S):
-        raise ValueError("ws must be felz_workspace(device, B, H, W, S) on the device of the keys")
-    return ws
-
-
 def felz_sort(keys, index, H, W, S=1, ws=None):
     """K71 / K72: (keys, index) of every image sorted in place by key, equal keys by index (stable) -> (keys, index)"""
     B = _felz_pairs(keys, index, H, W)
-    ws = _felz_ws(ws, keys.device, B, H, W, S)
+    ws, _ = _workspace("xai_felz_workspace_bytes", keys.device, B, H, W, S, lib="felz", required=True, ws=ws, wrong=_FELZ_WS)
     _call("xai_felz_sort_u64", keys.device, _ptr(keys), _ptr(index), B, H, W, S, _ptr(ws), ws.numel(), lib="felz")
     return keys, index
 
@@ -2023,9 +1996,9 @@ def felz_merge(keys, order, scales, H, W, min_size, status=None, ws=None):
     S = int(scales.numel())
     if scales.dim() != 1 or S < 1 or S > felz_limits()[2] or scales.device != keys.device:
         raise ValueError(f"scales must be (S,), 1 <= S <= {felz_limits()[2]}, on the device of the keys")
-    min_size = _slic_int(min_size, "min_size", 0)
-    ws = _felz_ws(ws, keys.device, B, H, W, S)
-    status = _felz_status(status, keys)
+    min_size = _int(min_size, "min_size", 0)
+    ws, _ = _workspace("xai_felz_workspace_bytes", keys.device, B, H, W, S, lib="felz", required=True, ws=ws, wrong=_FELZ_WS)
+    status = _status("felz", status, 1, keys.device, "one")
     roots = torch.empty((B, S, H, W), dtype=I32, device=keys.device)
     stats = torch.empty((B, S, 2), dtype=I32, device=keys.device)
     _call("xai_felz_merge_f64", keys.device, _ptr(keys), _ptr(order), _ptr(scales), B, S, H, W, min_size, _ptr(roots),
@@ -2043,7 +2016,7 @@ def felz_labels(roots, status=None):
     M = roots.numel() // n
     if n > felz_limits()[0]:
         raise ValueError(f"H * W = {n} is over THE LIMITS ({felz_limits()[0]}) (include/xai_hip_felz.h)")
-    status = _felz_status(status, roots)
+    status = _status("felz", status, 1, roots.device, "one")
     labels = torch.empty_like(roots)
     counts = torch.empty(tuple(roots.shape[:-2]), dtype=I32, device=roots.device)
     _call("xai_felz_labels_i32", roots.device, _ptr(roots), M, n, _ptr(labels), _ptr(counts), _ptr(status), lib="felz")
@@ -2058,10 +2031,6 @@ def clip_limits():
     """(XAI_CLIP_MAX_TOKENS, XAI_CLIP_MAX_WIDTH, XAI_CLIP_MAX_TEXTS) of the built library"""
     lib = _lib.load("clip")
     return lib.xai_clip_max_tokens(), lib.xai_clip_max_width(), lib.xai_clip_max_texts()
-
-
-def _clip_suffix(t):
-    return "f16" if t.dtype == F16 else "f32"
 
 
 def _clip_tokens(t, name, like=None):
@@ -2098,7 +2067,7 @@ def clip_cls_attention(q0, k, v, want_scores=False):
     attn = torch.empty((B, L), dtype=k.dtype, device=k.device)
     att_out = torch.empty((B, D), dtype=k.dtype, device=k.device)
     scores = torch.empty((B, L), dtype=k.dtype, device=k.device) if want_scores else None
-    _call(f"xai_clip_cls_attention_{_clip_suffix(k)}", k.device, _ptr(q0), _ptr(k), kl, kb, _ptr(v), vl, vb, B, L, D,
+    _call(f"xai_clip_cls_attention_{_suffix(k)}", k.device, _ptr(q0), _ptr(k), kl, kb, _ptr(v), vl, vb, B, L, D,
           float(D) ** -0.5, _ptr(scores), _ptr(attn), _ptr(att_out), lib="clip")
     return (attn, att_out, scores) if want_scores else (attn, att_out)
 
@@ -2126,7 +2095,7 @@ def clip_eclip_map(q_out0, k_out, v, grad_cls=None, texts=None, withksim=True, w
         raise TypeError("clip_eclip_map: without withgrad there is no grad_cls to count the texts; pass texts=T")
     T = _clip_texts(int(texts))
     out = torch.empty((B, L - 1), dtype=F32, device=v.device)
-    _call(f"xai_clip_eclip_map_{_clip_suffix(v)}", v.device, _ptr(q_out0) if withksim else None, _ptr(k_out) if withksim else None, kl, kb,
+    _call(f"xai_clip_eclip_map_{_suffix(v)}", v.device, _ptr(q_out0) if withksim else None, _ptr(k_out) if withksim else None, kl, kb,
           _ptr(v), vl, vb, _ptr(grad_cls) if withgrad else None, B, L, D, T, int(bool(withksim)), int(bool(withgrad)), _ptr(out),
           lib="clip")
     return out
@@ -2147,6 +2116,6 @@ def clip_maskclip_map(v_final, txt, k_out):
         raise ValueError(f"txt must be (T, {E}) or ({B}, T, {E}) on {k_out.device}, got {tuple(txt.shape)} on {txt.device}")
     T = _clip_texts(txt.shape[-2])
     out = torch.empty((B, L - 1), dtype=F32, device=k_out.device)
-    _call(f"xai_clip_maskclip_map_{_clip_suffix(k_out)}", k_out.device, _ptr(v_final), _ptr(txt), T * E if txt.dim() == 3 else 0,
+    _call(f"xai_clip_maskclip_map_{_suffix(k_out)}", k_out.device, _ptr(v_final), _ptr(txt), T * E if txt.dim() == 3 else 0,
           _ptr(k_out), kl, kb, B, L, D, E, T, _ptr(out), lib="clip")
     return out

@@ -280,6 +280,21 @@ def test_three_images_of_which_one_is_done_and_the_cap():
                 _launch(a, *args)
 
 
+def test_candidates_are_ranked_across_the_waves_when_the_lanes_hold_a_ragged_share():
+    """S = 601 over the select kernel's 256 lanes: three entries of `order` a lane, the last lane with one, 55 lanes with none.  Of the
+    first 500 entries all but every 97th are taken, and the minimum of `resp` takes the one at 393: the eight free ones that become
+    the next candidates lie in lanes 1, 34, 66, 98, 163, 166 and 167 (two), so the counts of three waves enter the ranks."""
+    S = 601
+    order = np.random.RandomState(S).permutation(S)                  # the order _select_case gives this S
+    pre = [int(order[j]) for j in range(500) if j % 97 != 5]
+    a, args = _select_case([0.5, 0.1, 0.2, 0.3, 0.0, 0.1, 0.2, 0.3], mode=0, S=S, L=8, plan=[(0, 8, -1), (1, 8, -1)], preloaded=pre)
+    assert a["order"][0].tolist() == order.tolist() and a["cand"][0].tolist() == [int(order[j]) for j in (5, 102, 199, 296, 393, 490, 500, 501)]
+    d = _launch(a, *args)
+    select_restated(a, *args)
+    _same(d, a)
+    assert a["cand"][0].tolist() == [int(order[j]) for j in (5, 102, 199, 296, 490, 500, 501, 502)]
+
+
 # ------------------------------------------------------------------------------------------------ both searches
 def _k_resize(x, size):
     from xai_engine import kernels as K

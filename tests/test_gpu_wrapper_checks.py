@@ -216,3 +216,119 @@ def test_rise_accum_acc(K):
     carried = torch.ones((4, 4), dtype=F64, device=DEV)
     once = K.rise_accum(grid, shift, scores, cell, 4, 4, 0.25)
     assert torch.equal(K.rise_accum(grid, shift, scores, cell, 4, 4, 0.25, acc=carried), once + 1.0)
+
+
+# ------------------------------------------------------------------------------ the checks the segmenters and clusterers share
+def slic_operands():
+    return torch.zeros(2, 4, 4, 3, device=DEV), torch.zeros(2, 2, 5, device=DEV), torch.zeros(2, 4, 4, dtype=I32, device=DEV)
+
+
+def felz_operands():
+    E = 4 * 3 + 3 * 4 + 2 * 3 * 3                              # the edges of a 4 x 4 image
+    return (torch.zeros(2, E, dtype=torch.int64, device=DEV), torch.arange(E, dtype=I32, device=DEV).repeat(2, 1).contiguous(),
+            torch.ones(1, dtype=F64, device=DEV))
+
+
+def kmeans_operands():
+    return (torch.zeros(8, 4, device=DEV), torch.zeros(2, 4, device=DEV), torch.zeros(8, dtype=I32, device=DEV),
+            torch.zeros(2, dtype=I32, device=DEV), torch.zeros(6, dtype=I32, device=DEV))
+
+
+def test_int_refuses_a_bool_in_three_families(K):
+    f, cen, _ = slic_operands()
+    with pytest.raises(TypeError, match="^step: expected an int, got bool$"):
+        K.slic_assign(f, cen, True)
+    keys, index, scales = felz_operands()
+    with pytest.raises(TypeError, match="^min_size: expected an int, got bool$"):
+        K.felz_merge(keys, index, scales, 4, 4, True)
+    x, C, assign, counts, state = kmeans_operands()
+    with pytest.raises(TypeError, match="^max_iter: expected an int, got bool$"):
+        K.kmeans_update(x, C, assign, counts, K.kmeans_workspace(x, 2), state, True, 1e-4)
+    with pytest.raises(TypeError, match="^n_clusters: expected an int, got bool$"):
+        K.kmeans_workspace(x, True)
+    with pytest.raises(ValueError, match="^step must be >= 1, got 0$"):
+        K.slic_assign(f, cen, 0)
+    with pytest.raises(ValueError, match="^max_iter must be >= 1, got 0$"):
+        K.kmeans_update(x, C, assign, counts, K.kmeans_workspace(x, 2), state, 0, 1e-4)
+
+
+def test_image_check_refuses_float16_and_a_missing_axis_in_three_families(K):
+    f, cen, _ = slic_operands()
+    with pytest.raises(TypeError, match="^features: expected torch.float32 or torch.float64, got torch.float16$"):
+        K.slic_assign(f.half(), cen, 2)
+    with pytest.raises(TypeError, match="^image: expected torch.float64, got torch.float16$"):
+        K.felz_costs(f.half())
+    with pytest.raises(TypeError, match="^features: expected torch.float64, got torch.float16$"):
+        K.quickshift_density(f.half(), torch.zeros(2, 4, 4, dtype=F64, device=DEV), 1.0)
+    with pytest.raises(ValueError, match=r"^features must be \(B, H, W, C\) with at least one element, got \(4, 4, 3\)$"):
+        K.slic_assign(f[0], cen, 2)
+    with pytest.raises(ValueError, match=r"^image must be \(B, H, W, C\) with at least one element, got \(4, 4, 3\)$"):
+        K.felz_costs(f[0].double())
+    with pytest.raises(ValueError, match=r"^features must be \(B, H, W, C\) with at least one element, got \(4, 4, 3\)$"):
+        K.quickshift_density(f[0].double(), torch.zeros(2, 4, 4, dtype=F64, device=DEV), 1.0)
+    with pytest.raises(TypeError, match="^points: expected torch.float32, got torch.float16$"):
+        K.kmeans_workspace(torch.zeros(8, 4, dtype=torch.float16, device=DEV), 2)
+    with pytest.raises(TypeError, match="^distance: expected torch.float32, got torch.float16$"):
+        K.linkage_workspace(torch.zeros(4, 4, dtype=torch.float16, device=DEV))
+
+
+def test_workspace_refuses_a_short_one_in_three_families(K):
+    _, _, labels = slic_operands()
+    need = K.slic_workspace(labels).numel()
+    for call in (lambda ws: K.slic_components(labels, 1, 17, ws=ws), lambda ws: K.slic_number(labels, 0, ws=ws)):
+        with pytest.raises(ValueError, match=r"^ws must be slic_workspace\(labels\) on the device of labels$"):
+            call(torch.zeros(need - 1, dtype=U8, device=DEV))
+        with pytest.raises(TypeError, match="^ws: expected torch.uint8"):
+            call(torch.zeros(need, dtype=I32, device=DEV))
+    keys, index, scales = felz_operands()
+    need = K.felz_workspace(DEV, 2, 4, 4, 1).numel()
+    for call in (lambda ws: K.felz_sort(keys, index, 4, 4, ws=ws), lambda ws: K.felz_merge(keys, index, scales, 4, 4, 1, ws=ws)):
+        with pytest.raises(ValueError, match=r"^ws must be felz_workspace\(device, B, H, W, S\) on the device of the keys$"):
+            call(torch.zeros(need - 1, dtype=U8, device=DEV))
+    assert K.felz_sort(keys, index, 4, 4, ws=torch.zeros(need, dtype=U8, device=DEV))[0] is keys
+    x, C, _, _, state = kmeans_operands()
+    need = K.kmeans_workspace(x, 2).numel()
+    first = torch.tensor([0, 1], device=DEV)
+    with pytest.raises(ValueError, match=r"^ws must be kmeans_workspace\(points, k\) on the device of points$"):
+        K.kmeans_init(x, first, C, torch.zeros(need - 1, dtype=U8, device=DEV), state)
+    with pytest.raises(TypeError, match="^ws: expected a torch.Tensor, got NoneType$"):
+        K.kmeans_init(x, first, C, None, state)
+
+
+def test_status_refuses_a_wrong_length_in_two_families_and_is_cleared_when_new(K):
+    f, cen, labels = slic_operands()
+    for bad in (1, 3):
+        with pytest.raises(ValueError, match="^status must hold 2 int32 on the device of its images$"):
+            K.slic_assign(f, cen, 2, status=torch.zeros(bad, dtype=I32, device=DEV))
+        with pytest.raises(ValueError, match="^status must hold 2 int32 on the device of its images$"):
+            K.slic_components(labels, 1, 17, status=torch.zeros(bad, dtype=I32, device=DEV))
+    keys, index, scales = felz_operands()
+    for call in (lambda st: K.felz_costs(f.double(), status=st), lambda st: K.felz_merge(keys, index, scales, 4, 4, 1, status=st),
+                 lambda st: K.felz_labels(labels, status=st)):
+        with pytest.raises(ValueError, match="^status must hold one int32 on the device of its images$"):
+            call(torch.zeros(2, dtype=I32, device=DEV))
+        with pytest.raises(TypeError, match="^status: expected torch.int32"):
+            call(torch.zeros(1, dtype=torch.int64, device=DEV))
+    assert K.felz_costs(f.double())[2].tolist() == [0]                 # a new word is cleared by the library's own entry
+    for clear in (K.slic_clear, K.felz_clear):
+        given = torch.full((3,), 7, dtype=I32, device=DEV)
+        assert clear(given) is given and given.tolist() == [0, 0, 0]
+        with pytest.raises(ValueError, match="^status must hold at least one int32$"):
+            clear(torch.zeros(0, dtype=I32, device=DEV))
+        with pytest.raises(TypeError, match="^status: expected a torch.Tensor, got NoneType$"):
+            clear(None)
+
+
+def test_a_cpu_tensor_is_refused_alike_in_every_family(K):
+    from xai_engine import XaiHipError
+    f, cen, labels = slic_operands()
+    keys, index, scales = felz_operands()
+    x = kmeans_operands()[0]
+    for call in (lambda: K.slic_assign(f.cpu(), cen, 2), lambda: K.slic_number(labels.cpu()), lambda: K.felz_costs(f.double().cpu()),
+                 lambda: K.felz_labels(labels.cpu()), lambda: K.quickshift_density(f.double().cpu(), torch.zeros(2, 4, 4, dtype=F64), 1.0),
+                 lambda: K.quickshift_labels(labels.cpu()), lambda: K.kmeans_workspace(x.cpu(), 2),
+                 lambda: K.linkage_workspace(torch.zeros(4, 4)), lambda: K.slic_clear(torch.zeros(2, dtype=I32)),
+                 lambda: K.slic_number(labels, 0, ws=torch.zeros(4096, dtype=U8)),
+                 lambda: K.felz_sort(keys, index, 4, 4, ws=torch.zeros(4096, dtype=U8))):
+        with pytest.raises(XaiHipError, match="lives on 'cpu'.*no CPU fallback"):
+            call()

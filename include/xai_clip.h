@@ -39,6 +39,10 @@
  * sums differ by at most (4 + 2n)u relatively.  p_j = rT(e_j / sum): (4 + 4 + 2n + 2)u = (10 + 2n)u relatively before rT, and rT may
  * move two such neighbours to adjacent values of T, one ulp of T apart.  att_output[d] = rT(sum_j p_j v_jd), in ascending j from +0:
  * the two sums differ by at most sum_j |dp_j| |v_jd| + 2 L u sum_j |p_j v_jd|, and again one ulp of T after rT.
+ * The relative 1 ulp of expf holds in the normal range only: below 2^-126 one ulp is 2^-149 absolute.  So for float dp_j gains
+ * 3 * 2^-149: the sum is at least 1 because the maximum contributes e = 1, so the quotient does not enlarge the two exps' 2 * 2^-149,
+ * and the quotient's own rounding adds one more.  (The device's expf keeps subnormal results, it does not return 0 for them:
+ * tests/test_gpu_clip_edges.py runs e_j down through the subnormal range to 0 and holds this term.)
  */
 #ifndef XAI_CLIP_H
 #define XAI_CLIP_H

@@ -205,15 +205,17 @@ def normalize_rows(rows, dt):
 def k75_scores(q0, k, dt):
     """q0 (B, D), k (L, B, D) as fp32 values of dtype dt -> (round(q * scaling) (B, D), scores (B, L)): all that precedes the exp"""
     D = q0.shape[1]
-    qs = rT(q0 * f32(float(D) ** -0.5), dt)
-    return qs, rT(wave_sum_rows(qs[None] * k), dt).T
+    with np.errstate(all="ignore"):
+        qs = rT(q0 * f32(float(D) ** -0.5), dt)
+        return qs, rT(wave_sum_rows(qs[None] * k), dt).T
 
 
 def k75(q0, k, v, dt):
     """-> (qs, scores, attn (B, L), att_out (B, D)) in the header's orders, NumPy's exp standing in for the device's"""
     L, B, D = k.shape
     qs, s = k75_scores(q0, k, dt)
-    e = np.exp(s - s.max(axis=1, keepdims=True)).astype(f32)
+    with np.errstate(all="ignore"):                                          # a NaN or an infinite score is a case, not a warning
+        e = np.exp(s - s.max(axis=1, keepdims=True)).astype(f32)             # NumPy's max returns a NaN that is there, as torch's
     pad = (-L) % 1024
     ep = np.concatenate([e, np.zeros((B, pad), dtype=f32)], axis=1).reshape(B, -1, 1024)
     lanes = np.zeros((B, 1024), dtype=f32)
@@ -223,11 +225,12 @@ def k75(q0, k, v, dt):
     total = np.zeros(B, dtype=f32)
     for w in range(16):
         total = total + waves[:, w]
-    p = rT(e / total[:, None], dt)
-    acc = np.zeros((B, D), dtype=f32)
-    for j in range(L):
-        acc = acc + p[:, j, None] * v[j]
-    return qs, s, p, rT(acc, dt)
+    with np.errstate(all="ignore"):
+        p = rT(e / total[:, None], dt)
+        acc = np.zeros((B, D), dtype=f32)
+        for j in range(L):
+            acc = acc + p[:, j, None] * v[j]
+        return qs, s, p, rT(acc, dt)
 
 
 def k76(q_out0, k_out, v, grad_cls, T, withksim, withgrad, dt):
@@ -268,3 +271,92 @@ def k77(v_final, txt, k_out, dt):
             a = rT(wave_sum_rows(fn * txt[:, t, None, :]), dt)
             acc = acc + rT(a * c, dt)
         return rT(acc, dt)
+
+
+# ------------------------------------------------------------------------------------------------ comparisons the GPU tests share
+U = 2.0 ** -24
+
+
+def spacing(x, dt):
+    """distance between neighbouring values of dtype dt at |x| (its least subnormal spacing below the normal range)"""
+    x = np.abs(np.asarray(x, dtype=np.float64))
+    bits, emin = (10, -14) if dt == np.float16 else (23, -126)
+    e = np.floor(np.log2(np.maximum(x, 2.0 ** emin)))
+    return 2.0 ** (e - bits)
+
+
+def same(got, want):
+    """bit for bit, a NaN by position"""
+    got, want = np.asarray(got), np.asarray(want)
+    gn, wn = np.isnan(got), np.isnan(want)
+    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(gn, wn) and got[~gn].tobytes() == want[~wn].tobytes()
+
+
+def k75_bound(p, p_ref, o, o_ref, v, dt, subnormal=0.0):
+    """The header's bound behind K75's first exp for attn p (B, L) and att_out o (B, D), all fp64, v (L, B, D) -> (dp, do):
+         dp_j = (10 + 2n) u |p_ref_j| + spacing_T(max(|p_j|, |p_ref_j|)),  n = ceil(L / 1024) + 22  (no spacing term for fp32, where
+                `subnormal` is added instead: the absolute error of two expf results below 2^-126 and of the quotient's rounding)
+         do_d = sum_j dp_j |v_jd| + 2 L u sum_j |p_ref_j v_jd| + spacing_T(max(|o_d|, |o_ref_d|))"""
+    L = v.shape[0]
+    n = -(-L // 1024) + 22
+    half = dt == np.float16
+    with np.errstate(all="ignore"):
+        dp = (10 + 2 * n) * U * np.abs(p_ref) + (spacing(np.maximum(np.abs(p), np.abs(p_ref)), dt) if half else subnormal)
+        absv = np.abs(v.astype(np.float64))
+        do = np.einsum("bj,jbd->bd", dp, absv) + 2 * L * U * np.einsum("bj,jbd->bd", np.abs(p_ref.astype(np.float64)), absv) \
+            + (spacing(np.maximum(np.abs(o), np.abs(o_ref)), dt) if half else 0.0)
+    return dp, do
+
+
+def merge_ledger(path, entries, **meta):
+    """Write {name, measured, bound} records into the JSON ledger at `path`, replacing those of the same name and keeping the rest
+    (two test files share one ledger, and a run of a few tests leaves the others' records alone)"""
+    import json
+    import os
+    old = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            old = json.load(f)
+    rows = {r["name"]: r for r in old.get("comparisons", [])}
+    rows.update({r["name"]: r for r in entries})
+    old.update(meta)
+    old["comparisons"] = [rows[k] for k in sorted(rows)]
+    with open(path, "w") as f:
+        json.dump(old, f, indent=1)
+        f.write("\n")
+
+
+# ------------------------------------------------------------------------------------------------ the edges of K75-K77
+# (L, D, B), each the smallest shape that reaches its edge of csrc/clip/clip_kernels.hip
+EDGES = {
+    "the lane loop of row_sum": [(2, 1, 1), (2, 63, 2), (3, 64, 1), (3, 65, 2), (18, 70, 1)],
+    "wave rounds over rows (16 waves)": [(16, 64, 1), (17, 64, 2), (18, 64, 1), (33, 5, 1)],
+    "workgroup strides over L (BLOCKSUM depth n = 23, 24, 25)": [(1023, 8, 1), (1024, 8, 1), (1025, 8, 2), (1026, 8, 1), (2049, 4, 1)],
+    "workgroup strides over D": [(5, 1023, 1), (5, 1024, 1), (3, 1025, 2), (3, 2049, 1)],
+    "the shipped models (ViT-B/16, ViT-B/32, ViT-L/14)": [(197, 768, 2), (50, 768, 1), (257, 1024, 1)],
+    "many workgroups": [(3, 7, 70)],
+}
+EDGE_SHAPES = [s for shapes in EDGES.values() for s in shapes]
+
+
+def edge_operands(L, D, B, dt, E=None, T=3, names=("q0", "k", "v", "q_out0", "k_out", "grad", "v_final", "txt")):
+    """The operands `names` of K75-K77 at (L, D, B), E = D // 2 + 1 unless given: seeded randn cast to dt, as fp32 values of dt"""
+    E = D // 2 + 1 if E is None else E
+    shapes = dict(q0=(B, D), k=(L, B, D), v=(L, B, D), q_out0=(B, D), k_out=(L, B, D), grad=(B, T, D), v_final=(B, L - 1, E), txt=(B, T, E))
+    tdt = torch.float16 if dt == np.float16 else torch.float32
+    return {n: torch.randn(shapes[n], generator=torch.Generator().manual_seed(100 + i)).to(tdt).float().numpy()
+            for i, n in enumerate(shapes) if n in names}
+
+
+def tiny_rows(rows, dt):
+    """`rows` scaled so that their norm is below the clamp 1e-12 (float; the sum of squares stays a normal number) or inside the
+    subnormal range of half (where the clamp rT(1e-12) is 0 and the norm itself is the denominator)"""
+    if dt == np.float16:
+        out = rT(rows * f32(2.0 ** -20), dt)
+        norm = np.sqrt((out.astype(np.float64) ** 2).sum(-1))
+        assert (norm > 0).all() and (norm < 2.0 ** -14).all()
+        return out
+    out = rows * f32(1e-15)
+    sumsq = (out.astype(np.float64) ** 2).sum(-1)
+    assert (np.sqrt(sumsq) < 1e-12).all() and (sumsq > 2.0 ** -100).all()
+    return out

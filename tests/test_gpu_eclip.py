@@ -14,7 +14,6 @@ Bounds.
   the margin of 4 because the device's GEMMs round differently from the CPU's.  Every measured error is written to
   profiles/r21_eclip_parity.json."""
 import json
-import math
 import os
 
 import numpy as np
@@ -22,12 +21,12 @@ import pytest
 import torch
 
 import clip_restated as R
+from clip_restated import same, spacing
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-U = 2.0 ** -24
 FIXTURES = {m: [str(j) for j in range(3)] + (["wide"] if m == "mini" else []) for m in R.MODELS}
 _LEDGER = []
 
@@ -89,21 +88,6 @@ def fixture_txt(G, model, tag, T):
     return R.fixture_texts(int(G[f"{model}/{tag}/t_seed"]), 2, R.MODELS[model][4])[:T]
 
 
-def spacing(x, dt):
-    """distance between neighbouring values of dtype dt at |x| (its least subnormal spacing below the normal range)"""
-    x = np.abs(np.asarray(x, dtype=np.float64))
-    bits, emin = (10, -14) if dt == np.float16 else (23, -126)
-    e = np.floor(np.log2(np.maximum(x, 2.0 ** emin)))
-    return 2.0 ** (e - bits)
-
-
-def same(got, want):
-    """bit for bit, a NaN by position"""
-    got, want = np.asarray(got), np.asarray(want)
-    gn, wn = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(gn, wn) and got[~gn].tobytes() == want[~wn].tobytes()
-
-
 def bound_vs_hi(hi, gap, out_dt):
     return max(float(spacing(np.abs(hi).max(), out_dt)), 4.0 * gap * float(np.abs(hi).max()))
 
@@ -162,13 +146,9 @@ def test_k75_scores_are_exact_and_the_softmax_row_is_within_the_derived_bound(G,
     _qs, s_ref, p_ref, o_ref = R.k75(h["q0"], h["k"], h["v"], dt)
     assert same(scores.float().cpu().numpy(), s_ref)
     p, o = attn.double().cpu().numpy(), att_out.double().cpu().numpy()
-    n = math.ceil(L / 1024) + 22
     half = dt == np.float16
-    dp = (10 + 2 * n) * U * np.abs(p_ref) + (spacing(np.maximum(np.abs(p), np.abs(p_ref)), dt) if half else 0.0)
+    dp, do = R.k75_bound(p, p_ref, o, o_ref, h["v"], dt)
     assert (np.abs(p - p_ref) <= dp).all(), float((np.abs(p - p_ref) / dp).max())
-    absv = np.abs(h["v"].astype(np.float64))                                       # (L, B, D)
-    do = np.einsum("bj,jbd->bd", dp, absv) + 2 * L * U * np.einsum("bj,jbd->bd", np.abs(p_ref.astype(np.float64)), absv) \
-        + (spacing(np.maximum(np.abs(o), np.abs(o_ref)), dt) if half else 0.0)
     assert (np.abs(o - o_ref) <= do).all(), float((np.abs(o - o_ref) / do).max())
     assert abs(p.sum(axis=1) - 1).max() < (1e-2 if half else 1e-5)
     one = K.clip_cls_attention(d["q0"][1:2], d["k"][:, 1:2], d["v"][:, 1:2])        # an image alone: its own bytes

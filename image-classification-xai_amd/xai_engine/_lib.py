@@ -137,15 +137,24 @@ LIBRARIES = {key: Library(key) for key in ("hip", "ext", "ext2", "ext3", "ext4",
 # operands): a table of their own, with headers include/xai_<key>.h and sources csrc/<key>/*.hip.  LIBRARIES above is the table of the
 # fp32 / fp64 / integer entries (include/xai_hip*.h, csrc/*.hip), which the tests of the features before hold whole, key by key.
 DTYPE_LIBRARIES = {"clip": Library("clip", header="xai_clip.h")}
+# The libraries whose kernels stand in for a launch INSIDE the classifier (xai_engine/prepare.py proves each site bit for bit before
+# it relies on one): a third table of the same records, headers include/xai_<key>.h and sources csrc/<key>/*.hip like the second.
+# A key cannot join either table above without an edit to an earlier feature's test: tests/test_cpu_quickshift.py, test_cpu_kmeans.py,
+# test_cpu_linkage.py and test_cpu_lrp.py each end a test with `{k: (version, minor) for k in LIBRARIES} == PINNED`, the eleven pairs of
+# tests/abi_libs.py, and tests/test_cpu_eclip.py asserts `list(DTYPE_LIBRARIES) == ["clip"]`.
+CLASSIFIER_LIBRARIES = {"conv": Library("conv", header="xai_conv.h")}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key] or DTYPE_LIBRARIES[key] (cached by the record); raises, never falls back, when the file
-    is absent or refused."""
-    return (LIBRARIES[key] if key in LIBRARIES else DTYPE_LIBRARIES[key]).load()
+    """The loaded handle of LIBRARIES[key], DTYPE_LIBRARIES[key] or CLASSIFIER_LIBRARIES[key] (cached by the record); raises, never
+    falls back, when the file is absent or refused."""
+    for table in (LIBRARIES, CLASSIFIER_LIBRARIES):
+        if key in table:
+            return table[key].load()
+    return DTYPE_LIBRARIES[key].load()
 
 
 def check(code, what):

@@ -696,6 +696,33 @@ def bn_relu_bwd_bcast(grad_out, fc_weight, targets, shape, mask, weight, var, ep
     return gx, gid
 
 
+# ---- the 1x1 convolution backward-data GEMM with its order of summation as an argument (K78-K79, include/xai_conv.h)
+# a walk = (splits, membership, grouping, order, from_zero) in the words of csrc/xai_conv_walk.h
+WALK_CONTIGUOUS, WALK_ROUND_ROBIN = 0, 1
+WALK_K_CONSECUTIVE, WALK_K_STRIDE4 = 0, 1
+WALK_ASCENDING, WALK_DESCENDING = 0, 1
+
+
+def conv1x1_bwd_data(gy, weight, walk, tile_rows=0, simple=False, out=None):
+    """gx (N,C,H,W) = the input gradient of a kernel-1, stride-1, pad-0 convolution with `weight` (K,C,1,1) or (K,C) for the output
+    gradient gy (N,K,H,W), summed over k as `walk` says (K78).  simple: by the one-wave-per-tile kernel K79, which takes no
+    tile_rows."""
+    _need(gy, F32, "gy"); _need(weight, F32, "weight")
+    if gy.dim() != 4 or weight.dim() not in (2, 4) or weight.numel() != weight.shape[0] * weight.shape[1] or weight.shape[0] != gy.shape[1]:
+        raise ValueError("gy must be (N, K, H, W) and weight (K, C) or (K, C, 1, 1)")
+    splits, membership, grouping, order, from_zero = (int(v) for v in walk)
+    N, K, H, W = gy.shape
+    Cc = int(weight.shape[1])
+    gx = _out(out, "out", (N, Cc, H, W), gy)
+    if simple:
+        _call("xai_conv1x1_bwd_data_simple_f32", gy.device, _ptr(gy), _ptr(weight), N, K, Cc, H * W, splits, membership, grouping, order,
+              from_zero, _ptr(gx), lib="conv")
+    else:
+        _call("xai_conv1x1_bwd_data_f32", gy.device, _ptr(gy), _ptr(weight), N, K, Cc, H * W, splits, membership, grouping, order,
+              from_zero, int(tile_rows), _ptr(gx), lib="conv")
+    return gx.view(N, Cc, H, W)
+
+
 def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, stride, pad):
     """-> (y, code): max_pool2d(relu(bn(x)), kernel, stride, pad) and one uint8 per pooled output for bn_relu_maxpool_bwd (the
     window-local arg-max, or 255 for a closed ReLU gate); x (N,C,H,W) -> (N,C,PH,PW) twice."""

@@ -321,7 +321,10 @@ def site_report():
     c = SITE_COUNTS
     text = (f"{c['shortcut_compact']} strided 1x1 shortcut site(s) on compact channel-major tensors, {c['shortcut_refused']} refused; "
             f"{c['head_broadcast']} pool+Linear head backward(s) as a broadcast operand, {c['head_refused']} refused")
-    return text + ("" if not c["reasons"] else " (" + "; ".join(c["reasons"]) + ")")
+    text += "" if not c["reasons"] else " (" + "; ".join(c["reasons"]) + ")"
+    k = CONV_SITE_COUNTS
+    text += (f"; {k['conv_bwd_kernel']} 1x1 convolution backward-data site(s) on the folded-batch GEMM kernel, {k['conv_bwd_refused']} refused")
+    return text + ("" if not k["reasons"] else " (" + "; ".join(k["reasons"]) + ")")
 
 
 def _refuse(kind, why):
@@ -341,20 +344,28 @@ def _solver_key():
     return bool(torch.backends.cudnn.deterministic), bool(torch.backends.cudnn.benchmark)
 
 
-def _proven(key, prove, kind, why):
-    """The decision for `key`, made once per process under the lock by `prove()` (-> a candidate or None) on the first eager call;
-    inside a stream capture nothing is decided and None is returned, so the caller takes the PyTorch / MIOpen form there."""
+def _proven(key, prove, kind, why, store=None):
+    """The decision for `key`, made once under the lock by `prove()` (-> a candidate or None) on the first eager call; inside a
+    stream capture nothing is decided and None is returned, so the caller takes the PyTorch / MIOpen form there.  `store`: where
+    the decisions of this kind of site live (default: _PROVEN, process-wide).  kind "shortcut" | "head" counts in SITE_COUNTS and
+    warns on a refusal; kind "conv" counts in CONV_SITE_COUNTS and records the reason there."""
     import torch
     with _PROOF_LOCK:
-        if key not in _PROVEN:
+        if store is None:
+            store = _PROVEN
+        if key not in store:
             if torch.cuda.is_current_stream_capturing():
                 return None
-            _PROVEN[key] = prove()
-            if _PROVEN[key] is None:
+            store[key] = prove()
+            if kind == "conv":
+                CONV_SITE_COUNTS["conv_bwd_refused" if store[key] is None else "conv_bwd_kernel"] += 1
+                if store[key] is None:
+                    CONV_SITE_COUNTS["reasons"].append(why)
+            elif store[key] is None:
                 _refuse(kind + "_refused", why)
             else:
                 SITE_COUNTS["shortcut_compact" if kind == "shortcut" else "head_broadcast"] += 1
-        return _PROVEN[key]
+        return store[key]
 
 
 def _conv_on_view(xv, conv):
@@ -470,6 +481,93 @@ def _compact_shortcut(conv, side):
     return cand[1](xv, conv)
 
 
+# ------------------------------------------------------------------------------ 1x1 backward-data on small planes: our GEMM kernel
+# MIOpen hands the backward-data of a stride-1 1x1 convolution to rocBLAS as one GEMM per image, HW x C x K.  On layer4's 7x7 planes
+# rocBLAS pads 49 to its macro tile, cuts K into 19 partial sums through its handle's workspace and adds them in a second kernel;
+# K78 (kernels.conv1x1_bwd_data) folds the batch into the columns and keeps the partial sums in registers, in an order of summation
+# that is its argument.  The sites (a site = one module at one running shape under one pair of solver switches) that run on it, the
+# ones whose proof refused, and why: counted apart from SITE_COUNTS, said by `site_report()` in a sentence of their own.
+CONV_SITE_COUNTS = {"conv_bwd_kernel": 0, "conv_bwd_refused": 0, "walks": [], "reasons": []}
+_CONV_MAX_PLANE = 64         # HW up to one 64-column tile: where a GEMM per image pads and folding the batch pays
+# (splits, membership, grouping, order, from_zero) in the words of csrc/xai_conv_walk.h.  rocBLAS picks its kernel, and with it the
+# order of every sum, by shape, so none is assumed: per site the first walk that reproduces MIOpen's backward-data bit for bit is
+# kept.  19 partial sums dealt round robin, k in consecutive fours, added in ascending order: rocBLAS's GSU19 kernel at layer4
+# (profiles/conv3_bwd_walk_probe.txt); one partial sum: a GEMM kernel that does not split K.
+_CONV_WALKS = [(19, 1, 0, 0, 0), (1, 0, 0, 0, 0)]
+_CONV_FN = None
+
+
+def _conv_bwd_function():
+    global _CONV_FN
+    if _CONV_FN is None:
+        import torch
+        import torch.nn.functional as F
+        from . import kernels as K
+
+        class Conv1x1(torch.autograd.Function):
+            """conv(x) for a stride-1 1x1 convolution whose weight takes no gradient: the forward is the module's own MIOpen call,
+            the backward-data is K78 walking `walk`."""
+
+            @staticmethod
+            def forward(ctx, x, conv, walk):
+                ctx.conv, ctx.walk = conv, walk
+                return F.conv2d(x, conv.weight, conv.bias)
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable      # a kernel launch: no graph through it, create_graph raises
+            def backward(ctx, gy):
+                return K.conv1x1_bwd_data(gy.contiguous(), ctx.conv.weight, ctx.walk), None, None
+        _CONV_FN = Conv1x1
+    return _CONV_FN
+
+
+def _prove_conv_bwd(conv, x):
+    """-> the first walk of _CONV_WALKS with which K78 returns MIOpen's backward-data of conv at x's shape bit for bit, or None"""
+    import torch
+    import torch.nn.functional as F
+    from . import kernels as K
+    with torch.enable_grad():
+        xin = x.detach().clone().requires_grad_(True)
+        ref = F.conv2d(xin, conv.weight, conv.bias)
+        gy = torch.randn_like(ref)
+        (want,) = torch.autograd.grad(ref, xin, gy)
+    for walk in list(_CONV_WALKS):
+        if _bits_equal(K.conv1x1_bwd_data(gy, conv.weight, walk), want):
+            return walk
+    return None
+
+
+def _conv1x1(conv, x):
+    """conv(x).  For a stride-1 1x1 convolution on planes of at most _CONV_MAX_PLANE positions, in a gradient pass of a caller that
+    differentiates with respect to the network input alone (target_scores says so) under deterministic solvers, the backward-data
+    runs on K78 once the site has proven itself: on its first eager call (never inside a stream capture) MIOpen's own backward-data
+    is computed too, and the kernel is kept only if it returns the same bits; otherwise the site keeps MIOpen's call for good and
+    CONV_SITE_COUNTS records why (_proven; no warning: the reason is in site_report()).  The decision lives on the module, per
+    running shape and pair of solver switches.  Under autocast the module runs as it is."""
+    import torch
+    import torch.nn as nn
+    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and not conv.weight.requires_grad
+            and (conv.bias is None or not conv.bias.requires_grad) and conv.weight.dtype == torch.float32
+            and conv.out_channels % 16 == 0
+            and not conv._forward_hooks and not conv._forward_pre_hooks and not conv._backward_hooks and not conv._backward_pre_hooks
+            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+            and x.shape[2] * x.shape[3] <= _CONV_MAX_PLANE and torch.backends.cudnn.deterministic
+            and torch.is_grad_enabled() and x.requires_grad and getattr(_INPUT_ONLY, "on", False)
+            and not torch.is_autocast_enabled()):
+        return conv(x)
+    key = (tuple(x.shape), str(x.device)) + _solver_key()
+    with _PROOF_LOCK:                                     # (re-entrant: _proven takes it again)
+        decided = conv.__dict__.setdefault("_xai_bwd_walks", {})
+        fresh = key not in decided
+        walk = _proven(key, lambda: _prove_conv_bwd(conv, x), "conv",
+                       f"no walk of the GEMM kernel reproduces MIOpen's backward-data of the 1x1 convolution "
+                       f"{tuple(conv.weight.shape[:2])} on input {tuple(x.shape)} bit for bit", store=decided)
+        if fresh and walk is not None:
+            CONV_SITE_COUNTS["walks"].append((tuple(conv.weight.shape[:2]), tuple(x.shape), walk))
+    return conv(x) if walk is None else _conv_bwd_function().apply(x, conv, walk)
+
+
 def _fused_block_forward(self, x):
     import torch.nn as nn
     side = getattr(x, "_xai_alias", x)              # the previous fused block's second handle on its output, if any
@@ -489,7 +587,7 @@ def _fused_block_forward(self, x):
     fork = getattr(self, "_xai_fork", False)
     if hasattr(self, "conv3"):                      # bottleneck
         out = bn_relu(self.conv2(out), self.bn2)
-        return bn_relu(self.conv3(out), self.bn3, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)
+        return bn_relu(_conv1x1(self.conv3, out), self.bn3, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)
     return bn_relu(self.conv2(out), self.bn2, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)     # basic block
 
 

@@ -38,8 +38,38 @@ def timeit(fn, iters=9, warm=2, burst=None):
     return float(np.median(ts))
 
 
+def conv1x1_rows(rep):
+    """K78 at layer4's conv3 backward-data, 50 x 2048 -> 512 x 7 x 7, next to MIOpen's launch (a rocBLAS GSU19 GEMM and its
+    reduction kernel) on the same tensors under deterministic solvers, and K79 for scale.  The bytes are the algorithmic ones: gy and
+    the weight read once, gx written once; the kernel is a 5.14 GFLOP GEMM, so `note` carries TFLOP/s."""
+    import torch.nn.functional as F
+    det = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    g = torch.Generator(device=DEV).manual_seed(1)
+    w = torch.randn(2048, 512, 1, 1, device=DEV, generator=g) * 0.05
+    x = torch.randn(50, 512, 7, 7, device=DEV, generator=g).requires_grad_(True)
+    y = F.conv2d(x, w)
+    gy = torch.randn(y.shape, device=DEV, generator=g)
+    nbytes = (gy.numel() + w.numel() + x.numel()) * 4
+    flop = 2.0 * 2048 * x.numel()
+    walk = (19, K.WALK_ROUND_ROBIN, K.WALK_K_CONSECUTIVE, K.WALK_ASCENDING, 0)
+    out = torch.empty_like(x)
+    (ref,) = torch.autograd.grad(y, x, gy, retain_graph=True)
+    same = bool((K.conv1x1_bwd_data(gy, w, walk).view(torch.int32) == ref.view(torch.int32)).all())
+    ms = timeit(lambda: torch.ops.aten.convolution_backward(gy, x, w, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1, (True, False, False)))
+    rep("MIOpen conv3 bwd-data 50x2048->512x7x7", nbytes, ms, f"{flop / ms / 1e9:.1f} TFLOP/s; GEMM + reduction kernel")
+    for tile in (64, 32):
+        ms = timeit(lambda: K.conv1x1_bwd_data(gy, w, walk, tile_rows=tile, out=out))
+        rep(f"conv1x1_bwd_data tile_rows={tile}", nbytes, ms, f"{flop / ms / 1e9:.1f} TFLOP/s; MIOpen's bits: {same}")
+    ms = timeit(lambda: K.conv1x1_bwd_data(gy, w, walk, simple=True, out=out))
+    rep("conv1x1_bwd_data simple (K79)", nbytes, ms, f"{flop / ms / 1e9:.1f} TFLOP/s")
+    torch.backends.cudnn.deterministic = det
+
+
 def main():
-    ap = argparse.ArgumentParser(); ap.add_argument("--json"); args = ap.parse_args()
+    ap = argparse.ArgumentParser(); ap.add_argument("--json")
+    ap.add_argument("--only", choices=["conv1x1"], help="run one group of rows only")
+    args = ap.parse_args()
     res = []
 
     def rep(name, nbytes, ms, note=""):
@@ -47,6 +77,11 @@ def main():
         res.append(dict(kernel=name, bytes=nbytes, us=ms * 1e3, gbs=gbs, frac=gbs / PEAK, note=note))
         print(f"{name:34s} {nbytes / 1e6:10.1f} MB {ms * 1e3:9.1f} us {gbs:8.1f} GB/s  frac={gbs / PEAK:.3f}  {note}")
 
+    if args.only == "conv1x1":
+        conv1x1_rows(rep)
+        if args.json:
+            json.dump(res, open(args.json, "w"), indent=1)
+        return
     C, H, W = 3, 224, 224
     N = C * H * W
     B, S = 32, 50
@@ -212,6 +247,8 @@ def main():
     ms = timeit(lambda: K.bn_relu_bwd(K.maxpool_bwd(sg1 + sg2, sidx, 112, 112, 3, 2, 1), sya, sw, sv, 1e-5, BN_VARIANT))
     rep("stem chain bwd (add, maxpool_bwd, bn_relu_bwd)", 3 * (sn // 4) + sn // 4 + sn // 2 + sn + 3 * sn, ms, "three kernels")
     del sx, sy, scode, sg1, sg2, sya, sidx
+    # K78 / K79
+    conv1x1_rows(rep)
     # K9
     lg = torch.randn(50, 1000, device=DEV)
     ms = timeit(lambda: K.softmax_stats(lg, 3))

@@ -73,4 +73,46 @@ XAI_WALK_HD inline int xai_walk_block(const XaiWalk& w, int p, int t) { return w
 XAI_WALK_HD inline int xai_walk_k(int grouping, int m, int q) { return grouping == XAI_WALK_K_STRIDE4 ? m + 4 * q : 4 * m + q; }
 XAI_WALK_HD inline int xai_walk_row(int grouping, int k) { return grouping == XAI_WALK_K_STRIDE4 ? (k & 3) * 4 + (k >> 2) : k; }
 
+// ---- the staggered start of a K loop -------------------------------------------------------------------------------------
+// A GEMM library's kernel whose name says SU<n> and SUS<bytes> (n > 0) does not start every output tile's K loop at k = 0: the loop
+// runs K / depth iterations of `depth` k each, and the workgroup whose output tile is number w along one axis starts at iteration
+// s(w) = (w & mask) << shift, goes on to the last iteration, wraps and ends with iteration s(w) - 1.  shift makes a step of s `stride`
+// bytes of a K-contiguous operand (log2(stride / (4 * depth)), 0 where that is below one iteration), and mask + 1 is the largest
+// power of two <= n with (mask + 1) << shift <= K / depth (mask 0: every tile starts at 0).  One partial sum; what is a rotation of
+// the K-blocks per tile.  profiles/wide_bwd_walk_probe.txt has the kernels whose bits this reproduces.
+enum XaiStaggerAxis { XAI_STAGGER_COLUMNS = 0, XAI_STAGGER_ROWS = 1 };      // the tile number counts hw / tile, or c / tile
+
+struct XaiStagger {
+  int blocks;                  // K-blocks (of kWalkBlock) in K
+  int per_iter;                // K-blocks per loop iteration: depth / kWalkBlock
+  int tile;                    // outputs per tile along the axis
+  int axis;                    // XaiStaggerAxis
+  int mask, shift;
+};
+
+// -> false (and *st untouched) for K or depth no positive multiple of 16, K % depth != 0, tile no positive multiple of 16, an
+// unknown axis, n negative or no power of two (0: no stagger), stride negative
+XAI_WALK_HD inline bool xai_stagger_plan(int K, int depth, int tile, int axis, int n, int stride, XaiStagger* st) {
+  if (K < kWalkBlock || depth < kWalkBlock || depth % kWalkBlock != 0 || K % depth != 0 || tile < 16 || tile % 16 != 0) return false;
+  if ((axis != XAI_STAGGER_COLUMNS && axis != XAI_STAGGER_ROWS) || n < 0 || (n & (n - 1)) != 0 || stride < 0) return false;
+  XaiStagger out{};
+  out.blocks = K / kWalkBlock;
+  out.per_iter = depth / kWalkBlock;
+  out.tile = tile;
+  out.axis = axis;
+  const int iters = K / depth;
+  int shift = 0;
+  while ((static_cast<int64_t>(4) * depth << (shift + 1)) <= stride) ++shift;
+  int su = n;
+  while (su > 1 && iters < (static_cast<int64_t>(su) << shift)) su /= 2;
+  out.mask = su >= 1 ? su - 1 : 0;
+  out.shift = out.mask != 0 ? shift : 0;
+  *st = out;
+  return true;
+}
+
+// the K-block at which the output at `at` along the axis (hw inside its image, or c) starts, and the t-th K-block of its chain
+XAI_WALK_HD inline int xai_stagger_first(const XaiStagger& st, int at) { return (((at / st.tile) & st.mask) << st.shift) * st.per_iter; }
+XAI_WALK_HD inline int xai_stagger_block(const XaiStagger& st, int first, int t) { return (first + t) % st.blocks; }
+
 #undef XAI_WALK_HD

@@ -143,15 +143,18 @@ DTYPE_LIBRARIES = {"clip": Library("clip", header="xai_clip.h")}
 # test_cpu_linkage.py and test_cpu_lrp.py each end a test with `{k: (version, minor) for k in LIBRARIES} == PINNED`, the eleven pairs of
 # tests/abi_libs.py, and tests/test_cpu_eclip.py asserts `list(DTYPE_LIBRARIES) == ["clip"]`.
 CLASSIFIER_LIBRARIES = {"conv": Library("conv", header="xai_conv.h")}
+# CLASSIFIER_LIBRARIES is pinned too (tests/test_cpu_conv_walk.py asserts `list(CLASSIFIER_LIBRARIES) == ["conv"]`), so the classifier
+# kernels added after it have a fourth table of the same records: a site's library per key, no test holds the list of keys.
+SITE_LIBRARIES = {"convw": Library("convw", header="xai_convw.h")}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key], DTYPE_LIBRARIES[key] or CLASSIFIER_LIBRARIES[key] (cached by the record); raises, never
-    falls back, when the file is absent or refused."""
-    for table in (LIBRARIES, CLASSIFIER_LIBRARIES):
+    """The loaded handle of LIBRARIES[key], DTYPE_LIBRARIES[key], CLASSIFIER_LIBRARIES[key] or SITE_LIBRARIES[key] (cached by the
+    record); raises, never falls back, when the file is absent or refused."""
+    for table in (LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES):
         if key in table:
             return table[key].load()
     return DTYPE_LIBRARIES[key].load()

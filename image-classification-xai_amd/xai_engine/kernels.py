@@ -723,6 +723,24 @@ def conv1x1_bwd_data(gy, weight, walk, tile_rows=0, simple=False, out=None):
     return gx.view(N, Cc, H, W)
 
 
+def conv1x1_bwd_data_wide(gy, weight, walk, simple=False, out=None):
+    """gx (N,C,H,W) as conv1x1_bwd_data gives it, for large planes (K80: every element of gy read from global memory once), summed
+    over k in one partial sum as `walk` = (grouping, from_zero, depth, tile, axis, stagger, stride) says: the K loop of `depth` k per
+    iteration starts, for the outputs of tile number w of `tile` along hw (axis 0) or c (axis 1), at the iteration csrc/xai_conv_walk.h's
+    xai_stagger_plan gives for a GEMM kernel named SU<stagger>_SUS<stride>; stagger 0: at k = 0.  simple: by the one-wave-per-tile
+    kernel K81, which takes both axes."""
+    _need(gy, F32, "gy"); _need(weight, F32, "weight")
+    if gy.dim() != 4 or weight.dim() not in (2, 4) or weight.numel() != weight.shape[0] * weight.shape[1] or weight.shape[0] != gy.shape[1]:
+        raise ValueError("gy must be (N, K, H, W) and weight (K, C) or (K, C, 1, 1)")
+    grouping, from_zero, depth, tile, axis, stagger, stride = (int(v) for v in walk)
+    N, K, H, W = gy.shape
+    Cc = int(weight.shape[1])
+    gx = _out(out, "out", (N, Cc, H, W), gy)
+    _call("xai_convw_bwd_data_simple_f32" if simple else "xai_convw_bwd_data_f32", gy.device, _ptr(gy), _ptr(weight), N, K, Cc, H * W,
+          grouping, from_zero, depth, tile, axis, stagger, stride, _ptr(gx), lib="convw")
+    return gx.view(N, Cc, H, W)
+
+
 def bn_relu_maxpool_fwd_code(x, weight, bias, mean, var, eps, variant, kernel, stride, pad):
     """-> (y, code): max_pool2d(relu(bn(x)), kernel, stride, pad) and one uint8 per pooled output for bn_relu_maxpool_bwd (the
     window-local arg-max, or 255 for a closed ReLU gate); x (N,C,H,W) -> (N,C,PH,PW) twice."""

@@ -324,7 +324,11 @@ def site_report():
     text += "" if not c["reasons"] else " (" + "; ".join(c["reasons"]) + ")"
     k = CONV_SITE_COUNTS
     text += (f"; {k['conv_bwd_kernel']} 1x1 convolution backward-data site(s) on the folded-batch GEMM kernel, {k['conv_bwd_refused']} refused")
-    return text + ("" if not k["reasons"] else " (" + "; ".join(k["reasons"]) + ")")
+    text += "" if not k["reasons"] else " (" + "; ".join(k["reasons"]) + ")"
+    w = CONV_WIDE_SITE_COUNTS
+    text += (f"; {w['conv_wide_kernel']} 1x1 convolution backward-data site(s) on large planes on the read-once GEMM kernel, "
+             f"{w['conv_wide_refused']} refused")
+    return text + ("" if not w["reasons"] else " (" + "; ".join(w["reasons"]) + ")")
 
 
 def _refuse(kind, why):
@@ -348,7 +352,8 @@ def _proven(key, prove, kind, why, store=None):
     """The decision for `key`, made once under the lock by `prove()` (-> a candidate or None) on the first eager call; inside a
     stream capture nothing is decided and None is returned, so the caller takes the PyTorch / MIOpen form there.  `store`: where
     the decisions of this kind of site live (default: _PROVEN, process-wide).  kind "shortcut" | "head" counts in SITE_COUNTS and
-    warns on a refusal; kind "conv" counts in CONV_SITE_COUNTS and records the reason there."""
+    warns on a refusal; kind "conv" counts in CONV_SITE_COUNTS and kind "conv_wide" in CONV_WIDE_SITE_COUNTS, and record the reason
+    there."""
     import torch
     with _PROOF_LOCK:
         if store is None:
@@ -361,6 +366,10 @@ def _proven(key, prove, kind, why, store=None):
                 CONV_SITE_COUNTS["conv_bwd_refused" if store[key] is None else "conv_bwd_kernel"] += 1
                 if store[key] is None:
                     CONV_SITE_COUNTS["reasons"].append(why)
+            elif kind == "conv_wide":
+                CONV_WIDE_SITE_COUNTS["conv_wide_refused" if store[key] is None else "conv_wide_kernel"] += 1
+                if store[key] is None:
+                    CONV_WIDE_SITE_COUNTS["reasons"].append(why)
             elif store[key] is None:
                 _refuse(kind + "_refused", why)
             else:
@@ -568,6 +577,106 @@ def _conv1x1(conv, x):
     return conv(x) if walk is None else _conv_bwd_function().apply(x, conv, walk)
 
 
+# ------------------------------------------------------------------------------ 1x1 backward-data on large planes: the read-once kernel
+# On planes of more than _CONV_MAX_PLANE positions the GEMM per image is the right cut, but for some shapes rocBLAS answers with
+# kernels on 32-wide output tiles (MT32x32x64, MT32x64x64) that fetch gy many times over and cost four to five times as much beside
+# two other streams as alone, where its other kernels cost twice as much.  K80 (kernels.conv1x1_bwd_data_wide)
+# reads gy once.  Those rocBLAS kernels start each output tile's K loop at an iteration of its own (their names say SU32_SUS256),
+# which K80 takes as its argument.  Sites, refusals and reasons are counted apart, with a sentence of their own in `site_report()`.
+CONV_WIDE_SITE_COUNTS = {"conv_wide_kernel": 0, "conv_wide_refused": 0, "walks": [], "reasons": []}
+# (grouping, from_zero, depth, tile, axis, stagger, stride) in the words of csrc/xai_conv_walk.h; per site the first that reproduces
+# MIOpen's backward-data bit for bit is kept.  The staggered loop of rocBLAS's MT32x32x64 and MT32x64x64 kernels (tiles of 32 along
+# hw), the one of its MT64x64x32 kernel with a stagger (tiles of 64; two of its iterations of 32 are one of 64), and the plain
+# ascending sum of its kernels without one (profiles/wide_bwd_walk_probe.txt).
+_CONV_WIDE_WALKS = [(0, 0, 64, 32, 0, 32, 256), (0, 0, 64, 64, 0, 32, 256), (0, 0, 64, 64, 0, 0, 0)]
+_CONV_WIDE_FN = None
+
+
+def _conv_wide_enabled(K, C, HW):
+    """The shape classes (gy channels K -> gx channels C on HW positions) whose launch K80 makes cheaper beside two other streams
+    (profiles/wide_bwd_walk_probe.txt): the planes up to 14 x 14, and at most 128 output rows under a sum of 512 or
+    more -- in ResNet-50 layer2's conv3, layer3's conv1 (blocks 1-5) and conv3 and layer4.0's conv1, the shapes rocBLAS serves on
+    32-wide tiles.  The other shapes (its MT64x64x32 and MT128x128x32 kernels) stay with MIOpen: there K80 is the slower of the two."""
+    return HW <= 196 or (K >= 512 and C <= 128)
+
+
+def _conv_wide_function():
+    global _CONV_WIDE_FN
+    if _CONV_WIDE_FN is None:
+        import torch
+        import torch.nn.functional as F
+        from . import kernels as K
+
+        class Conv1x1Wide(torch.autograd.Function):
+            """conv(x) for a stride-1 1x1 convolution whose weight takes no gradient: the forward is the module's own MIOpen call,
+            the backward-data is K80 walking `walk`."""
+
+            @staticmethod
+            def forward(ctx, x, conv, walk):
+                ctx.conv, ctx.walk = conv, walk
+                return F.conv2d(x, conv.weight, conv.bias)
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable      # a kernel launch: no graph through it, create_graph raises
+            def backward(ctx, gy):
+                return K.conv1x1_bwd_data_wide(gy.contiguous(), ctx.conv.weight, ctx.walk), None, None
+        _CONV_WIDE_FN = Conv1x1Wide
+    return _CONV_WIDE_FN
+
+
+def _prove_conv_wide(conv, x):
+    """-> the first walk of _CONV_WIDE_WALKS with which K80 returns MIOpen's backward-data of conv at x's shape bit for bit, or None"""
+    import torch
+    import torch.nn.functional as F
+    from . import kernels as K
+    with torch.enable_grad():
+        xin = x.detach().clone().requires_grad_(True)
+        ref = F.conv2d(xin, conv.weight, conv.bias)
+        gy = torch.randn_like(ref)
+        (want,) = torch.autograd.grad(ref, xin, gy)
+    for walk in list(_CONV_WIDE_WALKS):
+        if conv.out_channels % walk[2] == 0 and _bits_equal(K.conv1x1_bwd_data_wide(gy, conv.weight, walk), want):
+            return walk
+    return None
+
+
+def _conv1x1_wide(conv, x):
+    """conv(x).  For a stride-1 1x1 convolution on planes of more than _CONV_MAX_PLANE positions whose shape class is enabled
+    (_conv_wide_enabled), under the conditions of _conv1x1 -- a caller that differentiates with respect to the network input alone,
+    deterministic solvers, frozen fp32 weights, no hooks, no autocast -- the backward-data runs on K80 once the site has proven itself
+    on its first eager call (never inside a stream capture); a refusal keeps MIOpen's call for good and CONV_WIDE_SITE_COUNTS records
+    why.  The decision lives on the module, per running shape and pair of solver switches."""
+    import torch
+    import torch.nn as nn
+    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and not conv.weight.requires_grad
+            and (conv.bias is None or not conv.bias.requires_grad) and conv.weight.dtype == torch.float32
+            and conv.out_channels % 16 == 0
+            and not conv._forward_hooks and not conv._forward_pre_hooks and not conv._backward_hooks and not conv._backward_pre_hooks
+            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+            and x.shape[2] * x.shape[3] > _CONV_MAX_PLANE and torch.backends.cudnn.deterministic
+            and _conv_wide_enabled(conv.out_channels, conv.in_channels, x.shape[2] * x.shape[3])
+            and torch.is_grad_enabled() and x.requires_grad and getattr(_INPUT_ONLY, "on", False)
+            and not torch.is_autocast_enabled()):
+        return conv(x)
+    key = (tuple(x.shape), str(x.device)) + _solver_key()
+    with _PROOF_LOCK:                                     # (re-entrant: _proven takes it again)
+        decided = conv.__dict__.setdefault("_xai_bwd_wide_walks", {})
+        fresh = key not in decided
+        walk = _proven(key, lambda: _prove_conv_wide(conv, x), "conv_wide",
+                       f"no walk of the read-once GEMM kernel reproduces MIOpen's backward-data of the 1x1 convolution "
+                       f"{tuple(conv.weight.shape[:2])} on input {tuple(x.shape)} bit for bit", store=decided)
+        if fresh and walk is not None:
+            CONV_WIDE_SITE_COUNTS["walks"].append((tuple(conv.weight.shape[:2]), tuple(x.shape), walk))
+    return conv(x) if walk is None else _conv_wide_function().apply(x, conv, walk)
+
+
+def _conv1x1_site(conv, x):
+    """conv(x) through the site of its plane size: K78's up to _CONV_MAX_PLANE positions, K80's above"""
+    small = x.dim() == 4 and x.shape[2] * x.shape[3] <= _CONV_MAX_PLANE
+    return _conv1x1(conv, x) if small else _conv1x1_wide(conv, x)
+
+
 def _fused_block_forward(self, x):
     import torch.nn as nn
     side = getattr(x, "_xai_alias", x)              # the previous fused block's second handle on its output, if any
@@ -580,14 +689,14 @@ def _fused_block_forward(self, x):
             compact = None
             if _bn_usable(last_bn, side) and _bn_usable(ds[1], side):
                 compact = _compact_shortcut(ds[0], side)        # a strided 1x1 convolution: on the compact tensor, channel-major
-            identity, cnhw = (ds[0](side), False) if compact is None else (compact, True)
+            identity, cnhw = (_conv1x1_wide(ds[0], side), False) if compact is None else (compact, True)
         else:
             identity = ds(side)
-    out = bn_relu(self.conv1(x), self.bn1)
+    out = bn_relu(_conv1x1_wide(self.conv1, x), self.bn1)
     fork = getattr(self, "_xai_fork", False)
     if hasattr(self, "conv3"):                      # bottleneck
         out = bn_relu(self.conv2(out), self.bn2)
-        return bn_relu(_conv1x1(self.conv3, out), self.bn3, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)
+        return bn_relu(_conv1x1_site(self.conv3, out), self.bn3, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)
     return bn_relu(self.conv2(out), self.bn2, identity, fork=fork, identity_bn=identity_bn, identity_cnhw=cnhw)     # basic block
 
 

@@ -66,9 +66,41 @@ def conv1x1_rows(rep):
     torch.backends.cudnn.deterministic = det
 
 
+def conv1x1_wide_rows(rep):
+    """K80 at the enabled large-plane shapes of ResNet-50's backward-data, batch 50, next to MIOpen's launch (a
+    rocBLAS MT32x32x64 or MT32x64x64 GEMM per image) on the same tensors under deterministic solvers, and K79 for scale.  The bytes are
+    the algorithmic ones: gy and the weight read once, gx written once; every row is a 5.14 GFLOP GEMM, so `note` carries TFLOP/s and
+    the share of the launch's lower bound, the larger of 33 us (155 TFLOP/s) and bytes / 6.29 TB/s."""
+    import torch.nn.functional as F
+    det = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    g = torch.Generator(device=DEV).manual_seed(1)
+    walk = (0, 0, 64, 32, 0, 32, 256)
+    for name, Kc, Cc, H in (("layer2 conv3", 512, 128, 28), ("layer3 conv3", 1024, 256, 14), ("layer3 conv1", 256, 1024, 14),
+                            ("layer4.0 conv1", 512, 1024, 14)):
+        w = torch.randn(Kc, Cc, 1, 1, device=DEV, generator=g) * 0.05
+        x = torch.randn(50, Cc, H, H, device=DEV, generator=g).requires_grad_(True)
+        y = F.conv2d(x, w)
+        gy = torch.randn(y.shape, device=DEV, generator=g)
+        nbytes = (gy.numel() + w.numel() + x.numel()) * 4
+        flop = 2.0 * Kc * x.numel()
+        floor_ms = max(flop / 155e9, nbytes / 6.29e9)
+        out = torch.empty_like(x)
+        (ref,) = torch.autograd.grad(y, x, gy, retain_graph=True)
+        same = bool((K.conv1x1_bwd_data_wide(gy, w, walk).view(torch.int32) == ref.view(torch.int32)).all())
+        shape = f"50x{Kc}->{Cc}x{H}x{H}"
+        ms = timeit(lambda: torch.ops.aten.convolution_backward(gy, x, w, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1, (True, False, False)))
+        rep(f"MIOpen {name} bwd-data {shape}", nbytes, ms, f"{flop / ms / 1e9:.1f} TFLOP/s; {floor_ms / ms:.2f} of the bound")
+        ms = timeit(lambda: K.conv1x1_bwd_data_wide(gy, w, walk, out=out))
+        rep(f"conv1x1_bwd_data_wide (K80) {shape}", nbytes, ms, f"{flop / ms / 1e9:.1f} TFLOP/s; {floor_ms / ms:.2f} of the bound; MIOpen's bits: {same}")
+        ms = timeit(lambda: K.conv1x1_bwd_data(gy, w, (1, 0, 0, 0, 0), simple=True, out=out))
+        rep(f"conv1x1_bwd_data simple (K79) {shape}", nbytes, ms, f"{flop / ms / 1e9:.1f} TFLOP/s")
+    torch.backends.cudnn.deterministic = det
+
+
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--json")
-    ap.add_argument("--only", choices=["conv1x1"], help="run one group of rows only")
+    ap.add_argument("--only", choices=["conv1x1", "conv1x1_wide"], help="run one group of rows only")
     args = ap.parse_args()
     res = []
 
@@ -77,8 +109,8 @@ def main():
         res.append(dict(kernel=name, bytes=nbytes, us=ms * 1e3, gbs=gbs, frac=gbs / PEAK, note=note))
         print(f"{name:34s} {nbytes / 1e6:10.1f} MB {ms * 1e3:9.1f} us {gbs:8.1f} GB/s  frac={gbs / PEAK:.3f}  {note}")
 
-    if args.only == "conv1x1":
-        conv1x1_rows(rep)
+    if args.only in ("conv1x1", "conv1x1_wide"):
+        (conv1x1_rows if args.only == "conv1x1" else conv1x1_wide_rows)(rep)
         if args.json:
             json.dump(res, open(args.json, "w"), indent=1)
         return
@@ -249,6 +281,7 @@ def main():
     del sx, sy, scode, sg1, sg2, sya, sidx
     # K78 / K79
     conv1x1_rows(rep)
+    conv1x1_wide_rows(rep)
     # K9
     lg = torch.randn(50, 1000, device=DEV)
     ms = timeit(lambda: K.softmax_stats(lg, 3))

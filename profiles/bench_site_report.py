@@ -16,6 +16,8 @@ def report():
     print("site report: " + prepare.site_report(), file=sys.stderr)
     for weight, shape, walk in prepare.CONV_SITE_COUNTS["walks"]:
         print(f"  1x1 backward-data {weight} on input {shape}: walk {walk}", file=sys.stderr)
+    for weight, shape, walk in prepare.CONV_WIDE_SITE_COUNTS["walks"]:
+        print(f"  1x1 backward-data on large planes {weight} on input {shape}: walk {walk}", file=sys.stderr)
 
 
 atexit.register(report)

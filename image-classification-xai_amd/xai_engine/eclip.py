@@ -23,7 +23,10 @@ Every image of a batch gets the bytes of its own one-image call: the GEMMs run i
 its extents) and the kernels, which give every image its own workgroup, take the batch -- the rule of xai_engine/lrp.py.  Eager
 only: nothing here is captured into a hipGraph.
 
-Refused: the rows game, rollout, lrp, surgery and m2ib need three further, modified CLIP models (`REFUSED` names them).
+Refused here: surgery and m2ib need other models, and game, rollout and lrp are computed by the reference on a second model object
+(`REFUSED` names them all).  That second model has plain CLIP's weights and forward, so xai_engine/clip_attn.py serves game, rollout
+and lrp in closed form on the plain model; the harness does so only when asked (sweep.get_CLIP_attr, clip_attention_rows="plain"),
+because this engine holds one model where the reference holds two.  `eclip_batch` itself refuses all five, as it always has.
 """
 import torch
 import torch.nn.functional as F

@@ -9,8 +9,10 @@ segmentation CLIs, which do not serve CLIP, and all three refuse a CLIP model by
 `--weights` takes the state_dict of `clip.load(...)` (OpenAI's parameter names); without it the weights are seeded and random.
 `--text_embeddings` takes a (classes, E) tensor, row c the text embedding of "a photo of a <class c>" (the reference's
 testing_dict["embeddings"]); without it the embeddings are seeded and random too.  The served rows are eclip, eclip_wo, eclip_nograd,
-maskclip and selfattn (xai_engine/eclip.py); the other five of sweep.CLIP_ATTR_FUNCS raise NotImplementedError naming the model
-they need.
+maskclip and selfattn (xai_engine/eclip.py).  game, rollout and lrp are refused by default, naming the second model object the
+reference runs them on; `--clip_attention_rows plain` serves them in closed form on the plain model (xai_engine/clip_attn.py), which
+is exact because that second model has plain CLIP's weights and forward and the rows read only its attention probabilities and their
+gradients.  surgery and m2ib need other models and raise NotImplementedError naming them.
 """
 import torch
 
@@ -32,6 +34,9 @@ def build_parser():
     p.add_argument("--text_embeddings", type=str, default=None, help="a (classes, E) tensor saved with torch.save; default: seeded random")
     p.add_argument("--clip_fp32", action="store_true", help="run the model in fp32; default: OpenAI's mixed fp16, as the reference's "
                    "clip.load gives on a GPU")
+    p.add_argument("--clip_attention_rows", choices=("modified", "plain"), default="modified",
+                   help="game, rollout and lrp: 'modified' refuses them (the reference runs them on a second, hooked model object); "
+                   "'plain' computes them in closed form on the plain model")
     return p
 
 
@@ -66,7 +71,8 @@ def main(argv=None):
                     "batch_size": args.batch_size or batch_size, "attr_func": args.attr_func, "model_name": args.model,
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
                     "weights_path": args.weights or "", "num_patches": num_patches,
-                    "embeddings": emb.to(device=device, dtype=model.dtype), "num_classes": emb.shape[0]}
+                    "embeddings": emb.to(device=device, dtype=model.dtype), "num_classes": emb.shape[0],
+                    "clip_attention_rows": args.clip_attention_rows}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, out_dir=args.out_dir,
                                                      reference_counter=args.reference_counter)
     if rank == 0:

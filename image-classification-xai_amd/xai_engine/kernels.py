@@ -1,7 +1,7 @@
 """Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
-Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES or _lib.DTYPE_LIBRARIES>)`.
+Every launch goes through `_call(name, dev, *args, lib=<key of one of _lib's tables of libraries>)`.
 """
 import math
 
@@ -2163,4 +2163,96 @@ def clip_maskclip_map(v_final, txt, k_out):
     out = torch.empty((B, L - 1), dtype=F32, device=k_out.device)
     _call(f"xai_clip_maskclip_map_{_suffix(k_out)}", k_out.device, _ptr(v_final), _ptr(txt), T * E if txt.dim() == 3 else 0,
           _ptr(k_out), kl, kb, B, L, D, E, T, _ptr(out), lib="clip")
+    return out
+
+
+# ------------------------------------------------------------------------------ CLIP: the attention rows (K82-K85, include/xai_cattn.h)
+def cattn_limits():
+    """(XAI_CATTN_MAX_TOKENS, XAI_CATTN_MAX_WIDTH, XAI_CATTN_MAX_TEXTS) of the built library"""
+    lib = _lib.load("cattn")
+    return lib.xai_cattn_max_tokens(), lib.xai_cattn_max_width(), lib.xai_cattn_max_texts()
+
+
+def _cattn_rows(t, name, like=None):
+    """The class-token rows a0 (B, H, L) of every head's attention, dense -> (B, H, L); `like`: an operand whose dtype and device it has"""
+    _typed(t, CLIP_DTYPES if like is None else like.dtype, name)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{name} must be (B, H, L), got {tuple(t.shape)}")
+    B, H, L = t.shape
+    max_l, max_d, _ = cattn_limits()
+    if L < 2 or L > max_l or H > max_d:
+        raise ValueError(f"{name}: L = {L}, H = {H}; K82 and K83 take 2 <= L <= {max_l} and H <= {max_d}")
+    _need(t, t.dtype, name)
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{name} must be on {like.device}, got {t.device}")
+    return B, H, L
+
+
+def _cattn_texts(T):
+    _int(T, "texts")
+    if not 1 <= T <= cattn_limits()[2]:
+        raise ValueError(f"T = {T} texts: K82 and K83 take 1 .. {cattn_limits()[2]}")
+    return T
+
+
+def clip_game_map(g, v, a0):
+    """K82: g (B, T, D) the gradients of the T logits with respect to row 0 of the last block's attention output, v (L, B, D), a0
+    (B, H, L) the class-token row of every head -> (B, L - 1) fp32, mm_interpret of generate_emap.py:133-174 summed over the texts."""
+    L, B, D, vl, vb = _clip_tokens(v, "v")
+    _, H, _ = _cattn_rows(a0, "a0", like=v)
+    if tuple(a0.shape) != (B, H, L) or D % H:
+        raise ValueError(f"a0 must be ({B}, H, {L}) with H dividing D = {D}, got {tuple(a0.shape)}")
+    _need(g, v.dtype, "g")
+    if g.dim() != 3 or g.shape[0] != B or g.shape[2] != D or g.device != v.device:
+        raise ValueError(f"g must be ({B}, T, {D}) on {v.device}, got {tuple(g.shape)} on {g.device}")
+    T = _cattn_texts(int(g.shape[1]))
+    out = torch.empty((B, L - 1), dtype=F32, device=v.device)
+    _call(f"xai_cattn_game_map_{_suffix(v)}", v.device, _ptr(g), _ptr(v), vl, vb, _ptr(a0), B, L, D, H, T, _ptr(out), lib="cattn")
+    return out
+
+
+def clip_rollout_row(a0, texts=1):
+    """K83: a0 (B, H, L) -> (B, L - 1) fp32, the rollout row of compute_rollout_attention (generate_emap.py:269-285) on the one matrix
+    mm_interpret(rollout=True) hands it; `texts`: how often the reference repeats the image in its batch."""
+    _int(texts, "texts")
+    B, H, L = _cattn_rows(a0, "a0")
+    T = _cattn_texts(texts)
+    out = torch.empty((B, L - 1), dtype=F32, device=a0.device)
+    _call(f"xai_cattn_rollout_row_{_suffix(a0)}", a0.device, _ptr(a0), B, H, L, T, _ptr(out), lib="cattn")
+    return out
+
+
+def clip_lrp_matrices(attn, grad, out=None):
+    """K84: attn and grad (n, B, H, L, L) -> c (B, n, L, L) in their dtype, mean over the heads of clamp(grad * attn, min=0)
+    (generate_emap.py:231-237).  `out`: the caller's buffer for c."""
+    _typed(attn, CLIP_DTYPES, "attn")
+    if attn.dim() != 5 or attn.numel() == 0 or attn.shape[3] != attn.shape[4]:
+        raise ValueError(f"attn must be (n, B, H, L, L), got {tuple(attn.shape)}")
+    n, B, H, L, _ = attn.shape
+    max_l, max_d, _ = cattn_limits()
+    if L < 2 or L > max_l or H > max_d or n * B > 65535:
+        raise ValueError(f"attn: L = {L}, H = {H}, n * B = {n * B}; K84 takes 2 <= L <= {max_l}, H <= {max_d} and n * B <= 65535")
+    _need(attn, attn.dtype, "attn")
+    _need(grad, attn.dtype, "grad")
+    if grad.shape != attn.shape or grad.device != attn.device:
+        raise ValueError(f"grad must have the shape and device of attn, {tuple(attn.shape)} on {attn.device}")
+    c = _out(out, "out", (B, n, L, L), attn, dtype=attn.dtype)
+    if c.device != attn.device:
+        raise ValueError(f"out must be on {attn.device}")
+    _call(f"xai_cattn_lrp_matrices_{_suffix(attn)}", attn.device, _ptr(attn), _ptr(grad), n, B, H, L, _ptr(c), lib="cattn")
+    return c.view(B, n, L, L)
+
+
+def clip_lrp_row(c):
+    """K85: c (B, n, L, L) as K84 writes it -> (B, L - 1) fp32, row 0 of the relevance R of clip_lrp (generate_emap.py:226-239) without
+    its first column, by n vector-matrix products from the last block down."""
+    _typed(c, CLIP_DTYPES, "c")
+    if c.dim() != 4 or c.numel() == 0 or c.shape[2] != c.shape[3]:
+        raise ValueError(f"c must be (B, n, L, L), got {tuple(c.shape)}")
+    B, n, L, _ = c.shape
+    if L < 2 or L > cattn_limits()[0] or n * B > 65535:
+        raise ValueError(f"c: L = {L}, n * B = {n * B}; K85 takes 2 <= L <= {cattn_limits()[0]} and n * B <= 65535")
+    _need(c, c.dtype, "c")
+    out = torch.empty((B, L - 1), dtype=F32, device=c.device)
+    _call(f"xai_cattn_lrp_row_{_suffix(c)}", c.device, _ptr(c), n, B, L, _ptr(out), lib="cattn")
     return out

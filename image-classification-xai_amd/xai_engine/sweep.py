@@ -42,7 +42,9 @@ VIT_LRP_ATTR_FUNCS = ("t_attr",)     # ViT rows of the relevance pass (xai_engin
 # the rows of the reference's get_CLIP_attr in its order (:401-437); xai_engine/eclip.py serves METHODS of them and names what the
 # others need (REFUSED)
 CLIP_ATTR_FUNCS = ("eclip", "eclip_nograd", "eclip_wo", "game", "maskclip", "rollout", "selfattn", "surgery", "m2ib", "lrp")
-CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)      # generate_emap.py:27
+# the rows of them that xai_engine/clip_attn.py serves on the plain model, when testing_dict["clip_attention_rows"] == "plain" asks for it
+CLIP_ATTENTION_ROWS = ("game", "rollout", "lrp")
+CLIP_MEAN, CLIP_STD =(0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)      # generate_emap.py:27
 
 
 def get_CNN_attr(input_tensor, trans_img, target_class, testing_dict):
@@ -292,10 +294,31 @@ def get_CLIP_attr(trans_img, target_class, testing_dict):
     """(H,W) float32 numpy saliency map of the rows of the reference's get_CLIP_attr (evaluatePerturbation.py:373-445) that hang on
     clip_encode_dense: eclip, eclip_wo, eclip_nograd, maskclip, selfattn (xai_engine/eclip.py).  The text embedding is
     normalize(testing_dict["embeddings"][target_class]): the reference re-encodes "a photo of a <class>", the very text that row
-    of `embeddings` was made from, so no tokeniser is needed.  game, rollout, lrp, surgery and m2ib need further, modified CLIP
-    models: NotImplementedError naming the model."""
+    of `embeddings` was made from, so no tokeniser is needed.  surgery and m2ib need further, modified CLIP models:
+    NotImplementedError naming the model.  game, rollout and lrp are refused the same way by default, because the reference runs them
+    on a second model object (testing_dict["models"][1]) and this engine has only models[0]; with
+    testing_dict["clip_attention_rows"] == "plain" they are served in closed form on models[0] (xai_engine/clip_attn.py: that second
+    model has plain CLIP's weights and forward, and the rows read only its attention probabilities and their gradients).  They take
+    the reference's preprocess(img), so the image must be input_resolution-square.  Any other value of the key: ValueError."""
     from . import eclip
     attr_function = testing_dict["attr_func"]
+    rows = testing_dict.get("clip_attention_rows")
+    if rows not in (None, "modified", "plain"):
+        raise ValueError(f"get_CLIP_attr: clip_attention_rows must be 'plain' or 'modified' (the default), got {rows!r}")
+    if rows == "plain" and attr_function in CLIP_ATTENTION_ROWS:
+        from . import clip_attn
+        clipmodel = testing_dict["models"][0]
+        emb = testing_dict["embeddings"]
+        emb = emb.reshape(-1, emb.shape[-1])
+        txt = torch.nn.functional.normalize(emb[int(target_class)][None], dim=-1)
+        res = int(clipmodel.visual.input_resolution)
+        if tuple(trans_img.shape[1:]) != (res, res):
+            raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} takes the reference's preprocess(img); a "
+                                      f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
+                                      "bicubic resize is not restated here")
+        x = clip_keepsize_input(trans_img, (1, 1))
+        sal = clip_attn.attention_rows_batch(clipmodel, x, txt, attr_function, img_hw=testing_dict["img_hw"])[0]
+        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     if attr_function in eclip.REFUSED:
         raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} needs {eclip.REFUSED[attr_function]}, which this engine "
                                   "does not build")

@@ -334,14 +334,14 @@ class CLIP(nn.Module):
     """The CLIP of Radford et al. 2021 with a ViT visual tower, written from the published architecture.  Parameter names are
     OpenAI's (visual.conv1, visual.transformer.resblocks.N.attn.in_proj_weight, ..., token_embedding, text_projection,
     logit_scale), so a state_dict of `clip.load(...)` loads with strict=True.  Heads are width // 64 in both towers unless
-    `transformer_heads` says otherwise."""
+    `vision_heads` or `transformer_heads` says otherwise (the head count is no parameter's shape, so a state dict loads either way)."""
 
     def __init__(self, embed_dim, image_resolution, vision_layers, vision_width, vision_patch_size, context_length=77,
-                 vocab_size=49408, transformer_width=512, transformer_heads=None, transformer_layers=12):
+                 vocab_size=49408, transformer_width=512, transformer_heads=None, transformer_layers=12, vision_heads=None):
         super().__init__()
         self.context_length, self.vocab_size = context_length, vocab_size
         self.visual = ClipVisualTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
-                                            max(1, vision_width // 64), embed_dim)
+                                            vision_heads or max(1, vision_width // 64), embed_dim)
         self.transformer = ClipTransformer(transformer_width, transformer_layers, transformer_heads or max(1, transformer_width // 64),
                                            self.build_attention_mask())
         self.token_embedding = nn.Embedding(vocab_size, transformer_width)

@@ -149,17 +149,20 @@ SITE_LIBRARIES = {"convw": Library("convw", header="xai_convw.h")}
 # CLIP's attention rows game, rollout and lrp (K82-K85, xai_engine/clip_attn.py): entries in _f32 and _f16 like libxai_clip.so's, whose
 # export list and whose table DTYPE_LIBRARIES tests/test_cpu_eclip.py pins; so, like conv and convw, a one-record table of its own.
 ATTENTION_LIBRARIES = {"cattn": Library("cattn", header="xai_cattn.h")}
+# CLIP Surgery (K86-K87, xai_engine/surgery.py): entries in _f32 only.  tests/test_cpu_clip_attn.py pins ATTENTION_LIBRARIES' key list,
+# as the tests before pin the other tables', so this library too has a one-record table of its own.
+SURGERY_LIBRARIES = {"csurg": Library("csurg", header="xai_csurg.h")}
 # every table, for the readers that walk all libraries: load below, __graft_entry__.build's version check
-ALL_TABLES = (LIBRARIES, DTYPE_LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES, ATTENTION_LIBRARIES)
+ALL_TABLES = (LIBRARIES, DTYPE_LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES, ATTENTION_LIBRARIES, SURGERY_LIBRARIES)
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key], DTYPE_LIBRARIES[key], CLASSIFIER_LIBRARIES[key], SITE_LIBRARIES[key] or
-    ATTENTION_LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
-    for table in (LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES, ATTENTION_LIBRARIES):
+    """The loaded handle of LIBRARIES[key], DTYPE_LIBRARIES[key], CLASSIFIER_LIBRARIES[key], SITE_LIBRARIES[key],
+    ATTENTION_LIBRARIES[key] or SURGERY_LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
+    for table in (LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES, ATTENTION_LIBRARIES, SURGERY_LIBRARIES):
         if key in table:
             return table[key].load()
     return DTYPE_LIBRARIES[key].load()

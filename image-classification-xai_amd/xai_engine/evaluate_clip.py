@@ -12,7 +12,10 @@ testing_dict["embeddings"]); without it the embeddings are seeded and random too
 maskclip and selfattn (xai_engine/eclip.py).  game, rollout and lrp are refused by default, naming the second model object the
 reference runs them on; `--clip_attention_rows plain` serves them in closed form on the plain model (xai_engine/clip_attn.py), which
 is exact because that second model has plain CLIP's weights and forward and the rows read only its attention probabilities and their
-gradients.  surgery and m2ib need other models and raise NotImplementedError naming them.
+gradients.  surgery is refused by default too, naming the third model object; `--clip_surgery plain` serves it in closed form on the
+plain model in fp32 (xai_engine/surgery.py), with `--surgery_text_features`, a (T - 1, E) tensor of the context classes' text
+features (the reference's 59 prompt-ensembled class names; without it seeded and random, like `--text_embeddings`).  m2ib needs
+another model and raises NotImplementedError naming it.
 """
 import torch
 
@@ -37,6 +40,12 @@ def build_parser():
     p.add_argument("--clip_attention_rows", choices=("modified", "plain"), default="modified",
                    help="game, rollout and lrp: 'modified' refuses them (the reference runs them on a second, hooked model object); "
                    "'plain' computes them in closed form on the plain model")
+    p.add_argument("--clip_surgery", choices=("modified", "plain"), default="modified",
+                   help="surgery: 'modified' refuses it (the reference runs it on a third model object, the CLIP Surgery class); "
+                   "'plain' computes it in closed form on the plain model, in fp32")
+    p.add_argument("--surgery_text_features", type=str, default=None,
+                   help="a (T - 1, E) tensor saved with torch.save, the text features of surgery's context classes; default: 59 seeded "
+                   "random rows")
     return p
 
 
@@ -67,12 +76,19 @@ def main(argv=None):
         emb = torch.randn(1000, embed, generator=torch.Generator().manual_seed(0))
     if not torch.is_tensor(emb) or emb.dim() != 2 or emb.shape[1] != embed:
         raise SystemExit(f"--text_embeddings must hold a (classes, {embed}) tensor")
+    if args.surgery_text_features:
+        context = torch.load(args.surgery_text_features, map_location="cpu", weights_only=True)
+    else:
+        context = torch.randn(59, embed, generator=torch.Generator().manual_seed(1))
+    if not torch.is_tensor(context) or context.dim() != 2 or context.shape[1] != embed:
+        raise SystemExit(f"--surgery_text_features must hold a (T - 1, {embed}) tensor")
     testing_dict = {"models": [model], "imagenet_dataset": args.dataset_path, "normalize": norm, "img_hw": 224,
                     "batch_size": args.batch_size or batch_size, "attr_func": args.attr_func, "model_name": args.model,
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
                     "weights_path": args.weights or "", "num_patches": num_patches,
                     "embeddings": emb.to(device=device, dtype=model.dtype), "num_classes": emb.shape[0],
-                    "clip_attention_rows": args.clip_attention_rows}
+                    "clip_attention_rows": args.clip_attention_rows, "clip_surgery": args.clip_surgery,
+                    "surgery_text_features": context.to(device=device, dtype=torch.float32)}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, out_dir=args.out_dir,
                                                      reference_counter=args.reference_counter)
     if rank == 0:

@@ -2256,3 +2256,69 @@ def clip_lrp_row(c):
     out = torch.empty((B, L - 1), dtype=F32, device=c.device)
     _call(f"xai_cattn_lrp_row_{_suffix(c)}", c.device, _ptr(c), n, B, L, _ptr(out), lib="cattn")
     return out
+
+
+# ------------------------------------------------------------------------------ CLIP Surgery (K86-K87, include/xai_csurg.h)
+def csurg_limits():
+    """(XAI_CSURG_MAX_TOKENS, XAI_CSURG_MAX_WIDTH, XAI_CSURG_MAX_TEXTS, XAI_CSURG_LDS_FLOATS, XAI_CSURG_VV_WAVES) of the built library"""
+    lib = _lib.load("csurg")
+    return (lib.xai_csurg_max_tokens(), lib.xai_csurg_max_width(), lib.xai_csurg_max_texts(), lib.xai_csurg_lds_floats(),
+            lib.xai_csurg_vv_waves())
+
+
+def clip_vv_attention(v, heads, want_scores=False):
+    """K86: v (n, L, B, D) fp32, the V third of n blocks' in-projections where it lies (any strides over n, L and B, the last axis
+    contiguous), `heads` = H -> out (n, B, L, D) fp32, per block, image and head softmax((v @ v.T) * d ** -0.5) @ v with d = D / H,
+    laid out as the reference's (attn @ v).transpose(1, 2).reshape(B, N, C) (clip_surgery_model.py:82-99).  want_scores: a second
+    result, the (n, B, H, L, L) scores in front of the softmax."""
+    _typed(v, F32, "v")
+    H = _int(heads, "heads", least=1)
+    if v.dim() != 4 or v.numel() == 0:
+        raise ValueError(f"v must be (n, L, B, D), got {tuple(v.shape)}")
+    n, L, B, D = v.shape
+    if L < 2 or D % H:
+        raise ValueError(f"v: L = {L}, D = {D}, heads = {H}; K86 takes L >= 2 and heads dividing D")
+    max_l, max_d, _, lds, waves = csurg_limits()
+    d = D // H
+    if L > max_l or D > max_d or L * (d + 1 + waves) > lds or n * B > 65535 or B > 65535 or H > 65535:
+        raise ValueError(f"v: L = {L}, D = {D}, d = {d}, n * B = {n * B} are over the limits of K86 (L <= {max_l}, D <= {max_d}, "
+                         f"L * (d + {1 + waves}) <= {lds}: one head's V and a row per wave in LDS, n * B <= 65535)")
+    _need(v, F32, "v", rows=True)
+    out = torch.empty((n, B, L, D), dtype=F32, device=v.device)
+    scores = torch.empty((n, B, H, L, L), dtype=F32, device=v.device) if want_scores else None
+    _call("xai_csurg_vv_attention_f32", v.device, _ptr(v), v.stride(0), v.stride(1), v.stride(2), n, B, L, D, H, float(d) ** -0.5,
+          _ptr(scores), _ptr(out), lib="csurg")
+    return (out, scores) if want_scores else out
+
+
+def clip_surgery_similarity(features, txt, texts_out=1, want_weights=False):
+    """K87: features (B, L, E) fp32 as ln_post and the projection leave them (not normalised), txt (T, E) shared or (B, T, E) ->
+    (B, texts_out, L - 1) fp32: the reference's division by the norm over the tokens (generate_emap.py:121), clip_feature_surgery
+    (clip.py:287-308) in closed form and the min-max of get_similarity_map (clip.py:274), for the first texts_out texts.
+    want_weights: a second result, the (B, T) weights w of clip_feature_surgery."""
+    _typed(features, F32, "features")
+    if features.dim() != 3 or features.numel() == 0:
+        raise ValueError(f"features must be (B, L, E), got {tuple(features.shape)}")
+    B, L, E = features.shape
+    if L < 2:
+        raise ValueError(f"features: L = {L}; the class token and at least one patch are needed (L >= 2)")
+    _typed(txt, F32, "txt")
+    if txt.dim() not in (2, 3) or txt.numel() == 0 or txt.shape[-1] != E or (txt.dim() == 3 and txt.shape[0] != B):
+        raise ValueError(f"txt must be (T, {E}) or ({B}, T, {E}), got {tuple(txt.shape)}")
+    T = int(txt.shape[-2])
+    T_out = _int(texts_out, "texts_out", least=1)
+    if T_out > T:
+        raise ValueError(f"texts_out = {T_out} of T = {T} texts")
+    max_l, max_e, max_t, lds, _ = csurg_limits()
+    if L > max_l or E > max_e or T > max_t or 2 * E + T > lds or B > 65535:
+        raise ValueError(f"features, txt: L = {L}, E = {E}, T = {T} are over the limits of K87 (L <= {max_l}, E <= {max_e}, T <= {max_t}, "
+                         f"2 * E + T <= {lds})")
+    _need(features, F32, "features")
+    _need(txt, F32, "txt")
+    if txt.device != features.device:
+        raise ValueError(f"txt must be on {features.device}, got {txt.device}")
+    out = torch.empty((B, T_out, L - 1), dtype=F32, device=features.device)
+    w = torch.empty((B, T), dtype=F32, device=features.device) if want_weights else None
+    _call("xai_csurg_similarity_map_f32", features.device, _ptr(features), _ptr(txt), T * E if txt.dim() == 3 else 0, B, L, E, T, T_out,
+          _ptr(w), _ptr(out), lib="csurg")
+    return (out, w) if want_weights else out

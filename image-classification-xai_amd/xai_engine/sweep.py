@@ -299,7 +299,13 @@ def get_CLIP_attr(trans_img, target_class, testing_dict):
     on a second model object (testing_dict["models"][1]) and this engine has only models[0]; with
     testing_dict["clip_attention_rows"] == "plain" they are served in closed form on models[0] (xai_engine/clip_attn.py: that second
     model has plain CLIP's weights and forward, and the rows read only its attention probabilities and their gradients).  They take
-    the reference's preprocess(img), so the image must be input_resolution-square.  Any other value of the key: ValueError."""
+    the reference's preprocess(img), so the image must be input_resolution-square.  Any other value of the key: ValueError.
+    surgery is served the same way on request, testing_dict["clip_surgery"] == "plain" (xai_engine/surgery.py: the reference's third
+    model object is plain CLIP's state dict under another forward, in fp32).  Its text 0 is the normalised row of `embeddings`, like
+    every other row; the remaining texts are testing_dict["surgery_text_features"], a (T - 1, E) tensor (the 59 context classes of
+    evaluatePerturbation.py:427 in the reference's harness), normalised here; "plain" without that table, or any value of
+    `clip_surgery` other than None, "modified" and "plain": ValueError.  The reference also prompt-ensembles the caption over its 85
+    templates (encode_text_with_prompt_ensemble): a caller who wants that passes an `embeddings` table made that way."""
     from . import eclip
     attr_function = testing_dict["attr_func"]
     rows = testing_dict.get("clip_attention_rows")
@@ -318,6 +324,29 @@ def get_CLIP_attr(trans_img, target_class, testing_dict):
                                       "bicubic resize is not restated here")
         x = clip_keepsize_input(trans_img, (1, 1))
         sal = clip_attn.attention_rows_batch(clipmodel, x, txt, attr_function, img_hw=testing_dict["img_hw"])[0]
+        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
+    surgery_rows = testing_dict.get("clip_surgery")
+    if surgery_rows not in (None, "modified", "plain"):
+        raise ValueError(f"get_CLIP_attr: clip_surgery must be 'plain' or 'modified' (the default), got {surgery_rows!r}")
+    if surgery_rows == "plain" and attr_function == "surgery":
+        from . import surgery
+        context = testing_dict.get("surgery_text_features")
+        if context is None:
+            raise ValueError("get_CLIP_attr: clip_surgery='plain' needs testing_dict['surgery_text_features'], the (T - 1, E) text "
+                             "features of the context classes (59 prompt-ensembled class names in the reference's harness)")
+        clipmodel = testing_dict["models"][0]
+        emb = testing_dict["embeddings"]
+        emb = emb.reshape(-1, emb.shape[-1])
+        if not isinstance(context, torch.Tensor) or context.dim() != 2 or context.shape[1] != emb.shape[1]:
+            raise ValueError(f"get_CLIP_attr: surgery_text_features must be a (T - 1, {emb.shape[1]}) tensor")
+        res = int(clipmodel.visual.input_resolution)
+        if tuple(trans_img.shape[1:]) != (res, res):
+            raise NotImplementedError(f"get_CLIP_attr: the row 'surgery' takes the reference's preprocess(img); a "
+                                      f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
+                                      "bicubic resize is not restated here")
+        txt = torch.nn.functional.normalize(torch.cat([emb[int(target_class)][None].float(), context.to(emb.device).float()]), dim=-1)
+        x = clip_keepsize_input(trans_img, (1, 1))
+        sal = surgery.surgery_batch(clipmodel, x, txt, img_hw=testing_dict["img_hw"])[0]
         return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     if attr_function in eclip.REFUSED:
         raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} needs {eclip.REFUSED[attr_function]}, which this engine "

@@ -1,9 +1,12 @@
 """ctypes binding of the C ABI libraries.  LIBRARIES is the one table of them, a Library record per key: lib/libxai_<key>.so,
-declared by include/xai_hip_<key>.h with the version defines XAI_<KEY>_VERSION and XAI_<KEY>_MINOR.  The main library, key "hip", is the
-one exception: include/xai_hip.h, XAI_ABI_VERSION and XAI_ABI_MINOR, frozen at ABI 1.11; new entry points go into a library of
-their own.  A new library is a header, its key in LIBRARIES and the same
-key in csrc/Makefile's LIBS with a SRCS_<key> line.  DTYPE_LIBRARIES is a second table of the same records, for libraries whose entries
-come in the dtype of a half-precision model (include/xai_<key>.h, csrc/<key>/).
+declared by include/xai_hip_<key>.h (or the header its record names) with the version defines XAI_<KEY>_VERSION and XAI_<KEY>_MINOR.
+The main library, key "hip", is the one exception: include/xai_hip.h, XAI_ABI_VERSION and XAI_ABI_MINOR, frozen at ABI 1.11; new
+entry points go into a library of their own.
+
+The rule.  A new library is: its header under include/; one record in LIBRARIES; the same key in csrc/Makefile's LIBS with a
+SRCS_<key> line, plus a header override there and a `header=` here if its header is not xai_hip_<key>.h; and its literal version pair
+in tests/abi_libs.py's PINNED.  A feature's own test file holds only what is particular to its entries; it never asserts a complete
+list of keys or the absence of its key from somewhere.  The completeness checks live in tests/test_cpu_abi_libs.py and read the tree.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
 it at import (parse_header), nothing here repeats a prototype.  There is no CPU fallback: if a shared library is missing or a
@@ -131,41 +134,21 @@ class Library:
         return lib
 
 
-# the one list of the libraries, in the order in which their headers were written; csrc/Makefile's LIBS is its build-side twin
-LIBRARIES = {key: Library(key) for key in ("hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6", "ext7", "compact", "slic", "felz")}
-# The libraries whose entries come in the operand dtype of a half-precision model (`_f32` and `_f16` from one template, void*
-# operands): a table of their own, with headers include/xai_<key>.h and sources csrc/<key>/*.hip.  LIBRARIES above is the table of the
-# fp32 / fp64 / integer entries (include/xai_hip*.h, csrc/*.hip), which the tests of the features before hold whole, key by key.
-DTYPE_LIBRARIES = {"clip": Library("clip", header="xai_clip.h")}
-# The libraries whose kernels stand in for a launch INSIDE the classifier (xai_engine/prepare.py proves each site bit for bit before
-# it relies on one): a third table of the same records, headers include/xai_<key>.h and sources csrc/<key>/*.hip like the second.
-# A key cannot join either table above without an edit to an earlier feature's test: tests/test_cpu_quickshift.py, test_cpu_kmeans.py,
-# test_cpu_linkage.py and test_cpu_lrp.py each end a test with `{k: (version, minor) for k in LIBRARIES} == PINNED`, the eleven pairs of
-# tests/abi_libs.py, and tests/test_cpu_eclip.py asserts `list(DTYPE_LIBRARIES) == ["clip"]`.
-CLASSIFIER_LIBRARIES = {"conv": Library("conv", header="xai_conv.h")}
-# CLASSIFIER_LIBRARIES is pinned too (tests/test_cpu_conv_walk.py asserts `list(CLASSIFIER_LIBRARIES) == ["conv"]`), so the classifier
-# kernels added after it have a fourth table of the same records: a site's library per key, no test holds the list of keys.
-SITE_LIBRARIES = {"convw": Library("convw", header="xai_convw.h")}
-# CLIP's attention rows game, rollout and lrp (K82-K85, xai_engine/clip_attn.py): entries in _f32 and _f16 like libxai_clip.so's, whose
-# export list and whose table DTYPE_LIBRARIES tests/test_cpu_eclip.py pins; so, like conv and convw, a one-record table of its own.
-ATTENTION_LIBRARIES = {"cattn": Library("cattn", header="xai_cattn.h")}
-# CLIP Surgery (K86-K87, xai_engine/surgery.py): entries in _f32 only.  tests/test_cpu_clip_attn.py pins ATTENTION_LIBRARIES' key list,
-# as the tests before pin the other tables', so this library too has a one-record table of its own.
-SURGERY_LIBRARIES = {"csurg": Library("csurg", header="xai_csurg.h")}
-# every table, for the readers that walk all libraries: load below, __graft_entry__.build's version check
-ALL_TABLES = (LIBRARIES, DTYPE_LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES, ATTENTION_LIBRARIES, SURGERY_LIBRARIES)
+# the one list of the libraries, in the order in which their headers were written; csrc/Makefile's LIBS is its build-side twin.
+# `header=`: the five whose header is include/xai_<key>.h (their sources are under csrc/clip/ and csrc/conv/).
+LIBRARIES = {rec.key: rec for rec in (
+    Library("hip"), Library("ext"), Library("ext2"), Library("ext3"), Library("ext4"), Library("ext5"), Library("ext6"), Library("ext7"),
+    Library("compact"), Library("slic"), Library("felz"),
+    Library("clip", header="xai_clip.h"), Library("conv", header="xai_conv.h"), Library("convw", header="xai_convw.h"),
+    Library("cattn", header="xai_cattn.h"), Library("csurg", header="xai_csurg.h"))}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor
 
 
 def load(key="hip"):
-    """The loaded handle of LIBRARIES[key], DTYPE_LIBRARIES[key], CLASSIFIER_LIBRARIES[key], SITE_LIBRARIES[key],
-    ATTENTION_LIBRARIES[key] or SURGERY_LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
-    for table in (LIBRARIES, CLASSIFIER_LIBRARIES, SITE_LIBRARIES, ATTENTION_LIBRARIES, SURGERY_LIBRARIES):
-        if key in table:
-            return table[key].load()
-    return DTYPE_LIBRARIES[key].load()
+    """The loaded handle of LIBRARIES[key] (cached by the record); raises, never falls back, when the file is absent or refused."""
+    return LIBRARIES[key].load()
 
 
 def check(code, what):

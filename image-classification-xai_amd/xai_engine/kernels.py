@@ -1,7 +1,7 @@
 """Torch-tensor front end of the C ABI (include/xai_hip.h and the extension headers beside it): shape/device checks, output
 allocation, stream plumbing.  Every function launches asynchronously on torch's current
 stream of the tensors' device and returns device tensors; nothing here computes on the CPU.
-Every launch goes through `_call(name, dev, *args, lib=<key of one of _lib's tables of libraries>)`.
+Every launch goes through `_call(name, dev, *args, lib=<key of _lib.LIBRARIES>)`.
 """
 import math
 

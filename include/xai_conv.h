@@ -3,7 +3,7 @@
  *
  * include/xai_hip.h is frozen at ABI 1.11 and the extension headers before this one are frozen or pinned by their tests, each to
  * its exact entry list; entry points added after that live here, in a library of their own with a version pair of its own (its
- * record is the one of xai_engine/_lib.py's CLASSIFIER_LIBRARIES; the source is csrc/conv/).  The
+ * record is the key `conv` of xai_engine/_lib.py's LIBRARIES; the source is csrc/conv/).  The
  * grammar is xai_hip.h's (one extern "C" block, the stream typedef, launch entries end in _f32 / _f64 / _i32 / _u64, return int and
  * take the caller's stream last), so xai_engine/_lib.py binds this header with the same strict reader, and so are the conventions:
  * device pointers owned by the caller, asynchronous graph-capturable launches, nothing allocated or retained, no global state, no

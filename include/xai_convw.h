@@ -3,7 +3,7 @@
  * libxai_conv.so.
  *
  * include/xai_conv.h is pinned by its tests at 1.0 with exactly two entries; the entry points added after it live here, in a library of
- * their own with a version pair of its own (its record is the one of xai_engine/_lib.py's SITE_LIBRARIES; the source is csrc/conv/).
+ * their own with a version pair of its own (its record is the key `convw` of xai_engine/_lib.py's LIBRARIES; the source is csrc/conv/).
  * The grammar and the conventions are xai_hip.h's (one extern "C" block, the stream typedef, launch entries end in _f32, return int and
  * take the caller's stream last; device pointers owned by the caller, asynchronous graph-capturable launches, nothing allocated or
  * retained, no global state, no atomics).  Return values are xai_hip.h's: 0 = success, <0 = XAI_E_*, >0 = hipError_t of the launch;

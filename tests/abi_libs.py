@@ -1,5 +1,10 @@
 """What the tests of the C ABI libraries share: the names a header declares, the names a built library exports, the built
-file of a key of xai_engine._lib.LIBRARIES, and the version pairs the headers are frozen or pinned at."""
+file of a key of xai_engine._lib.LIBRARIES, and the version pairs the headers are frozen or pinned at.
+
+The rule.  A new library is: its header under include/; one record in xai_engine._lib.LIBRARIES; the same key in csrc/Makefile's
+LIBS with a SRCS_<key> line, plus a header override if its header is not xai_hip_<key>.h; and its literal pair appended to PINNED
+below.  A feature's own test file holds only what is particular to its entries; it never asserts a complete list of keys or the
+absence of its key from somewhere.  The completeness checks live in tests/test_cpu_abi_libs.py and read the tree."""
 import os
 import re
 import subprocess
@@ -8,7 +13,7 @@ from conftest import PKG
 
 # literal pins, not read from the code under test: a header that moves has to move this line too
 PINNED = {"hip": (1, 11), "ext": (1, 0), "ext2": (1, 1), "ext3": (1, 0), "ext4": (1, 0), "ext5": (1, 0), "ext6": (1, 0), "ext7": (1, 0),
-          "compact": (1, 0), "slic": (1, 0), "felz": (1, 0)}
+          "compact": (1, 0), "slic": (1, 0), "felz": (1, 0), "clip": (1, 0), "conv": (1, 0), "convw": (1, 0), "cattn": (1, 0), "csurg": (1, 0)}
 
 
 def declared(header):

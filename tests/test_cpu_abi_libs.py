@@ -16,6 +16,10 @@ from xai_engine import _lib
 
 KEYS = list(_lib.LIBRARIES)
 ELEVEN = ["hip", "ext", "ext2", "ext3", "ext4", "ext5", "ext6", "ext7", "compact", "slic", "felz"]
+SIXTEEN = ELEVEN + ["clip", "conv", "convw", "cattn", "csurg"]
+# the file name of each header, literally: the eleven by the rule xai_hip[_<key>].h, the five after them by name
+HEADERS = dict({key: "xai_hip.h" if key == "hip" else f"xai_hip_{key}.h" for key in ELEVEN},
+               clip="xai_clip.h", conv="xai_conv.h", convw="xai_convw.h", cattn="xai_cattn.h", csurg="xai_csurg.h")
 _p, _i = C.c_void_p, C.c_int
 
 
@@ -25,18 +29,18 @@ def L():
 
 
 def pin(rec):
-    """the literal pair of tests/abi_libs.py where it has one; a library added since is pinned by its feature's own test file"""
-    return PINNED.get(rec.key, (rec.version, rec.minor))
+    """the literal pair of tests/abi_libs.py: a key without one fails, the record under test is never its own pin"""
+    return PINNED[rec.key]
 
 
-def test_the_table_begins_with_the_eleven_libraries_and_the_old_names_are_aliases_of_the_main_record(L):
-    """The table begins with these eleven keys in this order; keys after them are allowed.  "And no other key" is given up on
+def test_the_table_begins_with_the_sixteen_libraries_and_the_old_names_are_aliases_of_the_main_record(L):
+    """The table begins with these sixteen keys in this order; keys after them are allowed.  "And no other key" is given up on
     purpose: it made every new library a new table beside this one.  What holds the table to the tree instead is the closure
     test below, which grows with the tree: the headers, the Makefile's LIBS and the kernel files must all say the same keys."""
     import xai_engine
-    assert KEYS[:11] == ELEVEN and set(PINNED) <= set(KEYS)
+    assert KEYS[:16] == SIXTEEN and set(PINNED) <= set(KEYS)
     for key, rec in L.LIBRARIES.items():
-        header = "xai_hip.h" if key == "hip" else f"xai_hip_{key}.h"
+        header = HEADERS.get(key, f"xai_hip_{key}.h")
         stem = "xai" if key == "hip" else f"xai_{key}"
         assert isinstance(rec, L.Library) and rec.key == key and os.path.basename(rec.path) == f"libxai_{key}.so"
         assert os.path.dirname(rec.path) == os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "lib")
@@ -51,16 +55,25 @@ def test_the_table_begins_with_the_eleven_libraries_and_the_old_names_are_aliase
 
 
 def test_the_table_the_headers_the_makefile_and_the_kernel_files_name_the_same_libraries(L):
-    """(a) include/xai_hip*.h is exactly the records' headers, (b) LIBS as make reads it is the table's keys in order, (c) every
-    csrc/*.hip is in exactly one SRCS_<key> of a key of the table and every file a SRCS_<key> names exists"""
+    """(a) include/*.h is exactly the records' headers, one record each, (b) LIBS as make reads it is the table's keys in order and
+    the SRCS_* variables are one per key, (c) every .hip under csrc/ outside csrc/tune/ is in exactly one SRCS_<key> and every file
+    a SRCS_<key> names exists, (d) `all` builds exactly the records' library files and `clean` removes $(OUTS)"""
     csrc = os.path.join(PKG, "csrc")
-    headers = glob.glob(os.path.join(ROOT, "include", "xai_hip*.h"))
+    headers = glob.glob(os.path.join(ROOT, "include", "*.h"))
     assert sorted(map(os.path.realpath, headers)) == sorted(os.path.realpath(rec.header_path) for rec in L.LIBRARIES.values())
+    assert len(headers) == len(KEYS)
     db = subprocess.run(["make", "-C", csrc, "-pnq"], capture_output=True, text=True).stdout      # the database, nothing is run
     make = dict(re.findall(r"^(LIBS|SRCS_\w+) :?= (.*)$", db, flags=re.M))
     assert make["LIBS"].split() == KEYS and set(make) == {"LIBS"} | {f"SRCS_{key}" for key in KEYS}
     listed = sorted(f for key in KEYS for f in make[f"SRCS_{key}"].split())
-    assert listed == sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*.hip")))
+    found = glob.glob(os.path.join(csrc, "**", "*.hip"), recursive=True)
+    assert listed == sorted(f for f in (os.path.relpath(f, csrc) for f in found) if not f.startswith("tune" + os.sep))
+    assert len(listed) == len(set(listed)) and all(os.path.isfile(os.path.join(csrc, f)) for f in listed)
+    goal = re.search(r"^all:(.*)$", db, flags=re.M).group(1).split()
+    assert len(goal) == len(KEYS)
+    assert sorted(os.path.realpath(os.path.join(csrc, f)) for f in goal) == sorted(os.path.realpath(rec.path) for rec in L.LIBRARIES.values())
+    clean = re.search(r"^clean:\n(?:#.*\n)*((?:\t.*\n)+)", db, flags=re.M).group(1)
+    assert clean == "\trm -rf build $(OUTS)\n" and re.search(r"^OUTS := (.*)$", db, flags=re.M).group(1).split() == goal
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -171,4 +184,5 @@ def test_build_passes_on_the_built_tree_and_imports_the_feature_modules(L, monke
     monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
     g.build()
     assert all(rec.handle is not None for rec in L.LIBRARIES.values())
-    assert all(f"xai_engine.{m}" in sys.modules for m in ("segeval", "lrp", "quickshift", "linkage", "kmeans", "slic", "felzenszwalb"))
+    assert all(f"xai_engine.{m}" in sys.modules for m in ("segeval", "lrp", "quickshift", "linkage", "kmeans", "slic", "felzenszwalb",
+                                                            "eclip", "clip_attn", "surgery"))

@@ -13,7 +13,7 @@ import torch
 
 import clip_attn_restated as A
 import clip_restated as R
-from abi_libs import built, declared, exported
+from abi_libs import built, declared, exported, exported_elsewhere
 from clip_restated import spacing
 from conftest import GOLDEN, ROOT
 
@@ -351,39 +351,15 @@ def test_cli_flag_and_its_default():
 
 
 # ------------------------------------------------------------------------------------------------ the library and its header
-def built_cattn():
-    """the path of libxai_cattn.so, built first where it is absent"""
-    import subprocess
+def test_header_entries_limits_and_argument_types():
+    """what is particular to libxai_cattn.so; what holds for every library alike is tests/test_cpu_abi_libs.py's, for the key cattn"""
     from xai_engine import _lib
-    path = _lib.ATTENTION_LIBRARIES["cattn"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "image-classification-xai_amd", "csrc"), "-j8"], check=True)
-    return path
-
-
-def test_header_library_record_exports_and_versions():
-    from xai_engine import _lib
-    assert list(_lib.ATTENTION_LIBRARIES) == ["cattn"]
-    assert not [t for t in (_lib.LIBRARIES, _lib.DTYPE_LIBRARIES, _lib.CLASSIFIER_LIBRARIES, _lib.SITE_LIBRARIES) if "cattn" in t]
-    rec = _lib.ATTENTION_LIBRARIES["cattn"]
-    assert isinstance(rec, _lib.Library) and os.path.basename(rec.path) == "libxai_cattn.so"
-    assert os.path.samefile(rec.header_path, HEADER) and (rec.version, rec.minor) == (1, 0)
-    assert rec.defines == ("XAI_CATTN_VERSION", "XAI_CATTN_MINOR") and rec.version_entries == ("xai_cattn_version", "xai_cattn_version_minor")
-    # the strict reader takes the header whole, and the record holds what it read
-    assert _lib.parse_header(open(HEADER).read(), rec.defines) == (rec.signatures, rec.restypes, (1, 0))
+    rec = _lib.LIBRARIES["cattn"]
+    assert os.path.samefile(rec.header_path, HEADER)
     names = sorted(ENTRIES + ["xai_cattn_version", "xai_cattn_version_minor"])
-    assert declared(HEADER) == names == exported(built_cattn()) == sorted(rec.signatures)
-    others = [(k, r) for t in (_lib.LIBRARIES, _lib.DTYPE_LIBRARIES, _lib.CLASSIFIER_LIBRARIES, _lib.SITE_LIBRARIES) for k, r in t.items()]
-    assert len(others) == 14
-    for key, orec in others:                                        # my symbols are in no other library, and in no other header
-        if key in _lib.LIBRARIES:
-            built(key)
-        assert not [n for n in exported(orec.path) if n in names or n.startswith("xai_cattn_")], key
-        assert not set(names) & set(orec.signatures), key
-    assert not [n for n in exported(rec.path) if n.startswith("xai_clip_")]
+    assert declared(HEADER) == names == sorted(rec.signatures) and all(rec.restypes[n] is _i for n in ENTRIES)
+    assert not [n for n in exported(built("cattn")) if n.startswith("xai_clip_")]
     lib = _lib.load("cattn")
-    assert lib is rec.handle is _lib.load("cattn")
-    assert (lib.xai_cattn_version(), lib.xai_cattn_version_minor()) == (1, 0)
     assert (lib.xai_cattn_max_tokens(), lib.xai_cattn_max_width(), lib.xai_cattn_max_texts()) == (4096, 8192, 1024)
     game = [_p, _p, _l, _l, _p, _i, _i, _i, _i, _i, _p, _p]
     for sfx in ("f32", "f16"):
@@ -391,35 +367,18 @@ def test_header_library_record_exports_and_versions():
         assert rec.signatures[f"xai_cattn_rollout_row_{sfx}"] == [_p, _i, _i, _i, _i, _p, _p]
         assert rec.signatures[f"xai_cattn_lrp_matrices_{sfx}"] == [_p, _p, _i, _i, _i, _i, _p, _p]
         assert rec.signatures[f"xai_cattn_lrp_row_{sfx}"] == [_p, _i, _i, _i, _p, _p]
-    for name in ENTRIES:
-        assert list(getattr(lib, name).argtypes) == rec.signatures[name] and getattr(lib, name).restype is _i
     make = open(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "Makefile")).read()
-    assert "clip/clip_attn_kernels.hip" in make and re.search(r"^all:.*\$\(CATTN_OUT\)", make, flags=re.M)
-    assert re.search(r"^\trm -rf .*\$\(CATTN_OUT\)", make, flags=re.M)
-    import __graft_entry__ as g
-    assert "ATTENTION_LIBRARIES" in inspect.getsource(g.build)
+    assert "SRCS_cattn := clip/clip_attn_kernels.hip\n" in make
 
 
-def test_loader_refuses_an_older_library(monkeypatch, tmp_path):
-    from xai_engine import _lib
-    rec = _lib.ATTENTION_LIBRARIES["cattn"]
-    real = built_cattn()
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_cattn.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("cattn")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1.*\(include/xai_cattn\.h\)"):
-        _lib.load("cattn")
-    monkeypatch.undo()
-    assert _lib.load("cattn") is rec.handle is not None
+def test_no_other_library_exports_a_cattn_name():
+    assert not [(o, n) for o, n in exported_elsewhere("cattn") if n.startswith("xai_cattn_")]
 
 
 def test_entries_refuse_bad_arguments_before_any_hip_call():
     """the checks come first, so a refused call needs no device: null pointers, extents, strides, limits"""
     from xai_engine import _lib
-    built_cattn()
+    built("cattn")
     lib = _lib.load("cattn")
     NUL, SHAPE, UNSUP = -1, -2, -3
     buf = (C.c_float * 16)()
@@ -458,7 +417,7 @@ def test_entries_refuse_bad_arguments_before_any_hip_call():
 
 def test_wrappers_refuse_what_is_no_device_tensor():
     from xai_engine import kernels as K, _lib
-    built_cattn()
+    built("cattn")
     v, a0, g = torch.zeros(5, 1, 8, dtype=torch.float16), torch.zeros(1, 2, 5, dtype=torch.float16), torch.zeros(1, 1, 8, dtype=torch.float16)
     c = torch.zeros(1, 2, 5, 5)
     with pytest.raises(TypeError, match="a0: expected a torch.Tensor"):

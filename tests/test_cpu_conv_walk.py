@@ -2,8 +2,8 @@
 (tests/conv_walk_main.cpp: it needs nothing of HIP), once plainly and once with -fsanitize=address,undefined -- that stand-alone
 program is the sanitizer run of the planner -- and both are asked the same cases; the expected plans are tests/conv_walk_restated.py's.
 Then the header of the library at 1.0 with the literal argument types of its two entries, and every refusal K78 and K79 make before
-any HIP call.  Its record is the one of _lib.CLASSIFIER_LIBRARIES, beside the tables tests/test_cpu_abi_libs.py and tests/test_cpu_eclip.py hold, so what
-holds for every library alike (the record, the exports, the loader, build()'s version check) is asked of it here."""
+any HIP call.  What holds for every library alike (the record, the exports, the loader, build()'s version check) is
+tests/test_cpu_abi_libs.py's, for the key conv."""
 import ctypes as C
 import itertools
 import os
@@ -13,9 +13,8 @@ import numpy as np
 import pytest
 
 import conv_walk_restated as R
-import re
 
-from abi_libs import built, declared, exported
+from abi_libs import built, declared, exported_elsewhere
 from conftest import PKG, ROOT
 
 HEADER = os.path.join(ROOT, "include", "xai_conv.h")
@@ -28,15 +27,6 @@ SHAPES = ((2048, 19), (2048, 3), (2048, 1), (80, 3), (16, 3), (32, 3), (48, 3), 
 CASES = [(K, S, m, g, o, z) for (K, S) in SHAPES for m, g, o, z in itertools.product((0, 1), (0, 1), (0, 1), (0, 1))]
 REFUSED = [(0, 1, 0, 0, 0, 0), (8, 1, 0, 0, 0, 0), (24, 1, 0, 0, 0, 0), (-16, 1, 0, 0, 0, 0), (2048, 0, 0, 0, 0, 0), (2048, 33, 0, 0, 0, 0),
            (2048, -1, 0, 0, 0, 0), (2048, 3, 2, 0, 0, 0), (2048, 3, -1, 0, 0, 0), (2048, 3, 0, 2, 0, 0), (2048, 3, 0, 0, 2, 0)]
-
-
-def built_conv():
-    """the path of libxai_conv.so, built first where it is absent"""
-    from xai_engine import _lib
-    path = _lib.CLASSIFIER_LIBRARIES["conv"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return path
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
@@ -115,8 +105,7 @@ def test_the_emulation_and_the_bound_on_a_small_sum():
 
 def test_the_header_parses_at_1_0_with_these_argument_types():
     from xai_engine import _lib
-    assert list(_lib.CLASSIFIER_LIBRARIES) == ["conv"] and "conv" not in _lib.LIBRARIES and "conv" not in _lib.DTYPE_LIBRARIES
-    rec = _lib.CLASSIFIER_LIBRARIES["conv"]
+    rec = _lib.LIBRARIES["conv"]
     text = open(HEADER).read()
     args, ret, version = _lib.parse_header(text, rec.defines)
     assert version == (rec.version, rec.minor) == (1, 0)
@@ -133,7 +122,7 @@ def test_the_header_parses_at_1_0_with_these_argument_types():
 
 def test_k78_and_k79_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    built_conv()
+    built("conv")
     lib = _lib.load("conv")
     p = 4096                                              # non-null, aligned, never dereferenced: every call below is refused
     NULL, SHAPE, UNSUPPORTED = -1, -2, -3
@@ -154,40 +143,6 @@ def test_k78_and_k79_check_their_arguments_without_a_gpu():
     assert fast(tile=16) == SHAPE and fast(tile=48) == SHAPE and fast(tile=-1) == SHAPE
 
 
-def test_the_record_the_exports_and_the_loader_of_the_library(monkeypatch, tmp_path):
-    """what tests/test_cpu_abi_libs.py asks of every key of LIBRARIES, of the one record of CLASSIFIER_LIBRARIES"""
-    import __graft_entry__ as g
-    from xai_engine import _lib
-    rec = _lib.CLASSIFIER_LIBRARIES["conv"]
-    assert isinstance(rec, _lib.Library) and os.path.basename(rec.path) == "libxai_conv.so" and os.path.samefile(rec.header_path, HEADER)
-    assert rec.defines == ("XAI_CONV_VERSION", "XAI_CONV_MINOR") and rec.version_entries == ("xai_conv_version", "xai_conv_version_minor")
-    text = open(HEADER).read()
-    assert re.search(r"^#define XAI_CONV_VERSION 1$", text, flags=re.M) and re.search(r"^#define XAI_CONV_MINOR 0$", text, flags=re.M)
-    names = sorted(ENTRIES + list(rec.version_entries))
-    real = built_conv()
-    assert exported(real) == names == sorted(rec.signatures)
-    for other, orec in list(_lib.LIBRARIES.items()) + list(_lib.DTYPE_LIBRARIES.items()):     # my symbols are in no other library or header
-        assert not set(names) & set(orec.signatures), other
-    for other in _lib.LIBRARIES:
-        assert not [n for n in exported(built(other)) if n in names or n.startswith("xai_conv")], other
-    lib = _lib.load("conv")
-    assert lib is rec.handle is _lib.load("conv") and (lib.xai_conv_version(), lib.xai_conv_version_minor()) == (1, 0)
-    for name, types in rec.signatures.items():
-        assert list(getattr(lib, name).argtypes) == types and getattr(lib, name).restype is rec.restypes[name], name
-    # absent, older, and build() checks it too; none of them is cached
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_conv.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("conv")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1.*\(include/xai_conv\.h\)"):
-        _lib.load("conv")
-    for key in _lib.LIBRARIES:
-        built(key)
-    monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
-    with pytest.raises(_lib.XaiHipError, match=r"libxai_conv\.so has ABI 1\.0, this package needs 1\.1"):
-        g.build()
-    assert rec.handle is None
-    monkeypatch.undo()
-    assert _lib.load("conv") is not None
+def test_no_other_library_exports_a_conv_name():
+    """the prefixes of this library's own names; xai_convw_ is the sibling's (tests/test_cpu_conv_wide.py)"""
+    assert not [(o, n) for o, n in exported_elsewhere("conv") if n.startswith(("xai_conv_", "xai_conv1x1_"))]

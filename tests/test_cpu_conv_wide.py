@@ -1,13 +1,12 @@
 """The staggered-start planner of csrc/xai_conv_walk.h and libxai_convw.so without a GPU.  The planner is built alone by the host
 compiler (tests/conv_stagger_main.cpp: it needs nothing of HIP), once plainly and once with -fsanitize=address,undefined -- that
 stand-alone program is the sanitizer run of the planner -- and both are asked the same cases; the expected plans and chains are
-tests/conv_stagger_restated.py's.  Then the header of the library at 1.0 with the literal argument types of its two entries, every
-refusal K80 and K81 make before any HIP call, and what holds for every library alike (the record, the exports, the loader, build()'s
-version check) of the one record of _lib.SITE_LIBRARIES."""
+tests/conv_stagger_restated.py's.  Then the header of the library at 1.0 with the literal argument types of its two entries and every
+refusal K80 and K81 make before any HIP call.  What holds for every library alike (the record, the exports, the loader, build()'s
+version check) is tests/test_cpu_abi_libs.py's, for the key convw."""
 import ctypes as C
 import itertools
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -15,7 +14,7 @@ import pytest
 
 import conv_stagger_restated as S
 
-from abi_libs import built, declared, exported
+from abi_libs import built, declared, exported_elsewhere
 from conftest import PKG, ROOT
 
 HEADER = os.path.join(ROOT, "include", "xai_convw.h")
@@ -31,15 +30,6 @@ CASES = [(512, 64, 32, 0, 32, 256), (1024, 64, 32, 0, 32, 256), (128, 32, 64, 0,
 REFUSED = [(0, 16, 16, 0, 0, 0), (8, 16, 16, 0, 0, 0), (24, 16, 16, 0, 0, 0), (64, 0, 16, 0, 0, 0), (64, 24, 16, 0, 0, 0), (64, 48, 16, 0, 0, 0),
            (64, 128, 16, 0, 0, 0), (64, 16, 0, 0, 0, 0), (64, 16, 8, 0, 0, 0), (64, 16, 24, 0, 0, 0), (64, 16, 16, 2, 0, 0), (64, 16, 16, -1, 0, 0),
            (64, 16, 16, 0, 3, 0), (64, 16, 16, 0, -2, 0), (64, 16, 16, 0, 12, 64), (64, 16, 16, 0, 4, -64)]
-
-
-def built_convw():
-    """the path of libxai_convw.so, built first where it is absent"""
-    from xai_engine import _lib
-    path = _lib.SITE_LIBRARIES["convw"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8"], check=True)
-    return path
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
@@ -107,8 +97,7 @@ def test_the_emulation_and_the_bound_on_a_small_sum():
 
 def test_the_header_parses_at_1_0_with_these_argument_types():
     from xai_engine import _lib
-    assert "convw" in _lib.SITE_LIBRARIES and not any("convw" in t for t in (_lib.LIBRARIES, _lib.DTYPE_LIBRARIES, _lib.CLASSIFIER_LIBRARIES))
-    rec = _lib.SITE_LIBRARIES["convw"]
+    rec = _lib.LIBRARIES["convw"]
     text = open(HEADER).read()
     args, ret, version = _lib.parse_header(text, rec.defines)
     assert version == (rec.version, rec.minor) == (1, 0)
@@ -125,7 +114,7 @@ def test_the_header_parses_at_1_0_with_these_argument_types():
 
 def test_k80_and_k81_check_their_arguments_without_a_gpu():
     from xai_engine import _lib
-    built_convw()
+    built("convw")
     lib = _lib.load("convw")
     p = 4096                                              # non-null, aligned, never dereferenced: every call below is refused
     NULL, SHAPE, UNSUPPORTED = -1, -2, -3
@@ -150,40 +139,5 @@ def test_k80_and_k81_check_their_arguments_without_a_gpu():
     assert call(ENTRIES[1], C=16 * 65535 + 1, HW=16) == UNSUPPORTED
 
 
-def test_the_record_the_exports_and_the_loader_of_the_library(monkeypatch, tmp_path):
-    """what tests/test_cpu_abi_libs.py asks of every key of LIBRARIES, of the one record of SITE_LIBRARIES"""
-    import __graft_entry__ as g
-    from xai_engine import _lib
-    rec = _lib.SITE_LIBRARIES["convw"]
-    assert isinstance(rec, _lib.Library) and os.path.basename(rec.path) == "libxai_convw.so" and os.path.samefile(rec.header_path, HEADER)
-    assert rec.defines == ("XAI_CONVW_VERSION", "XAI_CONVW_MINOR") and rec.version_entries == ("xai_convw_version", "xai_convw_version_minor")
-    text = open(HEADER).read()
-    assert re.search(r"^#define XAI_CONVW_VERSION 1$", text, flags=re.M) and re.search(r"^#define XAI_CONVW_MINOR 0$", text, flags=re.M)
-    names = sorted(ENTRIES + list(rec.version_entries))
-    real = built_convw()
-    assert exported(real) == names == sorted(rec.signatures)
-    others = list(_lib.LIBRARIES.items()) + list(_lib.DTYPE_LIBRARIES.items()) + list(_lib.CLASSIFIER_LIBRARIES.items())
-    for other, orec in others:                            # my symbols are in no other library or header
-        assert not set(names) & set(orec.signatures), other
-        assert not [n for n in exported(orec.path) if n in names or n.startswith("xai_convw")], other
-    lib = _lib.load("convw")
-    assert lib is rec.handle is _lib.load("convw") and (lib.xai_convw_version(), lib.xai_convw_version_minor()) == (1, 0)
-    for name, types in rec.signatures.items():
-        assert list(getattr(lib, name).argtypes) == types and getattr(lib, name).restype is rec.restypes[name], name
-    # absent, older, and build() checks it too; none of them is cached
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_convw.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("convw")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1.*\(include/xai_convw\.h\)"):
-        _lib.load("convw")
-    for key in _lib.LIBRARIES:
-        built(key)
-    monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
-    with pytest.raises(_lib.XaiHipError, match=r"libxai_convw\.so has ABI 1\.0, this package needs 1\.1"):
-        g.build()
-    assert rec.handle is None
-    monkeypatch.undo()
-    assert _lib.load("convw") is not None
+def test_no_other_library_exports_a_convw_name():
+    assert not [(o, n) for o, n in exported_elsewhere("convw") if n.startswith("xai_convw")]

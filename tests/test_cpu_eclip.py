@@ -6,14 +6,13 @@ import ctypes as C
 import inspect
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import clip_restated as R
-from abi_libs import built, declared, exported
+from abi_libs import built, declared, exported_elsewhere
 from conftest import GOLDEN, ROOT
 
 CLIP_HEADER = os.path.join(ROOT, "include", "xai_clip.h")
@@ -266,36 +265,17 @@ def test_clip_cli_is_a_module_of_its_own_and_the_three_older_clis_still_refuse_c
 
 
 # ------------------------------------------------------------------------------------------------ the library and its header
-def built_clip():
-    """the path of libxai_clip.so, built first where it is absent"""
-    import subprocess
+def test_clip_header_entries_limits_and_argument_types():
+    """what is particular to libxai_clip.so (entries in _f32 and _f16; header include/xai_clip.h, source csrc/clip/clip_kernels.hip);
+    what holds for every library alike is tests/test_cpu_abi_libs.py's, for the key clip"""
     from xai_engine import _lib
-    path = _lib.DTYPE_LIBRARIES["clip"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "image-classification-xai_amd", "csrc"), "-j8"], check=True)
-    return path
-
-
-def test_clip_header_library_record_and_the_pin_at_1_0():
-    """libxai_clip.so is the one record of _lib.DTYPE_LIBRARIES (entries in _f32 and _f16), beside the eleven of LIBRARIES: header
-    include/xai_clip.h, source csrc/clip/clip_kernels.hip, built by csrc/Makefile's `all`, loaded by _lib.load("clip") and
-    version-checked by build()"""
-    from xai_engine import _lib
-    assert list(_lib.DTYPE_LIBRARIES) == ["clip"] and "clip" not in _lib.LIBRARIES and "_f16" in _lib._LAUNCH
-    rec = _lib.DTYPE_LIBRARIES["clip"]
-    assert isinstance(rec, _lib.Library) and os.path.basename(rec.path) == "libxai_clip.so"
-    assert os.path.samefile(rec.header_path, CLIP_HEADER) and (rec.version, rec.minor) == (1, 0)
-    assert rec.defines == ("XAI_CLIP_VERSION", "XAI_CLIP_MINOR") and rec.version_entries == ("xai_clip_version", "xai_clip_version_minor")
-    text = open(CLIP_HEADER).read()
-    assert re.search(r"^#define XAI_CLIP_VERSION 1$", text, flags=re.M) and re.search(r"^#define XAI_CLIP_MINOR 0$", text, flags=re.M)
+    assert "_f16" in _lib._LAUNCH
+    rec = _lib.LIBRARIES["clip"]
+    assert os.path.samefile(rec.header_path, CLIP_HEADER)
     names = sorted(ENTRIES + ["xai_clip_version", "xai_clip_version_minor"])
-    assert declared(CLIP_HEADER) == names == exported(built_clip()) == sorted(rec.signatures)
-    for other, orec in _lib.LIBRARIES.items():                    # my symbols are in no other library, and in no other header
-        assert not [n for n in exported(built(other)) if n in names or n.startswith("xai_clip_")], other
-        assert not set(names) & set(orec.signatures), other
+    assert declared(CLIP_HEADER) == names == sorted(rec.signatures) and all(rec.restypes[n] is _i for n in ENTRIES)
+    built("clip")
     lib = _lib.load("clip")
-    assert lib is rec.handle is _lib.load("clip")
-    assert (lib.xai_clip_version(), lib.xai_clip_version_minor()) == (1, 0)
     assert (lib.xai_clip_max_tokens(), lib.xai_clip_max_width(), lib.xai_clip_max_texts()) == (4096, 8192, 1024)
     assert 4 * (4096 + 8192) <= 48 * 1024                      # the LDS budget the header states
     att = [_p, _p, _l, _l, _p, _l, _l, _i, _i, _i, _f, _p, _p, _p, _p]
@@ -305,40 +285,12 @@ def test_clip_header_library_record_and_the_pin_at_1_0():
         assert rec.signatures[f"xai_clip_cls_attention_{sfx}"] == att
         assert rec.signatures[f"xai_clip_eclip_map_{sfx}"] == ecl
         assert rec.signatures[f"xai_clip_maskclip_map_{sfx}"] == msk
-        for name in (f"xai_clip_cls_attention_{sfx}", f"xai_clip_eclip_map_{sfx}", f"xai_clip_maskclip_map_{sfx}"):
-            assert list(getattr(lib, name).argtypes) == rec.signatures[name] and getattr(lib, name).restype is _i
     make = open(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "Makefile")).read()
-    assert "clip/clip_kernels.hip" in make and os.path.exists(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "clip", "clip_kernels.hip"))
-    with pytest.raises(KeyError):
-        _lib.load("clip2")
+    assert "SRCS_clip := clip/clip_kernels.hip\n" in make
 
 
-def test_loader_and_build_refuse_an_older_or_stale_clip_library(monkeypatch, tmp_path):
-    import __graft_entry__ as g
-    from xai_engine import _lib
-    rec = _lib.DTYPE_LIBRARIES["clip"]
-    real = built_clip()
-    for key in _lib.LIBRARIES:
-        built(key)
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_clip.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("clip")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)                          # the package wants a later minor than the library has
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1.*\(include/xai_clip\.h\)"):
-        _lib.load("clip")
-    monkeypatch.setattr(g.subprocess, "run", lambda cmd, **kw: None)
-    with pytest.raises(_lib.XaiHipError, match=r"libxai_clip\.so has ABI 1\.0, this package needs 1\.1"):
-        g.build()                                                 # build() checks this library too
-    assert rec.handle is None
-    monkeypatch.setattr(rec, "minor", 0)
-    monkeypatch.setitem(rec.signatures, "xai_clip_not_in_the_library_f16", [_p])
-    monkeypatch.setitem(rec.restypes, "xai_clip_not_in_the_library_f16", _i)
-    with pytest.raises(AttributeError):
-        _lib.load("clip")
-    monkeypatch.undo()
-    assert _lib.load("clip") is rec.handle is not None
+def test_no_other_library_exports_a_clip_name():
+    assert not [(o, n) for o, n in exported_elsewhere("clip") if n.startswith("xai_clip_")]
 
 
 def test_entries_refuse_bad_arguments_before_any_hip_call():

@@ -13,7 +13,7 @@ import torch
 
 import clip_restated as R
 import surgery_restated as S
-from abi_libs import built, declared, exported
+from abi_libs import built, declared, exported, exported_elsewhere
 from conftest import GOLDEN, ROOT
 
 HEADER = os.path.join(ROOT, "include", "xai_csurg.h")
@@ -294,81 +294,40 @@ def test_cli_flags_and_their_defaults():
 
 
 # ------------------------------------------------------------------------------------------------ the library and its header
-def built_csurg():
-    """the path of libxai_csurg.so, built first where it is absent"""
-    import subprocess
+def test_header_entries_limits_and_argument_types():
+    """what is particular to libxai_csurg.so; what holds for every library alike is tests/test_cpu_abi_libs.py's, for the key csurg"""
     from xai_engine import _lib
-    path = _lib.SURGERY_LIBRARIES["csurg"].path
-    if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "image-classification-xai_amd", "csrc"), "-j8"], check=True)
-    return path
-
-
-def test_header_library_record_exports_and_versions():
-    from xai_engine import _lib
-    assert list(_lib.SURGERY_LIBRARIES) == ["csurg"] and any(t is _lib.SURGERY_LIBRARIES for t in _lib.ALL_TABLES)
-    earlier = (_lib.LIBRARIES, _lib.DTYPE_LIBRARIES, _lib.CLASSIFIER_LIBRARIES, _lib.SITE_LIBRARIES, _lib.ATTENTION_LIBRARIES)
-    assert not [t for t in earlier if "csurg" in t]
-    rec = _lib.SURGERY_LIBRARIES["csurg"]
-    assert isinstance(rec, _lib.Library) and os.path.basename(rec.path) == "libxai_csurg.so"
-    assert os.path.samefile(rec.header_path, HEADER) and (rec.version, rec.minor) == (1, 0)
-    assert rec.defines == ("XAI_CSURG_VERSION", "XAI_CSURG_MINOR") and rec.version_entries == ("xai_csurg_version", "xai_csurg_version_minor")
-    # the strict reader takes the header whole, and the record holds what it read
-    assert _lib.parse_header(open(HEADER).read(), rec.defines) == (rec.signatures, rec.restypes, (1, 0))
+    rec = _lib.LIBRARIES["csurg"]
+    assert os.path.samefile(rec.header_path, HEADER)
     names = sorted(ENTRIES + ["xai_csurg_version", "xai_csurg_version_minor"])
-    assert declared(HEADER) == names == exported(built_csurg()) == sorted(rec.signatures)
+    assert declared(HEADER) == names == sorted(rec.signatures) and all(rec.restypes[n] is _i for n in ENTRIES)
     assert not [n for n in names if n.endswith(("_f16", "_f64"))]              # fp32 is the reference's dtype for this row
-    others = [(k, r) for t in earlier for k, r in t.items()]
-    assert len(others) == 15
-    for key, orec in others:                                        # my symbols are in no other library, and in no other header
-        if key in _lib.LIBRARIES:
-            built(key)
-        assert not [n for n in exported(orec.path) if n in names or n.startswith("xai_csurg_")], key
-        assert not set(names) & set(orec.signatures), key
-    assert not [n for n in exported(rec.path) if n.startswith(("xai_clip_", "xai_cattn_"))]
+    assert not [n for n in exported(built("csurg")) if n.startswith(("xai_clip_", "xai_cattn_"))]
     lib = _lib.load("csurg")
-    assert lib is rec.handle is _lib.load("csurg")
-    assert (lib.xai_csurg_version(), lib.xai_csurg_version_minor()) == (1, 0)
     assert (lib.xai_csurg_max_tokens(), lib.xai_csurg_max_width(), lib.xai_csurg_max_texts()) == (4096, 8192, 1024)
     assert (lib.xai_csurg_lds_floats(), lib.xai_csurg_vv_waves()) == (16384, 4)
     assert rec.signatures["xai_csurg_vv_attention_f32"] == [_p, _l, _l, _l, _i, _i, _i, _i, _i, _f, _p, _p, _p]
     assert rec.signatures["xai_csurg_similarity_map_f32"] == [_p, _p, _l, _i, _i, _i, _i, _i, _p, _p, _p]
-    for name in ENTRIES:
-        assert list(getattr(lib, name).argtypes) == rec.signatures[name] and getattr(lib, name).restype is _i
     text = open(HEADER).read()
     for word in ("THE ARITHMETIC RULE", "THE LIMITS", "THE BOUND AFTER THE FIRST EXP", "THE BOUND OF K87's w", "in ascending c from +0",
                  "in ascending j from +0", "XAI_CSURG_LDS_FLOATS", "L <= 237 at d = 64"):
         assert word in text, word
     make = open(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "Makefile")).read()
-    assert "clip/clip_surgery_kernels.hip" in make and re.search(r"^all:.*\$\(CSURG_OUT\)", make, flags=re.M)
-    assert re.search(r"^\trm -rf .*\$\(CSURG_OUT\)", make, flags=re.M) and "-ffp-contract=off" in make
+    assert "SRCS_csurg := clip/clip_surgery_kernels.hip\n" in make and "-ffp-contract=off" in make
     import __graft_entry__ as g
-    src = inspect.getsource(g.build)
-    assert "SURGERY_LIBRARIES" in src and "ATTENTION_LIBRARIES" in src and re.search(r"import .*\bsurgery\b", src)
+    assert re.search(r"import .*\bsurgery\b", inspect.getsource(g.build))
     kernel = open(os.path.join(ROOT, "image-classification-xai_amd", "csrc", "clip", "clip_surgery_kernels.hip")).read()
     assert not re.search(r"atomic|hipMalloc|hipMemset|__builtin_amdgcn_mfma", kernel)
 
 
-def test_loader_refuses_an_older_library(monkeypatch, tmp_path):
-    from xai_engine import _lib
-    rec = _lib.SURGERY_LIBRARIES["csurg"]
-    real = built_csurg()
-    monkeypatch.setattr(rec, "handle", None)
-    monkeypatch.setattr(rec, "path", str(tmp_path / "libxai_csurg.so"))
-    with pytest.raises(_lib.XaiHipError, match="not found"):
-        _lib.load("csurg")
-    monkeypatch.setattr(rec, "path", real)
-    monkeypatch.setattr(rec, "minor", 1)
-    with pytest.raises(_lib.XaiHipError, match=r"has ABI 1\.0, this package needs 1\.1.*\(include/xai_csurg\.h\)"):
-        _lib.load("csurg")
-    monkeypatch.undo()
-    assert _lib.load("csurg") is rec.handle is not None
+def test_no_other_library_exports_a_csurg_name():
+    assert not [(o, n) for o, n in exported_elsewhere("csurg") if n.startswith("xai_csurg_")]
 
 
 def test_entries_refuse_bad_arguments_before_any_hip_call():
     """the checks come first, so a refused call needs no device: null pointers, extents, strides, limits"""
     from xai_engine import _lib
-    built_csurg()
+    built("csurg")
     lib = _lib.load("csurg")
     NUL, SHAPE, UNSUP = -1, -2, -3
     buf = (C.c_float * 16)()
@@ -401,7 +360,7 @@ def test_entries_refuse_bad_arguments_before_any_hip_call():
 
 def test_wrappers_refuse_what_is_no_device_tensor():
     from xai_engine import kernels as K, _lib
-    built_csurg()
+    built("csurg")
     v, f, t = torch.zeros(6, 5, 1, 8), torch.zeros(1, 5, 16), torch.zeros(3, 16)
     with pytest.raises(TypeError, match="v: expected a torch.Tensor"):
         K.clip_vv_attention(None, 2)

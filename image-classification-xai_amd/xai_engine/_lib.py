@@ -5,7 +5,7 @@ entry points go into a library of their own.
 
 The rule.  A new library is: its header under include/; one record in LIBRARIES; the same key in csrc/Makefile's LIBS with a
 SRCS_<key> line, plus a header override there and a `header=` here if its header is not xai_hip_<key>.h; and its literal version pair
-in tests/abi_libs.py's PINNED.  A feature's own test file holds only what is particular to its entries; it never asserts a complete
+in tests/abi_libs.py's PINNED (cm2ib's is registered there by tests/test_cpu_m2ib.py at import).  A feature's own test file holds only what is particular to its entries; it never asserts a complete
 list of keys or the absence of its key from somewhere.  The completeness checks live in tests/test_cpu_abi_libs.py and read the tree.
 
 Each header is the one description of its ABI: the argument types, the return types and the two version numbers are read from
@@ -140,7 +140,7 @@ LIBRARIES = {rec.key: rec for rec in (
     Library("hip"), Library("ext"), Library("ext2"), Library("ext3"), Library("ext4"), Library("ext5"), Library("ext6"), Library("ext7"),
     Library("compact"), Library("slic"), Library("felz"),
     Library("clip", header="xai_clip.h"), Library("conv", header="xai_conv.h"), Library("convw", header="xai_convw.h"),
-    Library("cattn", header="xai_cattn.h"), Library("csurg", header="xai_csurg.h"))}
+    Library("cattn", header="xai_cattn.h"), Library("csurg", header="xai_csurg.h"), Library("cm2ib"))}
 # the main library's fields under the names they have always had, for readers: aliases read at import, the record is the state
 _HIP = LIBRARIES["hip"]
 LIB_PATH, HEADER_PATH, SIGNATURES, ABI_VERSION, ABI_MINOR = _HIP.path, _HIP.header_path, _HIP.signatures, _HIP.version, _HIP.minor

@@ -14,8 +14,10 @@ reference runs them on; `--clip_attention_rows plain` serves them in closed form
 is exact because that second model has plain CLIP's weights and forward and the rows read only its attention probabilities and their
 gradients.  surgery is refused by default too, naming the third model object; `--clip_surgery plain` serves it in closed form on the
 plain model in fp32 (xai_engine/surgery.py), with `--surgery_text_features`, a (T - 1, E) tensor of the context classes' text
-features (the reference's 59 prompt-ensembled class names; without it seeded and random, like `--text_embeddings`).  m2ib needs
-another model and raises NotImplementedError naming it.
+features (the reference's 59 prompt-ensembled class names; without it seeded and random, like `--text_embeddings`).  m2ib is refused
+by default as well, naming the fourth model object; `--clip_m2ib plain` serves it in closed form on the plain model in the model's
+dtype (xai_engine/m2ib.py), with `--m2ib_text_features`, the (classes, E) table of the M2IB wrapper's text features
+(m2ib.wrapper_text_features; without it seeded and random), and `--m2ib_noise device|host`.
 """
 import torch
 
@@ -46,6 +48,14 @@ def build_parser():
     p.add_argument("--surgery_text_features", type=str, default=None,
                    help="a (T - 1, E) tensor saved with torch.save, the text features of surgery's context classes; default: 59 seeded "
                    "random rows")
+    p.add_argument("--clip_m2ib", choices=("modified", "plain"), default="modified",
+                   help="m2ib: 'modified' refuses it (the reference runs it on a fourth model object, the M2IB wrapper); 'plain' "
+                   "computes it in closed form on the plain model, in the model's dtype")
+    p.add_argument("--m2ib_text_features", type=str, default=None,
+                   help="a (classes, E) tensor saved with torch.save, the M2IB wrapper's text feature of each class "
+                   "(m2ib.wrapper_text_features); default: seeded random rows")
+    p.add_argument("--m2ib_noise", choices=("device", "host"), default="device",
+                   help="m2ib: where the bottleneck's noise is drawn; 'host' draws from torch's CPU generator in the reference's order")
     return p
 
 
@@ -82,13 +92,21 @@ def main(argv=None):
         context = torch.randn(59, embed, generator=torch.Generator().manual_seed(1))
     if not torch.is_tensor(context) or context.dim() != 2 or context.shape[1] != embed:
         raise SystemExit(f"--surgery_text_features must hold a (T - 1, {embed}) tensor")
+    if args.m2ib_text_features:
+        m2ib_table = torch.load(args.m2ib_text_features, map_location="cpu", weights_only=True)
+    else:
+        m2ib_table = torch.randn(emb.shape[0], embed, generator=torch.Generator().manual_seed(2))
+    if not torch.is_tensor(m2ib_table) or m2ib_table.dim() != 2 or m2ib_table.shape[1] != embed:
+        raise SystemExit(f"--m2ib_text_features must hold a (classes, {embed}) tensor")
     testing_dict = {"models": [model], "imagenet_dataset": args.dataset_path, "normalize": norm, "img_hw": 224,
                     "batch_size": args.batch_size or batch_size, "attr_func": args.attr_func, "model_name": args.model,
                     "image_count": args.image_count, "device": str(device), "class_map_path": args.class_map,
                     "weights_path": args.weights or "", "num_patches": num_patches,
                     "embeddings": emb.to(device=device, dtype=model.dtype), "num_classes": emb.shape[0],
                     "clip_attention_rows": args.clip_attention_rows, "clip_surgery": args.clip_surgery,
-                    "surgery_text_features": context.to(device=device, dtype=torch.float32)}
+                    "surgery_text_features": context.to(device=device, dtype=torch.float32),
+                    "clip_m2ib": args.clip_m2ib, "m2ib_text_features": m2ib_table.to(device=device, dtype=model.dtype),
+                    "m2ib_noise": args.m2ib_noise}
     total, used, _ = harness.evaluate_perturbation(testing_dict, rank=rank, world=world, out_dir=args.out_dir,
                                                      reference_counter=args.reference_counter)
     if rank == 0:

@@ -2322,3 +2322,84 @@ def clip_surgery_similarity(features, txt, texts_out=1, want_weights=False):
     _call("xai_csurg_similarity_map_f32", features.device, _ptr(features), _ptr(txt), T * E if txt.dim() == 3 else 0, B, L, E, T, T_out,
           _ptr(w), _ptr(out), lib="csurg")
     return (out, w) if want_weights else out
+
+
+# ------------------------------------------------------------------------------ CLIP M2IB (K88-K90, include/xai_hip_cm2ib.h)
+def cm2ib_limits():
+    """(XAI_CM2IB_MAX_TOKENS, XAI_CM2IB_MAX_WIDTH, XAI_CM2IB_MAX_COPIES) of the built library"""
+    lib = _lib.load("cm2ib")
+    return lib.xai_cm2ib_max_tokens(), lib.xai_cm2ib_max_width(), lib.xai_cm2ib_max_copies()
+
+
+def _m2ib_operands(alpha, x9, eps, least_tokens=1, more=()):
+    """The checks K88-K90 share, the device last: alpha (B, L, D) fp32, x9 of its shape in fp32 or fp16, eps (None: absent)
+    (B, R, L, D) fp32, and `more`: (tensor, name, dtype, the tensor whose shape it must have, the words for that) -> (B, R, L, D),
+    R = 1 without eps"""
+    _typed(alpha, F32, "alpha")
+    if alpha.dim() != 3 or alpha.numel() == 0:
+        raise ValueError(f"alpha must be (B, L, D), got {tuple(alpha.shape)}")
+    B, L, D = alpha.shape
+    if L < least_tokens:
+        raise ValueError(f"alpha: L = {L}; the class token and at least one patch are needed (L >= {least_tokens})")
+    _typed(x9, (F32, F16), "x9")
+    if x9.shape != alpha.shape:
+        raise ValueError(f"x9 must be ({B}, {L}, {D}) like alpha, got {tuple(x9.shape)}")
+    R = 1
+    if eps is not None:
+        _typed(eps, F32, "eps")
+        if eps.dim() != 4 or eps.numel() == 0 or (eps.shape[0], *eps.shape[2:]) != (B, L, D):
+            raise ValueError(f"eps must be ({B}, R, {L}, {D}), got {tuple(eps.shape)}")
+        R = int(eps.shape[1])
+    for t, name, dtype, like, wrong in more:
+        _typed(t, dtype, name)
+        if t.shape != like.shape:
+            raise ValueError(f"{name} must {wrong}, got {tuple(t.shape)}")
+    max_l, max_d, max_r = cm2ib_limits()
+    if L > max_l or D > max_d or R > max_r or B > 65535:
+        raise ValueError(f"B = {B}, R = {R}, L = {L}, D = {D} are over the limits of K88-K90 (B <= 65535, R <= {max_r}, L <= {max_l}, "
+                         f"D <= {max_d})")
+    for t, name in ((alpha, "alpha"), (x9, "x9"), (eps, "eps")) + tuple(m[:2] for m in more):
+        if t is not None:
+            _need(t, t.dtype, name)
+            if t.device != alpha.device:
+                raise ValueError(f"{name} must be on {alpha.device}, got {t.device}")
+    return B, R, L, D
+
+
+def m2ib_sample(alpha, x9, eps):
+    """K88: alpha (B, L, D) fp32, x9 (B, L, D) in the model's dtype T (fp32 or fp16), eps (B, R, L, D) fp32 -> t (B, R, L, D) of T:
+    the sample of M2IB's information bottleneck, sigmoid(alpha) * x9 + (1 - sigmoid(alpha)) * eps in the reference's sequence
+    (iba.py:104-108, :122-127), rounded to T once."""
+    if eps is None:
+        raise TypeError("eps: expected a torch.Tensor, got NoneType")
+    B, R, L, D = _m2ib_operands(alpha, x9, eps)
+    t = torch.empty((B, R, L, D), dtype=x9.dtype, device=alpha.device)
+    _call(f"xai_cm2ib_sample_{_suffix(x9)}", alpha.device, _ptr(alpha), _ptr(x9), _ptr(eps), B, R, L, D, _ptr(t), lib="cm2ib")
+    return t
+
+
+def m2ib_adam_step(gt, eps, x9, alpha, m, v, beta, w1, b2, w2, bc2s, step_size, adam_eps):
+    """K89, in place: gt (B, R, L, D) of x9's dtype, dL/dt of the R copies; eps (B, R, L, D) fp32, the noise K88 was given; x9, alpha as
+    for K88; m, v (B, L, D) fp32, Adam's moments.  Forms the gradient autograd gives the reference's alpha (the fitting part from gt,
+    the compression part beta / (L * D) * d capacity / d alpha) and takes one step of torch's single-tensor Adam with the host-made
+    scalars of the step (m2ib.adam_scalars) -> alpha"""
+    if eps is None:
+        raise TypeError("eps: expected a torch.Tensor, got NoneType")
+    _typed(x9, (F32, F16), "x9")
+    B, R, L, D = _m2ib_operands(alpha, x9, eps, more=((gt, "gt", x9.dtype, eps, "have the shape of eps"),
+                                                      (m, "m", F32, alpha, "have the shape of alpha"),
+                                                      (v, "v", F32, alpha, "have the shape of alpha")))
+    _call(f"xai_cm2ib_adam_step_{_suffix(x9)}", alpha.device, _ptr(gt), _ptr(eps), _ptr(x9), B, R, L, D, float(beta), float(w1), float(b2),
+          float(w2), float(bc2s), float(step_size), float(adam_eps), _ptr(alpha), _ptr(m), _ptr(v), lib="cm2ib")
+    return alpha
+
+
+def m2ib_saliency(alpha, x9, want_capacity=False):
+    """K90: alpha, x9 (B, L, D) fp32 -> (B, L - 1) fp32, per patch token the nansum over D of the bottleneck's capacity
+    -0.5 * (1 + log(var) - mu ** 2 - var) (iba.py:111-114, :154).  want_capacity: a second result, the (B, L, D) capacities."""
+    _typed(x9, F32, "x9")
+    B, _, L, D = _m2ib_operands(alpha, x9, None, least_tokens=2)
+    out = torch.empty((B, L - 1), dtype=F32, device=alpha.device)
+    cap = torch.empty((B, L, D), dtype=F32, device=alpha.device) if want_capacity else None
+    _call("xai_cm2ib_saliency_f32", alpha.device, _ptr(alpha), _ptr(x9), B, L, D, _ptr(cap), _ptr(out), lib="cm2ib")
+    return (out, cap) if want_capacity else out

@@ -305,7 +305,13 @@ def get_CLIP_attr(trans_img, target_class, testing_dict):
     every other row; the remaining texts are testing_dict["surgery_text_features"], a (T - 1, E) tensor (the 59 context classes of
     evaluatePerturbation.py:427 in the reference's harness), normalised here; "plain" without that table, or any value of
     `clip_surgery` other than None, "modified" and "plain": ValueError.  The reference also prompt-ensembles the caption over its 85
-    templates (encode_text_with_prompt_ensemble): a caller who wants that passes an `embeddings` table made that way."""
+    templates (encode_text_with_prompt_ensemble): a caller who wants that passes an `embeddings` table made that way.
+    m2ib is served on request too, testing_dict["clip_m2ib"] == "plain" (xai_engine/m2ib.py: the reference's fourth model object is
+    a deep copy of plain CLIP; its ten Adam steps run in closed form behind block 9).  Its text features are NOT a row of
+    `embeddings`: the wrapper's text tower drops the causal mask, reads the last position and projects twice, so the caller passes
+    testing_dict["m2ib_text_features"], the (n_classes, E) table of m2ib.wrapper_text_features; "plain" without that table, or any
+    value of `clip_m2ib` other than None, "modified" and "plain": ValueError.  Optional: testing_dict["m2ib_noise"] ("device", the
+    default, "host" or a tensor) and testing_dict["m2ib_seed"], as m2ib_batch takes them."""
     from . import eclip
     attr_function = testing_dict["attr_func"]
     rows = testing_dict.get("clip_attention_rows")
@@ -347,6 +353,28 @@ def get_CLIP_attr(trans_img, target_class, testing_dict):
         txt = torch.nn.functional.normalize(torch.cat([emb[int(target_class)][None].float(), context.to(emb.device).float()]), dim=-1)
         x = clip_keepsize_input(trans_img, (1, 1))
         sal = surgery.surgery_batch(clipmodel, x, txt, img_hw=testing_dict["img_hw"])[0]
+        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
+    m2ib_rows = testing_dict.get("clip_m2ib")
+    if m2ib_rows not in (None, "modified", "plain"):
+        raise ValueError(f"get_CLIP_attr: clip_m2ib must be 'plain' or 'modified' (the default), got {m2ib_rows!r}")
+    if m2ib_rows == "plain" and attr_function == "m2ib":
+        from . import m2ib
+        table = testing_dict.get("m2ib_text_features")
+        if table is None:
+            raise ValueError("get_CLIP_attr: clip_m2ib='plain' needs testing_dict['m2ib_text_features'], the (n_classes, E) table of "
+                             "the M2IB wrapper's text features (m2ib.wrapper_text_features of each class's token ids; they are not "
+                             "encode_text's, so `embeddings` does not serve)")
+        clipmodel = testing_dict["models"][0]
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != clipmodel.visual.proj.shape[1]:
+            raise ValueError(f"get_CLIP_attr: m2ib_text_features must be a (n_classes, {clipmodel.visual.proj.shape[1]}) tensor")
+        res = int(clipmodel.visual.input_resolution)
+        if tuple(trans_img.shape[1:]) != (res, res):
+            raise NotImplementedError(f"get_CLIP_attr: the row 'm2ib' takes the reference's preprocess(img); a "
+                                      f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
+                                      "bicubic resize is not restated here")
+        x = clip_keepsize_input(trans_img, (1, 1))
+        sal = m2ib.m2ib_batch(clipmodel, x, table[int(target_class)], img_hw=testing_dict["img_hw"],
+                              noise=testing_dict.get("m2ib_noise", "device"), seed=testing_dict.get("m2ib_seed"))[0]
         return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
     if attr_function in eclip.REFUSED:
         raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} needs {eclip.REFUSED[attr_function]}, which this engine "

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""CLIP's M2IB row (xai_engine/m2ib.py, K88-K90) at ViT-B/16 and ViT-B/32 shapes; one model and dtype per run, appended to
+profiles/m2ib_bench.txt, so that every step has a time limit of its own:
+
+    for m in b16 b32; do for d in fp16 fp32; do
+        timeout -k 10 300 python profiles/bench_m2ib.py --model $m --dtype $d --out profiles/m2ib_bench.txt || break 2
+    done; done
+
+Random weights, OpenAI's mixed fp16 or fp32, 224 x 224, the reference's ten steps on ten copies.
+Every figure is taken by device events around a window of calls after a warm-up: the median of 7 windows, with their min and max.
+row      ms per image of `m2ib_batch(..., img_hw=224)` at B = 1 and B = 32 (device noise), and of the reference's flow written as torch
+         operators on the device in this process (iba.py:89-194, clip_wrapper.py): all twelve blocks on the ten copies and the text
+         tower in each of its ten steps, autograd back to alpha, torch.optim.Adam; one image per call as the reference's harness runs it.
+kernels  K88, K89 and K90 alone on the operands of that pass, us per launch, against their torch expressions (K89: autograd through
+         the bottleneck's expressions from a given dL/dt plus torch.optim.Adam's step).
+Nothing is gated on these numbers, and no ratio is promised.  A run without a GPU fails."""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "image-classification-xai_amd"))
+sys.path.insert(0, ROOT)
+
+DEV = "cuda:0"
+WINDOWS = 7
+LAYER, STEPS, COPIES, BETA = 9, 10, 10, 0.1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "m2ib_bench.txt"))
+    ap.add_argument("--model", choices=("b16", "b32"), default="b16")
+    ap.add_argument("--dtype", choices=("fp16", "fp32"), default="fp16")
+    ap.add_argument("--calls", type=int, default=2, help="calls of the row per window")
+    ap.add_argument("--launches", type=int, default=100, help="launches of a kernel per window")
+    args = ap.parse_args()
+    import torch
+    import torch.nn.functional as F
+    from xai_engine import clip_attn, m2ib, zoo
+    from xai_engine import kernels as K
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_m2ib: no GPU")
+
+    def windows(fn, calls, unit):
+        """(median, min, max) over WINDOWS windows of `calls` calls between two device events, in ms * unit per call"""
+        fn()
+        ts = []
+        for _ in range(WINDOWS):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(calls):
+                fn()
+            stop.record()
+            torch.cuda.synchronize()
+            ts.append(start.elapsed_time(stop) * unit / calls)
+        return statistics.median(ts), min(ts), max(ts)
+
+    def bottleneck(alpha, xb, eps):
+        lamb = torch.sigmoid(alpha)                  # broadcast over the copies, where the reference expands
+        mu, var = xb * lamb, (1 - lamb) ** 2
+        return mu + var.sqrt() * eps, -0.5 * (1 + torch.log(var) - mu ** 2 - var)
+
+    def torch_row(model, x, ids):
+        """the reference's flow for one image as torch operators -> (224, 224)"""
+        visual, dtype = model.visual, model.dtype
+        blocks = list(visual.transformer.resblocks)
+        alpha = torch.nn.Parameter(torch.full((1, (224 // visual.conv1.kernel_size[0]) ** 2 + 1, visual.transformer.width), 5.0, device=DEV))
+        opt = torch.optim.Adam(lr=1, params=[alpha])
+        cap = None
+        for _ in range(STEPS):
+            opt.zero_grad()
+            txt = m2ib.wrapper_text_features(model, ids.expand(COPIES, -1))
+            tok = clip_attn._native_tokens(visual, x.expand(COPIES, -1, -1, -1))
+            for blk in blocks[:LAYER + 1]:
+                tok = blk(tok)
+            t, cap = bottleneck(alpha, tok.permute(1, 0, 2), torch.randn((COPIES,) + tuple(alpha.shape[1:]), device=DEV))
+            tok = t.to(dtype).permute(1, 0, 2)
+            for blk in blocks[LAYER + 1:]:
+                tok = blk(tok)
+            feats = visual.ln_post(tok.permute(1, 0, 2)[:, 0, :]).to(dtype) @ visual.proj
+            loss = BETA * cap.mean() - F.cosine_similarity(txt, feats, eps=1e-6).mean()
+            loss.backward()
+            opt.step()
+        sal = torch.nansum(cap.detach().mean(axis=0), -1)[1:]
+        side = int(sal.numel() ** 0.5)
+        sal = F.interpolate(sal.reshape(1, 1, side, side), size=224, mode="bilinear")[0, 0]
+        return (sal - sal.min()) / (sal.max() - sal.min())
+
+    name, ctor = {"b16": ("ViT-B/16", zoo.clip_vit_b16), "b32": ("ViT-B/32", zoo.clip_vit_b32)}[args.model]
+    model = ctor()
+    if args.dtype == "fp16":
+        zoo.convert_weights_fp16(model)
+    model = model.to(DEV).eval()
+    ids = torch.randint(0, 49408, (1, 77), generator=torch.Generator().manual_seed(1)).to(DEV)
+    txt = m2ib.wrapper_text_features(model, ids)
+    x32 = torch.randn(32, 3, 224, 224, generator=torch.Generator().manual_seed(1)).to(DEV)
+    x1 = x32[:1]
+    lines = []
+    if not os.path.exists(args.out) or os.path.getsize(args.out) == 0:
+        lines += [f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; CLIP ViT-B (random weights), 224 x 224, layer {LAYER}, "
+                  f"{STEPS} steps on {COPIES} copies; device events around a window of calls, median, min, max of {WINDOWS} windows", ""]
+    lines.append(f"{name}, {args.dtype}: the row, ms per image")
+    lines.append("  m2ib_batch, B = 1                  %9.3f %9.3f %9.3f" % windows(lambda: m2ib.m2ib_batch(model, x1, txt, img_hw=224), args.calls, 1.0))
+    lines.append("  m2ib_batch, B = 32                 %9.3f %9.3f %9.3f" % windows(lambda: m2ib.m2ib_batch(model, x32, txt, img_hw=224), 1, 1.0 / 32))
+    lines.append("  torch operators, one image         %9.3f %9.3f %9.3f" % windows(lambda: torch_row(model, x1, ids), args.calls, 1.0))
+    D = int(model.visual.transformer.width)
+    L = (224 // model.visual.conv1.kernel_size[0]) ** 2 + 1
+    lines.append(f"{name}, {args.dtype}: kernels at R = {COPIES}, L = {L}, D = {D}, us per launch")
+    for B in (1, 32):
+        g = torch.Generator().manual_seed(B)
+        alpha = (5 + torch.randn(B, L, D, generator=g)).to(DEV)
+        x9 = torch.randn(B, L, D, generator=g).to(DEV, model.dtype)
+        eps = torch.randn(B, COPIES, L, D, generator=g).to(DEV)
+        gt = (1e-3 * torch.randn(B, COPIES, L, D, generator=g)).to(DEV, model.dtype)
+        m, v = torch.zeros_like(alpha), torch.zeros_like(alpha)
+        scalars = m2ib.adam_scalars(1)
+
+        def torch_sample():
+            return bottleneck(alpha[:, None], x9[:, None], eps)[0].to(model.dtype)
+
+        p = torch.nn.Parameter(alpha.clone())
+        opt = torch.optim.Adam(lr=1, params=[p])
+
+        def torch_step():
+            opt.zero_grad()
+            t, cap = bottleneck(p[:, None], x9[:, None].expand(-1, COPIES, -1, -1), eps)
+            ((t * gt).sum() + BETA * cap.mean(dim=(1, 2, 3)).sum()).backward()
+            opt.step()
+
+        def torch_saliency():
+            return torch.nansum(bottleneck(alpha, x9.float(), 0.0)[1], -1)[:, 1:]
+
+        t88 = windows(lambda: K.m2ib_sample(alpha, x9, eps), args.launches, 1e3)
+        t88t = windows(torch_sample, args.launches, 1e3)
+        t89 = windows(lambda: K.m2ib_adam_step(gt, eps, x9, alpha.clone(), m, v, BETA, *scalars), args.launches, 1e3)
+        clone = windows(lambda: alpha.clone(), args.launches, 1e3)
+        t89t = windows(torch_step, args.launches, 1e3)
+        xf = x9.float()
+        t90 = windows(lambda: K.m2ib_saliency(alpha, xf), args.launches, 1e3)
+        t90t = windows(torch_saliency, args.launches, 1e3)
+        lines.append(f"  K88 xai_cm2ib_sample, B = {B:<2d}                     %10.2f %10.2f %10.2f" % t88)
+        lines.append(f"  its torch expression, B = {B:<2d}                    %10.2f %10.2f %10.2f      x %.2f" % (*t88t, t88t[0] / t88[0]))
+        lines.append(f"  K89 xai_cm2ib_adam_step (+ a copy of alpha, %.2f us), B = {B:<2d}  %10.2f %10.2f %10.2f" % ((clone[0],) + t89))
+        lines.append(f"  autograd and torch.optim.Adam, B = {B:<2d}           %10.2f %10.2f %10.2f      x %.2f" % (*t89t, t89t[0] / t89[0]))
+        lines.append(f"  K90 xai_cm2ib_saliency_f32, B = {B:<2d}              %10.2f %10.2f %10.2f" % t90)
+        lines.append(f"  its torch expression, B = {B:<2d}                    %10.2f %10.2f %10.2f      x %.2f" % (*t90t, t90t[0] / t90[0]))
+    lines.append("")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,9 +1,8 @@
 // K82-K85: the attention rows of CLIP (game, rollout, lrp) from the attention probabilities and their gradients (libxai_cattn.so).
 // include/xai_cattn.h states the arithmetic: what is rounded to the operand dtype T and where, and the order of every sum.
-#include <hip/hip_fp16.h>
-
 #include "xai_common.h"
 #include "xai_cattn.h"
+#include "clip_device.h"
 
 XAI_VERSION_ENTRIES(xai_cattn_version, XAI_CATTN_VERSION, XAI_CATTN_MINOR)
 XAI_EXPORT int xai_cattn_max_tokens(void) { return XAI_CATTN_MAX_TOKENS; }
@@ -19,16 +18,6 @@ constexpr int kRowWaves = kRowThreads / kWave;
 constexpr int kMatThreads = 256;  // K84: streaming, a lane per 16 bytes
 constexpr int kRowUnroll = 8;     // K85: loads in flight per lane
 
-// ld: an operand as fp32;  rT: the header's rounding to T;  st: a result that already passed rT
-__device__ __forceinline__ float ld(const float* p) { return *p; }
-__device__ __forceinline__ float ld(const __half* p) { return __half2float(*p); }
-template <typename T>
-__device__ __forceinline__ float rT(float x) {
-  if constexpr (std::is_same<T, __half>::value) return __half2float(__float2half_rn(x));
-  else return x;
-}
-__device__ __forceinline__ void st(float* p, float x) { *p = x; }
-__device__ __forceinline__ void st(__half* p, float x) { *p = __float2half_rn(x); }
 // the header's relu: a NaN stays, -0 becomes +0
 __device__ __forceinline__ float relu_keep_nan(float x) { return x > 0.f ? x : (x != x ? x : 0.f); }
 

@@ -1,9 +1,8 @@
 // K75-K77: the class-token row of CLIP's last visual block and the Grad-ECLIP / MaskCLIP maps read from it (libxai_clip.so).
 // include/xai_clip.h states the arithmetic: what is rounded to the operand dtype T and where, and the order of every sum.
-#include <hip/hip_fp16.h>
-
 #include "xai_common.h"
 #include "xai_clip.h"
+#include "clip_device.h"
 
 XAI_VERSION_ENTRIES(xai_clip_version, XAI_CLIP_VERSION, XAI_CLIP_MINOR)
 XAI_EXPORT int xai_clip_max_tokens(void) { return XAI_CLIP_MAX_TOKENS; }
@@ -14,17 +13,6 @@ namespace {
 
 constexpr int kThreads = 1024;  // 16 waves: a wave per token row, so L = 197 rows are 13 rounds (measured against 4 waves: profiles/r21_eclip.txt)
 constexpr int kWaves = kThreads / kWave;
-
-// ld: an operand as fp32;  rT: the header's rounding to T;  st: a result that already passed rT
-__device__ __forceinline__ float ld(const float* p) { return *p; }
-__device__ __forceinline__ float ld(const __half* p) { return __half2float(*p); }
-template <typename T>
-__device__ __forceinline__ float rT(float x) {
-  if constexpr (std::is_same<T, __half>::value) return __half2float(__float2half_rn(x));
-  else return x;
-}
-__device__ __forceinline__ void st(float* p, float x) { *p = x; }
-__device__ __forceinline__ void st(__half* p, float x) { *p = __float2half_rn(x); }
 
 // the header's SUM over one row by one wave (DOT and SUMSQ are SUM over the products); every lane gets the result
 template <typename F>

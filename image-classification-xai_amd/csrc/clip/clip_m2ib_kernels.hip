@@ -1,9 +1,8 @@
 // K88-K90: CLIP's M2IB row (libxai_cm2ib.so): the sample of the information bottleneck, the gradient of alpha with its Adam step,
 // and the capacity with its nansum per token.  include/xai_hip_cm2ib.h states the arithmetic: every operation and the order of every sum.
-#include <hip/hip_fp16.h>
-
 #include "xai_common.h"
 #include "xai_hip_cm2ib.h"
+#include "clip_device.h"
 
 XAI_VERSION_ENTRIES(xai_cm2ib_version, XAI_CM2IB_VERSION, XAI_CM2IB_MINOR)
 XAI_EXPORT int xai_cm2ib_max_tokens(void) { return XAI_CM2IB_MAX_TOKENS; }
@@ -14,12 +13,6 @@ namespace {
 
 constexpr int kThreads = 256;  // K88, K89: streaming, a lane per (l, d);  K90: 4 waves, a wave per token
 constexpr int kWaves = kThreads / kWave;
-
-// ld: an operand as fp32;  st: a result rounded to T once (the header's rT)
-__device__ __forceinline__ float ld(const float* p) { return *p; }
-__device__ __forceinline__ float ld(const __half* p) { return __half2float(*p); }
-__device__ __forceinline__ void st(float* p, float x) { *p = x; }
-__device__ __forceinline__ void st(__half* p, float x) { *p = __float2half_rn(x); }
 
 // the header's per-element values
 struct Gate {

@@ -19,9 +19,8 @@ one-row flow; what lies between its GEMMs are the kernels K75-K77 (include/xai_c
 `clip_encode_dense`, `attention_layer`, `grad_eclip` and `mask_clip` are the full-row functions under the reference's names,
 signatures and return values, for callers that use them directly: plain torch operations, any device.
 
-Every image of a batch gets the bytes of its own one-image call: the GEMMs run image by image (a GEMM's summation order depends on
-its extents) and the kernels, which give every image its own workgroup, take the batch -- the rule of xai_engine/lrp.py.  Eager
-only: nothing here is captured into a hipGraph.
+The layout check, the tokens, the per-image loop and the epilogue are xai_engine/clip_tower.py's, which states the rule that every
+image of a batch gets the bytes of its own one-image call.
 
 Refused here: surgery and m2ib need other models, and game, rollout and lrp are computed by the reference on a second model object
 (`REFUSED` names them all).  That second model has plain CLIP's weights and forward, so xai_engine/clip_attn.py serves game, rollout
@@ -31,8 +30,8 @@ because this engine holds one model where the reference holds two.  `eclip_batch
 import torch
 import torch.nn.functional as F
 
+from . import clip_tower as T
 from . import kernels as K
-from .ig import hip_device
 
 METHODS = ("eclip", "eclip_wo", "eclip_nograd", "maskclip", "selfattn")
 # method -> (withksim, withgrad) of grad_eclip, evaluatePerturbation.py:401-409
@@ -43,45 +42,11 @@ REFUSED = {"game": "the modified CLIP of Game_MM_CLIP (mm_interpret, testing_dic
            "surgery": "the CLIP Surgery model (clip_surgery_map, testing_dict['models'][2])",
            "m2ib": "the M2IB wrapper and its tokenizer (m2ib_clip_map, testing_dict['models'][3] and [4])"}
 
-_VISUAL = ("conv1", "class_embedding", "positional_embedding", "ln_pre", "transformer", "ln_post", "proj", "input_resolution")
-_BLOCK = ("ln_1", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj", "ln_2", "mlp")
-
 
 def check_layout(clipmodel):
     """The attributes the pass reads (OpenAI's names), or a TypeError naming the one that is missing.  -> (visual, last block)"""
-    def need(obj, path, where):
-        for name in path.split("."):
-            if not hasattr(obj, name):
-                raise TypeError(f"eclip needs a CLIP of OpenAI's layout: {type(clipmodel).__name__} has no `{where}{path}`")
-            obj = getattr(obj, name)
-        return obj
-    visual = need(clipmodel, "visual", "")
-    for path in _VISUAL:
-        need(visual, path, "visual.")
-    need(visual, "transformer.width", "visual.")
-    blocks = need(visual, "transformer.resblocks", "visual.")
-    if len(blocks) == 0:
-        raise TypeError(f"eclip needs a CLIP of OpenAI's layout: {type(clipmodel).__name__} has no `visual.transformer.resblocks[-1]`")
-    for path in _BLOCK:
-        need(blocks[-1], path, "visual.transformer.resblocks[-1].")
+    visual, blocks, _ = T.check_layout(clipmodel, "eclip")
     return visual, blocks[-1]
-
-
-def _tokens(visual, x):
-    """x (N, 3, H, W) -> the (L, N, D) input of the first block and the conv grid (generate_emap.py:316-338): patch embedding, class
-    token, the positional embedding through the reference's bicubic interpolation to the grid (an identity at the native size), ln_pre"""
-    x = visual.conv1(x.to(visual.conv1.weight.dtype))
-    grid = tuple(x.shape[-2:])
-    x = x.flatten(2).transpose(1, 2)
-    x = torch.cat((visual.class_embedding.to(x.dtype).expand(x.shape[0], 1, -1), x), dim=1)
-    pos = visual.positional_embedding.to(x.dtype)
-    ksize = visual.conv1.kernel_size
-    ph, pw = visual.input_resolution // ksize[0], visual.input_resolution // ksize[1]
-    if pos.shape[0] != ph * pw + 1:
-        raise ValueError(f"visual.positional_embedding has {pos.shape[0]} rows, input_resolution and the patch size give {ph * pw + 1}")
-    img_pos = F.interpolate(pos[1:].reshape(1, ph, pw, -1).permute(0, 3, 1, 2), size=grid, mode="bicubic", align_corners=False)
-    pos = torch.cat((pos[:1], img_pos.flatten(2)[0].t()), dim=0)
-    return visual.ln_pre(x + pos).transpose(0, 1), grid
 
 
 # ---------------------------------------------------------------------------------- the reference's full-row functions
@@ -102,7 +67,7 @@ def clip_encode_dense(x, clipmodel):
     """The reference's 9-tuple (outputs (N, L, E), v_final[:, 1:], x_in, v, q_out, k_out, attn, attn_output, (h, w)); attn_output is
     in the autograd graph of outputs.  x is cast to the model's dtype (the reference's x.half() on its GPU model)."""
     visual, last = check_layout(clipmodel)
-    x, grid = _tokens(visual, x)
+    x, grid = T.interpolated_tokens(visual, x)
     x_in = torch.nn.Sequential(*visual.transformer.resblocks[:-1])(x)
     w, b = last.attn.out_proj.weight, last.attn.out_proj.bias
     q, k, v = F.linear(last.ln_1(x_in), last.attn.in_proj_weight, last.attn.in_proj_bias).chunk(3, dim=-1)
@@ -150,13 +115,6 @@ class ClsPass:
     the embedding; grid (h, w).  `leaves[b]` is the (1, D) autograd leaf that is row b of att_output, and outputs0[b] hangs on it."""
 
 
-def _tail(visual, last, rows, residual):
-    """out_proj, residual, MLP, ln_post and the projection of (n, D) rows"""
-    y = F.linear(rows, last.attn.out_proj.weight, last.attn.out_proj.bias) + residual
-    y = y + last.mlp(last.ln_2(y))
-    return visual.ln_post(y) @ visual.proj
-
-
 def cls_pass(clipmodel, x, want_grad=True):
     """The class-token row of clip_encode_dense for x (B, 3, H, W), on the model's HIP device -> ClsPass.  want_grad: keep the one-row tail in
     the autograd graph, for eclip and eclip_wo."""
@@ -166,18 +124,18 @@ def cls_pass(clipmodel, x, want_grad=True):
     ksize = visual.conv1.kernel_size
     if x.shape[2] % ksize[0] or x.shape[3] % ksize[1]:
         raise ValueError(f"x is {x.shape[2]} x {x.shape[3]}: H and W must be multiples of the patch size {tuple(ksize)}")
-    dev = hip_device(visual.conv1.weight.device)          # the model's device: the harness hands host tensors in
-    x = x.to(dev)
     B, D = x.shape[0], visual.transformer.width
     w_in, b_in = last.attn.in_proj_weight, last.attn.in_proj_bias
     w_out, b_out = last.attn.out_proj.weight, last.attn.out_proj.bias
     p = ClsPass()
+
+    def tokens(visual, image):
+        tok, p.grid = T.interpolated_tokens(visual, image)
+        return tok
     with torch.no_grad():
-        for b in range(B):
-            tok, p.grid = _tokens(visual, x[b:b + 1])
-            x_in = torch.nn.Sequential(*visual.transformer.resblocks[:-1])(tok)
+        for b, x_in in T.per_image(visual, x, list(visual.transformer.resblocks)[:-1], tokens):
             if b == 0:
-                L = x_in.shape[0]
+                L, dev = x_in.shape[0], x_in.device
                 p.x_in = torch.empty((L, B, D), dtype=x_in.dtype, device=dev)
                 kv = torch.empty((L, B, 2 * D), dtype=x_in.dtype, device=dev)
                 p.k_out = torch.empty((L, B, D), dtype=x_in.dtype, device=dev)
@@ -193,17 +151,8 @@ def cls_pass(clipmodel, x, want_grad=True):
         p.attn, p.att_output = K.clip_cls_attention(q0, p.k, p.v)
     p.leaves = [p.att_output[b:b + 1].clone().requires_grad_(want_grad) for b in range(B)]
     with torch.set_grad_enabled(want_grad):
-        p.outputs0 = [_tail(visual, last, leaf, p.x_in[0, b]) for b, leaf in enumerate(p.leaves)]
+        p.outputs0 = [T.tail(visual, last, leaf, p.x_in[0, b]) for b, leaf in enumerate(p.leaves)]
     return p
-
-
-def _texts(txt_embedding, B, dtype, dev):
-    t = txt_embedding.to(device=dev, dtype=dtype)
-    if t.dim() == 2:
-        t = t.unsqueeze(0).expand(B, -1, -1)
-    if t.dim() != 3 or t.shape[0] != B or t.shape[1] < 1:
-        raise ValueError(f"txt_embedding must be (T, E) or ({B}, T, E) with T >= 1, got {tuple(txt_embedding.shape)}")
-    return t
 
 
 def eclip_batch(clipmodel, x, txt_embedding, method, img_hw=None):
@@ -218,17 +167,17 @@ def eclip_batch(clipmodel, x, txt_embedding, method, img_hw=None):
     withksim, withgrad = _ECLIP_FLAGS.get(method, (False, False))
     p = cls_pass(clipmodel, x, want_grad=withgrad)
     B, dev = len(p.leaves), p.attn.device
-    txt = _texts(txt_embedding, B, p.attn.dtype, dev)
+    E = visual.proj.shape[1]
+    # the feature count is checked where a kernel reads the features; the other rows multiply by them in torch, or only count T
+    txt = T.texts(txt_embedding, B, E if method == "maskclip" else None, "txt_embedding")
+    txt = txt.to(device=dev, dtype=p.attn.dtype).expand(B, -1, -1)
     if method == "selfattn":
         maps = p.attn[:, 1:].float()
     elif method == "maskclip":
         with torch.no_grad():
-            E = visual.proj.shape[1]
             v_final = torch.empty((B, p.k.shape[0] - 1, E), dtype=p.attn.dtype, device=dev)
             for b in range(B):
-                v_final[b] = _tail(visual, last, p.v[:, b], p.x_in[:, b])[1:]
-        if txt.shape[2] != E:
-            raise ValueError(f"txt_embedding has {txt.shape[2]} features, the model embeds into {E}")
+                v_final[b] = T.tail(visual, last, p.v[:, b], p.x_in[:, b])[1:]
         maps = K.clip_maskclip_map(v_final, txt.contiguous(), p.k_out)
     else:
         grad_cls = None
@@ -239,8 +188,5 @@ def eclip_batch(clipmodel, x, txt_embedding, method, img_hw=None):
                 for t, c in enumerate(cosines):
                     grad_cls[b, t] = torch.autograd.grad(c, leaf, retain_graph=True)[0][0]
         maps = K.clip_eclip_map(p.q_out0, p.k_out, p.v, grad_cls, texts=txt.shape[1], withksim=withksim, withgrad=withgrad)
-    maps = maps.reshape(B, *p.grid)
-    if img_hw is None:
-        return maps
-    return K.resize_bilinear(maps.contiguous(), img_hw, img_hw, take_abs=True)
+    return T.finish(maps, B, p.grid, img_hw)
 

@@ -2103,6 +2103,31 @@ def _clip_rows(t, shape, like, name):
     return t
 
 
+def _clip_per_text(t, B, D, like, name):
+    """A dense (B, T, D) operand in the dtype and on the device of `like` -> T"""
+    _need(t, like.dtype, name)
+    if t.dim() != 3 or t.shape[0] != B or t.shape[2] != D or t.device != like.device:
+        raise ValueError(f"{name} must be ({B}, T, {D}) on {like.device}, got {tuple(t.shape)} on {t.device}")
+    return int(t.shape[1])
+
+
+def _clip_txt(txt, B, E, like):
+    """txt (T, E), shared by the images, or (B, T, E), in the dtype and on the device of `like`: what a host can test of it, the
+    caller's _need follows or went before -> (T, the stride from image to image: T * E, or 0 for shared texts)"""
+    _typed(txt, like.dtype, "txt")
+    if txt.dim() not in (2, 3) or txt.numel() == 0 or txt.shape[-1] != E or (txt.dim() == 3 and txt.shape[0] != B) \
+            or txt.device != like.device:
+        raise ValueError(f"txt must be (T, {E}) or ({B}, T, {E}) on {like.device}, got {tuple(txt.shape)} on {txt.device}")
+    T = int(txt.shape[-2])
+    return T, T * E if txt.dim() == 3 else 0
+
+
+def _texts_within(T, limit, kernels):
+    if not 1 <= T <= limit:
+        raise ValueError(f"T = {T} texts: {kernels} take 1 .. {limit}")
+    return T
+
+
 def clip_cls_attention(q0, k, v, want_scores=False):
     """K75: q0 (B, D) the class row of q, k and v (L, B, D) -> (attn (B, L), att_out (B, D)) in the operands' dtype: row 0 of the
     one-head attention of generate_emap.py:288-307.  want_scores: a third result, the (B, L) scores in front of the softmax."""
@@ -2117,12 +2142,6 @@ def clip_cls_attention(q0, k, v, want_scores=False):
     return (attn, att_out, scores) if want_scores else (attn, att_out)
 
 
-def _clip_texts(T):
-    if not 1 <= T <= clip_limits()[2]:
-        raise ValueError(f"T = {T} texts: K76 and K77 take 1 .. {clip_limits()[2]}")
-    return T
-
-
 def clip_eclip_map(q_out0, k_out, v, grad_cls=None, texts=None, withksim=True, withgrad=True):
     """K76: q_out0 (B, D), k_out and v (L, B, D), grad_cls (B, T, D) (None without withgrad: then `texts` = T) -> (B, L - 1) fp32,
     grad_eclip of generate_emap.py:453-485 summed over the T texts."""
@@ -2132,13 +2151,10 @@ def clip_eclip_map(q_out0, k_out, v, grad_cls=None, texts=None, withksim=True, w
         _, _, _, kl, kb = _clip_tokens(k_out, "k_out", like=v)
         _clip_rows(q_out0, (B, D), v, "q_out0")
     if withgrad:
-        _need(grad_cls, v.dtype, "grad_cls")
-        if grad_cls.dim() != 3 or grad_cls.shape[0] != B or grad_cls.shape[2] != D or grad_cls.device != v.device:
-            raise ValueError(f"grad_cls must be ({B}, T, {D}) on {v.device}, got {tuple(grad_cls.shape)} on {grad_cls.device}")
-        texts = grad_cls.shape[1]
+        texts = _clip_per_text(grad_cls, B, D, v, "grad_cls")
     elif texts is None:
         raise TypeError("clip_eclip_map: without withgrad there is no grad_cls to count the texts; pass texts=T")
-    T = _clip_texts(int(texts))
+    T = _texts_within(int(texts), clip_limits()[2], "K76 and K77")
     out = torch.empty((B, L - 1), dtype=F32, device=v.device)
     _call(f"xai_clip_eclip_map_{_suffix(v)}", v.device, _ptr(q_out0) if withksim else None, _ptr(k_out) if withksim else None, kl, kb,
           _ptr(v), vl, vb, _ptr(grad_cls) if withgrad else None, B, L, D, T, int(bool(withksim)), int(bool(withgrad)), _ptr(out),
@@ -2156,12 +2172,10 @@ def clip_maskclip_map(v_final, txt, k_out):
     E = v_final.shape[2]
     if E > clip_limits()[1]:
         raise ValueError(f"v_final: E = {E} is over the limit of K77 (E <= {clip_limits()[1]})")
-    _need(txt, k_out.dtype, "txt")
-    if txt.dim() not in (2, 3) or txt.shape[-1] != E or (txt.dim() == 3 and txt.shape[0] != B) or txt.device != k_out.device:
-        raise ValueError(f"txt must be (T, {E}) or ({B}, T, {E}) on {k_out.device}, got {tuple(txt.shape)} on {txt.device}")
-    T = _clip_texts(txt.shape[-2])
+    T, txt_ld = _clip_txt(_need(txt, k_out.dtype, "txt"), B, E, k_out)
+    _texts_within(T, clip_limits()[2], "K76 and K77")
     out = torch.empty((B, L - 1), dtype=F32, device=k_out.device)
-    _call(f"xai_clip_maskclip_map_{_suffix(k_out)}", k_out.device, _ptr(v_final), _ptr(txt), T * E if txt.dim() == 3 else 0,
+    _call(f"xai_clip_maskclip_map_{_suffix(k_out)}", k_out.device, _ptr(v_final), _ptr(txt), txt_ld,
           _ptr(k_out), kl, kb, B, L, D, E, T, _ptr(out), lib="clip")
     return out
 
@@ -2188,13 +2202,6 @@ def _cattn_rows(t, name, like=None):
     return B, H, L
 
 
-def _cattn_texts(T):
-    _int(T, "texts")
-    if not 1 <= T <= cattn_limits()[2]:
-        raise ValueError(f"T = {T} texts: K82 and K83 take 1 .. {cattn_limits()[2]}")
-    return T
-
-
 def clip_game_map(g, v, a0):
     """K82: g (B, T, D) the gradients of the T logits with respect to row 0 of the last block's attention output, v (L, B, D), a0
     (B, H, L) the class-token row of every head -> (B, L - 1) fp32, mm_interpret of generate_emap.py:133-174 summed over the texts."""
@@ -2202,10 +2209,7 @@ def clip_game_map(g, v, a0):
     _, H, _ = _cattn_rows(a0, "a0", like=v)
     if tuple(a0.shape) != (B, H, L) or D % H:
         raise ValueError(f"a0 must be ({B}, H, {L}) with H dividing D = {D}, got {tuple(a0.shape)}")
-    _need(g, v.dtype, "g")
-    if g.dim() != 3 or g.shape[0] != B or g.shape[2] != D or g.device != v.device:
-        raise ValueError(f"g must be ({B}, T, {D}) on {v.device}, got {tuple(g.shape)} on {g.device}")
-    T = _cattn_texts(int(g.shape[1]))
+    T = _texts_within(_clip_per_text(g, B, D, v, "g"), cattn_limits()[2], "K82 and K83")
     out = torch.empty((B, L - 1), dtype=F32, device=v.device)
     _call(f"xai_cattn_game_map_{_suffix(v)}", v.device, _ptr(g), _ptr(v), vl, vb, _ptr(a0), B, L, D, H, T, _ptr(out), lib="cattn")
     return out
@@ -2216,7 +2220,7 @@ def clip_rollout_row(a0, texts=1):
     mm_interpret(rollout=True) hands it; `texts`: how often the reference repeats the image in its batch."""
     _int(texts, "texts")
     B, H, L = _cattn_rows(a0, "a0")
-    T = _cattn_texts(texts)
+    T = _texts_within(texts, cattn_limits()[2], "K82 and K83")
     out = torch.empty((B, L - 1), dtype=F32, device=a0.device)
     _call(f"xai_cattn_rollout_row_{_suffix(a0)}", a0.device, _ptr(a0), B, H, L, T, _ptr(out), lib="cattn")
     return out
@@ -2302,10 +2306,7 @@ def clip_surgery_similarity(features, txt, texts_out=1, want_weights=False):
     B, L, E = features.shape
     if L < 2:
         raise ValueError(f"features: L = {L}; the class token and at least one patch are needed (L >= 2)")
-    _typed(txt, F32, "txt")
-    if txt.dim() not in (2, 3) or txt.numel() == 0 or txt.shape[-1] != E or (txt.dim() == 3 and txt.shape[0] != B):
-        raise ValueError(f"txt must be (T, {E}) or ({B}, T, {E}), got {tuple(txt.shape)}")
-    T = int(txt.shape[-2])
+    T, txt_ld = _clip_txt(txt, B, E, features)
     T_out = _int(texts_out, "texts_out", least=1)
     if T_out > T:
         raise ValueError(f"texts_out = {T_out} of T = {T} texts")
@@ -2315,11 +2316,9 @@ def clip_surgery_similarity(features, txt, texts_out=1, want_weights=False):
                          f"2 * E + T <= {lds})")
     _need(features, F32, "features")
     _need(txt, F32, "txt")
-    if txt.device != features.device:
-        raise ValueError(f"txt must be on {features.device}, got {txt.device}")
     out = torch.empty((B, T_out, L - 1), dtype=F32, device=features.device)
     w = torch.empty((B, T), dtype=F32, device=features.device) if want_weights else None
-    _call("xai_csurg_similarity_map_f32", features.device, _ptr(features), _ptr(txt), T * E if txt.dim() == 3 else 0, B, L, E, T, T_out,
+    _call("xai_csurg_similarity_map_f32", features.device, _ptr(features), _ptr(txt), txt_ld, B, L, E, T, T_out,
           _ptr(w), _ptr(out), lib="csurg")
     return (out, w) if want_weights else out
 

@@ -29,8 +29,8 @@ bottleneck never see it, so the row is served here on testing_dict["models"][0];
                that is never read): a CPU-seeded reference run is reproduced draw for draw.  A tensor (steps - 1, copies, L, D), or
                that with a leading B, is taken as given.
 
-Every image of a batch gets the bytes of its own one-image call when it gets the same noise: the GEMMs run image by image, the
-kernels take the batch -- the rule of xai_engine/eclip.py, clip_attn.py and surgery.py.  Eager only: the step is static-shaped, but
+Every image of a batch gets the bytes of its own one-image call when it gets the same noise (the rule and the shared checks,
+tokens, head loop and epilogue are xai_engine/clip_tower.py's).  Eager only: the step is static-shaped, but
 its middle is torch.autograd.grad through torch's own blocks, whose graph and buffers are made anew in every step; it is not on the
 shared capture-and-proof path, so no `graphs=True` is offered.  The model's HIP device is required; there is no CPU path
 (wrapper_text_features alone is plain torch and runs on the CPU too).
@@ -40,10 +40,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-from . import clip_attn
+from . import clip_tower as T
 from . import kernels as K
-from .ig import hip_device
-from .surgery import resize_maps
 
 MAP_SIZE = 224                      # iba.py:157, `interpolate(saliency, size=224, mode='bilinear')`
 INITIAL_ALPHA = 5.0                 # iba.py:93
@@ -52,11 +50,7 @@ ADAM = (0.9, 0.999, 1e-8)           # torch.optim.Adam's defaults, which iba.py:
 
 def check_model(clipmodel, layer=9):
     """The layout m2ib_batch reads, or an error naming what is missing -> (visual, blocks, H)"""
-    visual = getattr(clipmodel, "visual", None)
-    if visual is not None and not hasattr(visual, "transformer") and hasattr(visual, "attnpool"):
-        raise NotImplementedError("m2ib: a ResNet visual tower (AttentionPool2d) is not served; the reference's wrapper reads "
-                                  "visual.transformer.resblocks")
-    visual, blocks, H = clip_attn.check_layout(clipmodel, every_block=True)
+    visual, blocks, H = T.check_layout(clipmodel, "m2ib", every_block=True, heads=True)
     K._int(layer, "layer")
     if not 0 <= layer <= len(blocks) - 2:
         raise ValueError(f"m2ib: layer = {layer} is outside 0 .. {len(blocks) - 2}: the bottleneck sits behind visual block `layer` "
@@ -64,28 +58,11 @@ def check_model(clipmodel, layer=9):
     return visual, blocks, H
 
 
-def _checked_input(visual, x):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"x: expected a torch.Tensor, got {type(x).__name__}")
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"x must be (B, 3, H, W), got {tuple(x.shape)}")
-    res = int(visual.input_resolution)
-    if tuple(x.shape[2:]) != (res, res):
-        raise NotImplementedError(f"m2ib: x is {x.shape[2]} x {x.shape[3]}, the model's input_resolution is {res}: the row takes the "
-                                  "reference's preprocess(img); the wrapper adds the positional embedding without interpolating it, and "
-                                  "PIL's bicubic resize is not built")
-    ksize = visual.conv1.kernel_size
-    return res, (res // ksize[0], res // ksize[1])
-
-
 def _checked_texts(text_features, B, E):
-    if not isinstance(text_features, torch.Tensor):
-        raise TypeError(f"text_features: expected a torch.Tensor, got {type(text_features).__name__}")
+    T.tensor(text_features, "text_features")
     if text_features.dim() not in (1, 2) or (text_features.dim() == 2 and text_features.shape[0] not in (1, B)):
         raise ValueError(f"text_features must be (E,), (1, E) or ({B}, E), got {tuple(text_features.shape)}")
-    if text_features.shape[-1] != E:
-        raise ValueError(f"text_features has {text_features.shape[-1]} features, the model embeds into {E}")
-    return text_features.reshape(-1, E)
+    return T.embeds_into(text_features, E, "text_features").reshape(-1, E)
 
 
 def _checked_noise(noise, B, steps, R, L, D):
@@ -103,15 +80,7 @@ def _checked_noise(noise, B, steps, R, L, D):
 def _text_block(blk, x):
     """One block of the text tower on (L, N, D) tokens WITHOUT the causal mask (clip_wrapper.py:86, `layer.attn_mask = None`), in the
     sequence of nn.MultiheadAttention; the model's own block is not touched (the reference changes a deep copy)."""
-    L, N, D = x.shape
-    H = int(blk.attn.num_heads)
-    hd = D // H
-    q, k, v = F.linear(blk.ln_1(x), blk.attn.in_proj_weight, blk.attn.in_proj_bias).chunk(3, dim=-1)
-    q = q * (float(hd) ** -0.5)
-    q, k, v = (t.contiguous().view(L, N * H, hd).transpose(0, 1) for t in (q, k, v))
-    out = torch.bmm(F.softmax(torch.bmm(q, k.transpose(1, 2)), dim=-1), v).transpose(0, 1).contiguous().view(L, N, D)
-    x = x + F.linear(out, blk.attn.out_proj.weight, blk.attn.out_proj.bias)
-    return x + blk.mlp(blk.ln_2(x))
+    return T.written_out_block(blk, x, int(blk.attn.num_heads))[0]
 
 
 def wrapper_text_features(clipmodel, token_ids):
@@ -171,7 +140,7 @@ def m2ib_batch(clipmodel, x, text_features, img_hw=None, layer=9, beta=0.1, step
     (evaluatePerturbation.py:443-445).  layer, beta, steps, lr, copies: the reference's vlayer = 9, vbeta = 0.1, train_steps = 10,
     lr = 1, batch_size = 10.  noise, seed: see the module's docstring."""
     visual, blocks, _ = check_model(clipmodel, layer)
-    _, grid = _checked_input(visual, x)
+    _, grid = T.native_input(visual, x, "m2ib")
     B = x.shape[0]
     E, D = int(visual.proj.shape[1]), int(visual.transformer.width)
     L = grid[0] * grid[1] + 1
@@ -183,18 +152,15 @@ def m2ib_batch(clipmodel, x, text_features, img_hw=None, layer=9, beta=0.1, step
     noise = _checked_noise(noise, B, steps, R, L, D)
     if grid[0] != grid[1]:
         raise ValueError(f"m2ib: the patch grid {grid} is not square")
-    dev = hip_device(visual.conv1.weight.device)
     dtype = visual.conv1.weight.dtype
     head, tail = blocks[:layer + 1], blocks[layer + 1:]
-    x = x.to(device=dev)
-    txt = txt.to(device=dev, dtype=dtype)
     with torch.no_grad():
-        x9 = torch.empty((B, L, D), dtype=dtype, device=dev)
-        for b in range(B):
-            tok = clip_attn._native_tokens(visual, x[b:b + 1])
-            for blk in head:
-                tok = blk(tok)
+        for b, tok in T.per_image(visual, x, head, T.native_tokens):
+            if b == 0:
+                dev = tok.device
+                x9 = torch.empty((B, L, D), dtype=dtype, device=dev)
             x9[b] = tok[:, 0]
+        txt = txt.to(device=dev, dtype=dtype)
         alpha = torch.full((B, L, D), INITIAL_ALPHA, dtype=torch.float32, device=dev)
         m, v = torch.zeros_like(alpha), torch.zeros_like(alpha)
         draw = _noise_source(noise, seed, B, steps, R, L, D, dev)
@@ -206,12 +172,9 @@ def m2ib_batch(clipmodel, x, text_features, img_hw=None, layer=9, beta=0.1, step
                 gt[b] = _tail_grad(visual, tail, t[b], txt[b if txt.shape[0] > 1 else 0][None])
             K.m2ib_adam_step(gt, eps, x9, alpha, m, v, beta, *adam_scalars(k, lr))
         sal = K.m2ib_saliency(alpha, x9.float())                                             # (B, L - 1)
-        maps = resize_maps(sal.reshape(B, *grid), MAP_SIZE, MAP_SIZE)
+        maps = T.resize_maps(sal.reshape(B, *grid), MAP_SIZE, MAP_SIZE)
         lo, hi = maps.amin(dim=(1, 2), keepdim=True), maps.amax(dim=(1, 2), keepdim=True)
-        maps = (maps - lo) / (hi - lo)
-        if img_hw is not None:
-            maps = K.resize_bilinear(maps, img_hw, img_hw, take_abs=True)
-    return maps
+        return T.finish((maps - lo) / (hi - lo), B, (MAP_SIZE, MAP_SIZE), img_hw)
 
 
 def _noise_source(noise, seed, B, steps, R, L, D, dev):

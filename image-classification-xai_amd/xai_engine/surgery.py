@@ -32,9 +32,8 @@ The row takes the reference's `preprocess(img)` and the positional embedding as 
 anything else is refused (the Surgery tower's interpolation of the positional embedding is not built), and so are a ResNet visual
 tower and a tower of fewer than six blocks (the reference's `resblocks[-i]` raises there).
 
-Every image of a batch gets the bytes of its own one-image call: the GEMMs run image by image, the kernels take the batch -- the
-rule of xai_engine/eclip.py and clip_attn.py.  Eager only: nothing here is captured into a hipGraph.  The model's HIP device is
-required; there is no CPU path.
+The checks, the tokens, the per-image loop in front of the dual blocks and the epilogue are xai_engine/clip_tower.py's.  The
+model's HIP device is required; there is no CPU path.
 """
 import copy
 import weakref
@@ -42,12 +41,13 @@ import weakref
 import torch
 import torch.nn.functional as F
 
-from . import clip_attn
+from . import clip_tower as T
 from . import kernels as K
 from .ig import hip_device
 
 DUAL_BLOCKS = 6                     # clip_surgery_model.py:321, `for i in range(1, 7)`
 _FP32_TOWERS = weakref.WeakKeyDictionary()      # model object -> the fp32 copy of its visual tower
+resize_maps = T.resize_maps         # get_similarity_map's last step, under the name it has always had here
 
 
 def clear_cache():
@@ -60,7 +60,8 @@ def cached_towers():
     return len(_FP32_TOWERS)
 
 
-def _fp32_tower(clipmodel, visual):
+def fp32_tower(clipmodel, visual):
+    """The tower the row runs on: `visual` itself when it is fp32, else its cached fp32 copy"""
     if all(p.dtype == torch.float32 for p in visual.parameters()):
         return visual
     tower = _FP32_TOWERS.get(clipmodel)
@@ -74,37 +75,11 @@ def _fp32_tower(clipmodel, visual):
 
 def check_model(clipmodel):
     """The layout surgery_batch reads, or an error naming what is missing -> (visual, blocks, H)"""
-    visual = getattr(clipmodel, "visual", None)
-    if visual is not None and not hasattr(visual, "transformer") and hasattr(visual, "attnpool"):
-        raise NotImplementedError("surgery: a ResNet visual tower (AttentionPool2d) is not served; the reference's harness builds "
-                                  "CS-ViT-B/16 and CS-ViT-B/32 only")
-    visual, blocks, H = clip_attn.check_layout(clipmodel, every_block=True)
+    visual, blocks, H = T.check_layout(clipmodel, "surgery", every_block=True, heads=True)
     if len(blocks) < DUAL_BLOCKS:
         raise ValueError(f"surgery: the visual tower has {len(blocks)} blocks; the dual path takes the last {DUAL_BLOCKS} "
                          "(the reference's `resblocks[-i]` raises an IndexError there)")
     return visual, blocks, H
-
-
-def _checked_input(visual, x):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"x: expected a torch.Tensor, got {type(x).__name__}")
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"x must be (B, 3, H, W), got {tuple(x.shape)}")
-    res = int(visual.input_resolution)
-    if tuple(x.shape[2:]) != (res, res):
-        raise NotImplementedError(f"surgery: x is {x.shape[2]} x {x.shape[3]}, the model's input_resolution is {res}: the row takes the "
-                                  "reference's preprocess(img); the Surgery tower's interpolation of the positional embedding and "
-                                  "PIL's bicubic resize are not built")
-    ksize = visual.conv1.kernel_size
-    return res, (res // ksize[0], res // ksize[1])
-
-
-def _checked_texts(text_features, B):
-    if not isinstance(text_features, torch.Tensor):
-        raise TypeError(f"text_features: expected a torch.Tensor, got {type(text_features).__name__}")
-    if text_features.dim() not in (2, 3) or text_features.numel() == 0 or (text_features.dim() == 3 and text_features.shape[0] != B):
-        raise ValueError(f"text_features must be (T, E) or ({B}, T, E) with T >= 1, got {tuple(text_features.shape)}")
-    return text_features
 
 
 def _original_block(blk, x, H, qkv_out):
@@ -120,22 +95,14 @@ def _original_block(blk, x, H, qkv_out):
     return x + blk.mlp(blk.ln_2(x))
 
 
-def resize_maps(maps, H, W):
-    """get_similarity_map's F.interpolate(sm, shape, mode='bilinear') of (N, h, w) fp32 maps on the device -> (N, H, W).  torch's own
-    operator: K3 (kernels.bilinear_up) computes the same two taps but does not round as torch's kernel does
-    (tests/test_gpu_surgery.py measures the difference), and this step is the reference's last."""
-    return F.interpolate(maps[:, None], (H, W), mode="bilinear")[:, 0]
-
-
 def image_features(clipmodel, x):
     """encode_image of the Surgery model for x (B, 3, R, R) on the model's HIP device -> (B, L, E) fp32, not normalised"""
     visual, blocks, H = check_model(clipmodel)
-    _checked_input(visual, x)
-    dev = hip_device(visual.conv1.weight.device)
-    tower = _fp32_tower(clipmodel, visual)
+    T.native_input(visual, x, "surgery")
+    hip_device(visual.conv1.weight.device)                  # a model that is refused gets no fp32 copy
+    tower = fp32_tower(clipmodel, visual)
     blocks = list(tower.transformer.resblocks)
     head, dual = blocks[:-DUAL_BLOCKS], blocks[-DUAL_BLOCKS:]
-    x = x.to(device=dev, dtype=torch.float32)
     B, D = x.shape[0], int(tower.transformer.width)
     with torch.no_grad():
         w_cat = torch.cat([blk.attn.out_proj.weight for blk in dual], dim=1)              # (D, 6 D)
@@ -143,13 +110,10 @@ def image_features(clipmodel, x):
         for blk in dual[1:]:
             bias = bias + blk.attn.out_proj.bias
         qkv = x_in = cls = None
-        for b in range(B):
-            tok = clip_attn._native_tokens(tower, x[b:b + 1])
-            for blk in head:
-                tok = blk(tok)
+        for b, tok in T.per_image(tower, x, head, T.native_tokens):
             tok = tok.permute(1, 0, 2)                                                      # (1, L, D), as Attention.forward takes it
             if qkv is None:
-                L = tok.shape[1]
+                L, dev = tok.shape[1], tok.device
                 qkv = torch.empty((DUAL_BLOCKS, L, B, 3 * D), dtype=torch.float32, device=dev)
                 x_in = torch.empty((B, L, D), dtype=torch.float32, device=dev)
                 cls = torch.empty((B, D), dtype=torch.float32, device=dev)
@@ -176,20 +140,14 @@ def surgery_batch(clipmodel, x, text_features, img_hw=None, texts_out=1):
     visual tower, keyed by the model object, about 350 MB for ViT-B/16 (the reference holds a second whole model, 600 MB);
     clear_cache() frees it, and a model loaded in fp32 needs none."""
     visual, _, _ = check_model(clipmodel)
-    res, grid = _checked_input(visual, x)
+    res, grid = T.native_input(visual, x, "surgery")
     B = x.shape[0]
-    _checked_texts(text_features, B)
+    T.texts(text_features, B, visual.proj.shape[1], "text_features")
     K._int(texts_out, "texts_out", least=1)
-    E = visual.proj.shape[1]
-    if text_features.shape[-1] != E:
-        raise ValueError(f"text_features has {text_features.shape[-1]} features, the model embeds into {E}")
     if texts_out > text_features.shape[-2]:
         raise ValueError(f"texts_out = {texts_out} of T = {text_features.shape[-2]} texts")
-    dev = hip_device(visual.conv1.weight.device)
     feats = image_features(clipmodel, x)
-    txt = text_features.to(device=dev, dtype=torch.float32).contiguous()
+    txt = text_features.to(device=feats.device, dtype=torch.float32).contiguous()
     sim = K.clip_surgery_similarity(feats, txt, texts_out=texts_out)                        # (B, texts_out, L - 1)
-    maps = resize_maps(sim.reshape(B * texts_out, *grid), res, res)
-    if img_hw is not None:
-        maps = K.resize_bilinear(maps, img_hw, img_hw, take_abs=True)
+    maps = T.finish(resize_maps(sim.reshape(B * texts_out, *grid), res, res), B * texts_out, (res, res), img_hw)
     return maps.reshape(B, *maps.shape[1:]) if texts_out == 1 else maps.reshape(B, texts_out, *maps.shape[1:])

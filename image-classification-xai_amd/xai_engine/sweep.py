@@ -290,92 +290,82 @@ def clip_keepsize_input(trans_img, patch=(16, 16)):
     return x.sub(mean).div(std).unsqueeze(0)
 
 
+def _class_text(testing_dict, target_class):
+    """The (1, E) row of testing_dict["embeddings"] for the class, not normalised yet: the reference re-encodes "a photo of a <class>",
+    the very text that row was made from, so no tokeniser is needed"""
+    emb = testing_dict["embeddings"]
+    return emb.reshape(-1, emb.shape[-1])[int(target_class)][None]
+
+
+def _plain_attention_rows(td, clipmodel, target_class):
+    from . import clip_attn
+    txt = torch.nn.functional.normalize(_class_text(td, target_class), dim=-1)
+    return lambda x: clip_attn.attention_rows_batch(clipmodel, x, txt, td["attr_func"], img_hw=td["img_hw"])
+
+
+def _plain_surgery(td, clipmodel, target_class):
+    from . import surgery
+    context = td.get("surgery_text_features")
+    if context is None:
+        raise ValueError("get_CLIP_attr: clip_surgery='plain' needs testing_dict['surgery_text_features'], the (T - 1, E) text "
+                         "features of the context classes (59 prompt-ensembled class names in the reference's harness)")
+    row = _class_text(td, target_class)
+    if not isinstance(context, torch.Tensor) or context.dim() != 2 or context.shape[1] != row.shape[1]:
+        raise ValueError(f"get_CLIP_attr: surgery_text_features must be a (T - 1, {row.shape[1]}) tensor")
+    txt = torch.nn.functional.normalize(torch.cat([row.float(), context.to(row.device).float()]), dim=-1)
+    return lambda x: surgery.surgery_batch(clipmodel, x, txt, img_hw=td["img_hw"])
+
+
+def _plain_m2ib(td, clipmodel, target_class):
+    from . import m2ib
+    table = td.get("m2ib_text_features")
+    if table is None:
+        raise ValueError("get_CLIP_attr: clip_m2ib='plain' needs testing_dict['m2ib_text_features'], the (n_classes, E) table of "
+                         "the M2IB wrapper's text features (m2ib.wrapper_text_features of each class's token ids; they are not "
+                         "encode_text's, so `embeddings` does not serve)")
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != clipmodel.visual.proj.shape[1]:
+        raise ValueError(f"get_CLIP_attr: m2ib_text_features must be a (n_classes, {clipmodel.visual.proj.shape[1]}) tensor")
+    return lambda x: m2ib.m2ib_batch(clipmodel, x, table[int(target_class)], img_hw=td["img_hw"],
+                                     noise=td.get("m2ib_noise", "device"), seed=td.get("m2ib_seed"))
+
+
+# (the key of testing_dict that asks for it, the rows the key governs, what builds the row's text operand and returns the call):
+# the rows the reference runs on further model objects and this engine serves on models[0], in closed form, on request
+CLIP_PLAIN_ROWS = (("clip_attention_rows", CLIP_ATTENTION_ROWS, _plain_attention_rows),
+                   ("clip_surgery", ("surgery",), _plain_surgery),
+                   ("clip_m2ib", ("m2ib",), _plain_m2ib))
+
+
 def get_CLIP_attr(trans_img, target_class, testing_dict):
-    """(H,W) float32 numpy saliency map of the rows of the reference's get_CLIP_attr (evaluatePerturbation.py:373-445) that hang on
-    clip_encode_dense: eclip, eclip_wo, eclip_nograd, maskclip, selfattn (xai_engine/eclip.py).  The text embedding is
-    normalize(testing_dict["embeddings"][target_class]): the reference re-encodes "a photo of a <class>", the very text that row
-    of `embeddings` was made from, so no tokeniser is needed.  surgery and m2ib need further, modified CLIP models:
-    NotImplementedError naming the model.  game, rollout and lrp are refused the same way by default, because the reference runs them
-    on a second model object (testing_dict["models"][1]) and this engine has only models[0]; with
-    testing_dict["clip_attention_rows"] == "plain" they are served in closed form on models[0] (xai_engine/clip_attn.py: that second
-    model has plain CLIP's weights and forward, and the rows read only its attention probabilities and their gradients).  They take
-    the reference's preprocess(img), so the image must be input_resolution-square.  Any other value of the key: ValueError.
-    surgery is served the same way on request, testing_dict["clip_surgery"] == "plain" (xai_engine/surgery.py: the reference's third
-    model object is plain CLIP's state dict under another forward, in fp32).  Its text 0 is the normalised row of `embeddings`, like
-    every other row; the remaining texts are testing_dict["surgery_text_features"], a (T - 1, E) tensor (the 59 context classes of
-    evaluatePerturbation.py:427 in the reference's harness), normalised here; "plain" without that table, or any value of
-    `clip_surgery` other than None, "modified" and "plain": ValueError.  The reference also prompt-ensembles the caption over its 85
-    templates (encode_text_with_prompt_ensemble): a caller who wants that passes an `embeddings` table made that way.
-    m2ib is served on request too, testing_dict["clip_m2ib"] == "plain" (xai_engine/m2ib.py: the reference's fourth model object is
-    a deep copy of plain CLIP; its ten Adam steps run in closed form behind block 9).  Its text features are NOT a row of
-    `embeddings`: the wrapper's text tower drops the causal mask, reads the last position and projects twice, so the caller passes
-    testing_dict["m2ib_text_features"], the (n_classes, E) table of m2ib.wrapper_text_features; "plain" without that table, or any
-    value of `clip_m2ib` other than None, "modified" and "plain": ValueError.  Optional: testing_dict["m2ib_noise"] ("device", the
-    default, "host" or a tensor) and testing_dict["m2ib_seed"], as m2ib_batch takes them."""
+    """(H,W) float32 numpy saliency map of a row of the reference's get_CLIP_attr (evaluatePerturbation.py:373-445); with
+    testing_dict["device_maps"] the map stays a device tensor.  eclip, eclip_wo, eclip_nograd, maskclip and selfattn
+    (xai_engine/eclip.py) are served on testing_dict["models"][0] with the text normalize(testing_dict["embeddings"][target_class]).
+    game, rollout, lrp, surgery and m2ib run on further model objects in the reference: NotImplementedError naming the model,
+    unless the key of CLIP_PLAIN_ROWS that governs the row is "plain"; then the row is served on models[0] in closed form
+    (xai_engine/clip_attn.py, surgery.py, m2ib.py say why that is the same map), for an input_resolution-square image.  A key's
+    other values are None and "modified" (the default); anything else: ValueError.  surgery also needs
+    testing_dict["surgery_text_features"], the (T - 1, E) features of its context classes (the reference also prompt-ensembles the caption
+    over its 85 templates: a caller who wants that passes an `embeddings` table made that way), and m2ib
+    testing_dict["m2ib_text_features"], the (n_classes, E) table of m2ib.wrapper_text_features, with the optional "m2ib_noise" and
+    "m2ib_seed" of m2ib_batch."""
     from . import eclip
     attr_function = testing_dict["attr_func"]
-    rows = testing_dict.get("clip_attention_rows")
-    if rows not in (None, "modified", "plain"):
-        raise ValueError(f"get_CLIP_attr: clip_attention_rows must be 'plain' or 'modified' (the default), got {rows!r}")
-    if rows == "plain" and attr_function in CLIP_ATTENTION_ROWS:
-        from . import clip_attn
-        clipmodel = testing_dict["models"][0]
-        emb = testing_dict["embeddings"]
-        emb = emb.reshape(-1, emb.shape[-1])
-        txt = torch.nn.functional.normalize(emb[int(target_class)][None], dim=-1)
-        res = int(clipmodel.visual.input_resolution)
-        if tuple(trans_img.shape[1:]) != (res, res):
-            raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} takes the reference's preprocess(img); a "
-                                      f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
-                                      "bicubic resize is not restated here")
-        x = clip_keepsize_input(trans_img, (1, 1))
-        sal = clip_attn.attention_rows_batch(clipmodel, x, txt, attr_function, img_hw=testing_dict["img_hw"])[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
-    surgery_rows = testing_dict.get("clip_surgery")
-    if surgery_rows not in (None, "modified", "plain"):
-        raise ValueError(f"get_CLIP_attr: clip_surgery must be 'plain' or 'modified' (the default), got {surgery_rows!r}")
-    if surgery_rows == "plain" and attr_function == "surgery":
-        from . import surgery
-        context = testing_dict.get("surgery_text_features")
-        if context is None:
-            raise ValueError("get_CLIP_attr: clip_surgery='plain' needs testing_dict['surgery_text_features'], the (T - 1, E) text "
-                             "features of the context classes (59 prompt-ensembled class names in the reference's harness)")
-        clipmodel = testing_dict["models"][0]
-        emb = testing_dict["embeddings"]
-        emb = emb.reshape(-1, emb.shape[-1])
-        if not isinstance(context, torch.Tensor) or context.dim() != 2 or context.shape[1] != emb.shape[1]:
-            raise ValueError(f"get_CLIP_attr: surgery_text_features must be a (T - 1, {emb.shape[1]}) tensor")
-        res = int(clipmodel.visual.input_resolution)
-        if tuple(trans_img.shape[1:]) != (res, res):
-            raise NotImplementedError(f"get_CLIP_attr: the row 'surgery' takes the reference's preprocess(img); a "
-                                      f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
-                                      "bicubic resize is not restated here")
-        txt = torch.nn.functional.normalize(torch.cat([emb[int(target_class)][None].float(), context.to(emb.device).float()]), dim=-1)
-        x = clip_keepsize_input(trans_img, (1, 1))
-        sal = surgery.surgery_batch(clipmodel, x, txt, img_hw=testing_dict["img_hw"])[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
-    m2ib_rows = testing_dict.get("clip_m2ib")
-    if m2ib_rows not in (None, "modified", "plain"):
-        raise ValueError(f"get_CLIP_attr: clip_m2ib must be 'plain' or 'modified' (the default), got {m2ib_rows!r}")
-    if m2ib_rows == "plain" and attr_function == "m2ib":
-        from . import m2ib
-        table = testing_dict.get("m2ib_text_features")
-        if table is None:
-            raise ValueError("get_CLIP_attr: clip_m2ib='plain' needs testing_dict['m2ib_text_features'], the (n_classes, E) table of "
-                             "the M2IB wrapper's text features (m2ib.wrapper_text_features of each class's token ids; they are not "
-                             "encode_text's, so `embeddings` does not serve)")
-        clipmodel = testing_dict["models"][0]
-        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != clipmodel.visual.proj.shape[1]:
-            raise ValueError(f"get_CLIP_attr: m2ib_text_features must be a (n_classes, {clipmodel.visual.proj.shape[1]}) tensor")
-        res = int(clipmodel.visual.input_resolution)
-        if tuple(trans_img.shape[1:]) != (res, res):
-            raise NotImplementedError(f"get_CLIP_attr: the row 'm2ib' takes the reference's preprocess(img); a "
-                                      f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
-                                      "bicubic resize is not restated here")
-        x = clip_keepsize_input(trans_img, (1, 1))
-        sal = m2ib.m2ib_batch(clipmodel, x, table[int(target_class)], img_hw=testing_dict["img_hw"],
-                              noise=testing_dict.get("m2ib_noise", "device"), seed=testing_dict.get("m2ib_seed"))[0]
-        return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
+
+    def result(maps):
+        return maps[0] if testing_dict.get("device_maps") else maps[0].cpu().numpy()
+    for key, rows, serve in CLIP_PLAIN_ROWS:
+        asked = testing_dict.get(key)
+        if asked not in (None, "modified", "plain"):
+            raise ValueError(f"get_CLIP_attr: {key} must be 'plain' or 'modified' (the default), got {asked!r}")
+        if asked == "plain" and attr_function in rows:
+            clipmodel = testing_dict["models"][0]
+            call = serve(testing_dict, clipmodel, target_class)
+            res = int(clipmodel.visual.input_resolution)
+            if tuple(trans_img.shape[1:]) != (res, res):
+                raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} takes the reference's preprocess(img); a "
+                                          f"{trans_img.shape[1]} x {trans_img.shape[2]} image is not the model's {res} x {res}, and PIL's "
+                                          "bicubic resize is not restated here")
+            return result(call(clip_keepsize_input(trans_img, (1, 1))))
     if attr_function in eclip.REFUSED:
         raise NotImplementedError(f"get_CLIP_attr: the row {attr_function!r} needs {eclip.REFUSED[attr_function]}, which this engine "
                                   "does not build")
@@ -383,17 +373,12 @@ def get_CLIP_attr(trans_img, target_class, testing_dict):
         print("Model-attribution mismatch, please use --help.")
         raise SystemExit
     clipmodel = testing_dict["models"][0]
-    img_hw = testing_dict["img_hw"]
-    emb = testing_dict["embeddings"]
-    emb = emb.reshape(-1, emb.shape[-1])
-    txt = torch.nn.functional.normalize(emb[int(target_class)][None], dim=-1)
+    txt = torch.nn.functional.normalize(_class_text(testing_dict, target_class), dim=-1)
     ksize = clipmodel.visual.conv1.kernel_size
     if trans_img.shape[1] % ksize[0] or trans_img.shape[2] % ksize[1]:
         raise NotImplementedError(f"get_CLIP_attr: a {trans_img.shape[1]} x {trans_img.shape[2]} image is not a multiple of the model's "
                                   f"patch size {tuple(ksize)}")
-    x = clip_keepsize_input(trans_img)
-    sal = eclip.eclip_batch(clipmodel, x, txt, attr_function, img_hw=img_hw)[0]
-    return sal if testing_dict.get("device_maps") else sal.cpu().numpy()
+    return result(eclip.eclip_batch(clipmodel, clip_keepsize_input(trans_img), txt, attr_function, img_hw=testing_dict["img_hw"]))
 
 
 def run_perturbation(input_tensor, attribution, testing_dict, CLIP_test_info=None, blur=None):

@@ -97,7 +97,7 @@ def main():
     for row in clip_attn.METHODS:
         lines.append(f"  {row:8s} %9.3f %9.3f %9.3f" % windows_ms(lambda: clip_attn.attention_rows_batch(model, x, txt, row, img_hw=224)))
     visual, blocks, H = clip_attn.check_layout(model, every_block=True)
-    attn, grad = clip_attn._lrp_operands(model, visual, blocks, H, x, txt.unsqueeze(0))
+    attn, grad = clip_attn.lrp_operands(model, visual, blocks, H, x, txt.unsqueeze(0))
     n, _, _, L, _ = attn.shape
     p = clip_attn.cls_rows(model, x)
     g = (torch.randn(1, 1, p.v.shape[2], device=DEV) * 0.01).to(dt)

@@ -38,7 +38,7 @@ def main():
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
-    from xai_engine import clip_attn, m2ib, zoo
+    from xai_engine import clip_tower, m2ib, zoo
     from xai_engine import kernels as K
     if not torch.cuda.is_available():
         raise SystemExit("bench_m2ib: no GPU")
@@ -73,7 +73,7 @@ def main():
         for _ in range(STEPS):
             opt.zero_grad()
             txt = m2ib.wrapper_text_features(model, ids.expand(COPIES, -1))
-            tok = clip_attn._native_tokens(visual, x.expand(COPIES, -1, -1, -1))
+            tok = clip_tower.native_tokens(visual, x.expand(COPIES, -1, -1, -1))
             for blk in blocks[:LAYER + 1]:
                 tok = blk(tok)
             t, cap = bottleneck(alpha, tok.permute(1, 0, 2), torch.randn((COPIES,) + tuple(alpha.shape[1:]), device=DEV))

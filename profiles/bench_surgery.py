@@ -40,7 +40,7 @@ def main():
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
-    from xai_engine import clip_attn, surgery, zoo
+    from xai_engine import clip_tower, surgery, zoo
     from xai_engine import kernels as K
     if not torch.cuda.is_available():
         raise SystemExit("bench_surgery: no GPU")
@@ -84,7 +84,7 @@ def main():
         """the reference's flow for one image as torch operators -> (res, res), text 0"""
         with torch.no_grad():
             blocks = list(tower.transformer.resblocks)
-            tok = clip_attn._native_tokens(tower, x)
+            tok = clip_tower.native_tokens(tower, x)
             for blk in blocks[:-surgery.DUAL_BLOCKS]:
                 tok = blk(tok)
             new = ori = tok
@@ -120,7 +120,7 @@ def main():
         lines += [f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; CLIP ViT-B (random weights, mixed fp16; the row on its "
                   f"fp32 tower), 224 x 224, T = {TEXTS}; device events around a window of calls, median, min, max of {WINDOWS} windows", ""]
     got = surgery.surgery_batch(model, x1, txt, img_hw=224)[0]
-    tower = surgery._fp32_tower(model, visual)
+    tower = surgery.fp32_tower(model, visual)
     want = torch_row(tower, H, x1, txt, 224)
     err = float((got - want).abs().max() / want.abs().max())
     lines.append(f"{name}: the row, ms per image (surgery_batch against the dual-path flow as torch operators: max|diff| / max = {err:.2e})")
